@@ -15,6 +15,11 @@ with the state resident in HBM before the timed region.
 `python -m torch.distributed.run ... bench.py --gpus N` it uses the ranks it is given.  The ladder is then sharded by
 temperature block (64 ranks per GPU, 64*N in the ladder) and rows cross block edges over RCCL.
 
+A plain run sets up, warms up, times the K steps and reports them.  `--full` adds everything else the line can carry: the CPU
+baselines, the ESS leg after the timed region, the short legs of the other BASELINE configs under "also" and, with N > 1, the
+sharded pre-flight check.  `--dump-outputs DIR` writes the state the timed steps left (a fixed, seeded sample of walkers) to
+DIR/<name>.npy, for comparing two builds output for output.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -88,10 +93,16 @@ def make_parser():
                          "once in a hipGraph and replayed -- for small, launch-bound batches (PTEngine.callback_segment_graph)")
     ap.add_argument("--callback-launches", default="one", choices=["one", "two"],
                     help="one: ptmi_accept_propose (the accept test and the next proposal in one launch); two: ptmi_propose + ptmi_accept")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baselines, the ESS leg, the legs of the other configs (--also) and, with --gpus N > 1, "
+                         "the sharded pre-flight check.  Without it a run times the headline's steps and nothing else")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the state they left to DIR/<name>.npy (float64, temperature order): X, lnL, lp, "
+                         "nacc, nswap of a fixed, seeded sample of walkers and the adapted covariance")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--also-child", action="store_true", help=argparse.SUPPRESS)      # the process that runs the "also" legs (spawned by the headline's)
     ap.add_argument("--also", default="auto", choices=["auto", "on", "off"],
-                    help="after the headline's timed region (untouched by them), short legs of the other BASELINE configs on the same GPU, "
+                    help="--full: after the headline's timed region (untouched by them), short legs of the other BASELINE configs on the same GPU, "
                          "reported under \"also\": dense SCAM (configs[2]), default mix, dense default mix, a replica of reference runs "
                          "(per-walker covariance, device QL), config 4's share of one GPU, config 5's share.  auto = when the headline is "
                          "the default workload on one GPU")
@@ -101,7 +112,7 @@ def make_parser():
     ap.add_argument("--cpu-iters", type=int, default=100000, help="iterations per usable host core of the CPU baseline (10-30 s)")
     ap.add_argument("--ess-walkers", type=int, default=16, help="walkers whose T=1 chains the autocorrelation time is estimated from")
     ap.add_argument("--ess-burn", type=int, default=40000, help="the ESS window starts at this iteration at the earliest (adaptation settled)")
-    ap.add_argument("--ess-window", type=int, default=80000, help="iterations of the ESS window, run AFTER the timed region (0 = no ESS)")
+    ap.add_argument("--ess-window", type=int, default=80000, help="--full: iterations of the ESS window, run AFTER the timed region (0 = no ESS)")
     ap.add_argument("--ess-max-seconds", type=float, default=60.0, help="the ESS leg is shortened to fit this (flagged when < 50 tau)")
     return ap
 
@@ -177,6 +188,40 @@ class ColdSamples(object):
                 out[:, its - first] = ring[:, its % cu]
                 have[its - first] = True
         return out[:, have] if out is not None else None
+
+
+DUMP_BYTES = 48 * 10 ** 6      # --dump-outputs: what the files may hold in all (over every rank)
+DUMP_SEED = 20240601           # the walkers sampled when the whole state does not fit
+
+
+def dump_outputs(eng, out_dir, rank=0, world=1):
+    """--dump-outputs: the state the timed steps left, as a caller of the engine reads it -- X, lnL and lp in temperature order
+    (by_temp), the acceptance and swap counters (kept by temperature rank), the adapted covariance -- for the walkers of a fixed,
+    seeded sample when the whole state does not fit DUMP_BYTES.  float64, DIR/<name>.npy (DIR/<name>_rank<r>.npy with several ranks).
+    Selected on the device, so only the sample crosses to the host."""
+    import numpy as np
+    import torch
+    loc = getattr(eng, "local", eng)                              # a sharded ladder: this rank's block
+    W, nt, d, per_walker = loc.W, loc.nt, loc.d, loc.Wc > 1
+    row_bytes = 8 * (nt * d + 3 * nt + loc.ntg + 1 + (d * d if per_walker else 0))
+    fixed = 0 if per_walker else 8 * d * d
+    nw = int(max(1, min(W, (DUMP_BYTES // world - fixed) // row_bytes)))
+    ws = np.arange(W) if nw == W else np.sort(np.random.default_rng(DUMP_SEED).choice(W, nw, replace=False))
+    idx = torch.from_numpy(ws).to(loc.device)
+    t = loc.t
+    slot = t["slot_of"].index_select(0, idx).long()               # [nw][nt]: the slot that holds temperature rank k
+    out = {"walkers": ws,
+           "X": torch.gather(t["X"].index_select(0, idx), 1, slot.unsqueeze(-1).expand(-1, -1, d)),
+           "lnL": torch.gather(t["lnL"].index_select(0, idx), 1, slot),
+           "lp": torch.gather(t["lp"].index_select(0, idx), 1, slot),
+           "nacc": t["nacc"].index_select(0, idx), "nswap": t["nswap"].index_select(0, idx),
+           "cov": t["cov"].index_select(0, idx) if per_walker else loc.get("cov")}
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, v in out.items():
+        v = v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    return nw
 
 
 def cycle_weights(a):
@@ -332,6 +377,9 @@ def measure(a, rank, world, local, dist, backend):
     stored_timed = None
     if getattr(eng, "am_rle", False) and getattr(eng, "owns_cold", False) and hasattr(eng, "t") and eng.t.get("AMflag") is not None:
         stored_timed = float(((eng.t["AMflag"] & 3) != 0).double().mean().item())
+    if getattr(a, "dump_outputs", None):
+        nw = dump_outputs(eng, a.dump_outputs, rank, world)          # what the timed steps left, before the ESS leg moves the chains on
+        log("outputs of the last timed step: %d walkers -> %s" % (nw, a.dump_outputs))
 
     # ---- ESS leg, OUTSIDE the timed wall.  ESS/sec = (walkers x iterations/s of the timed region) / tau_int, with the
     # integrated autocorrelation time of the T = 1 chains estimated where it can be: on a stationary window of >= 50 tau
@@ -669,6 +717,12 @@ def sharded_selfcheck(rank, world, local, dist):
 
 def main():
     a = parse()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        # a plain run: set up, warm up, time the steps, report them -- the ESS leg, the other configs' legs, the CPU baselines and
+        # the sharded pre-flight are --full's
+        a.also, a.ess_window = "off", 0
     if a.also == "auto":
         dflt = parse_defaults()
         a.also = all(getattr(a, k) == getattr(dflt, k) for k in ("ndim", "ntemps", "nwalkers", "mix", "weights", "pick", "logl", "prior", "cov_mode",
@@ -690,7 +744,7 @@ def main():
     weights = cycle_weights(a)
     cpu = None
     # the CPU baseline is timed on rank 0 of the single-GPU run only; the NumPy port covers the Gaussian configs
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.mix != "nuts" and a.logl == "iso":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.mix != "nuts" and a.logl == "iso":
         cpu = cpu_baseline(a, weights)
         log("cpu baseline %.3g updates/s on %d cores" % (cpu["value"], cpu["cores"]))
     import numpy as np
@@ -715,7 +769,7 @@ def main():
         os.write(real_stdout, (json.dumps(also_legs(a, rank, world, local, dist, backend)) + "\n").encode())
         return
     check = None
-    if dist is not None and a.partition == "temps" and world > 1:
+    if a.full and dist is not None and a.partition == "temps" and world > 1:
         try:
             check = sharded_selfcheck(rank, world, local, dist)
             log("sharded selfcheck %s (%.1f s)" % ("ok" if check[0] else "FAILED", check[1]["seconds"]))

@@ -337,7 +337,7 @@ def test_bench_launches_its_own_ranks(extra, ntemps, ngpus):
     args = ["--nwalkers", "128", "--ntemps", "16"] if not extra else list(extra)
     # (three and four ranks: the lnL gather as one grouped send/recv to every peer, DistComm.all_gather; the 1000-d SCAM case: the
     # owner's device factorization with eig_lag = a covariance period, the table broadcast behind the next epoch's statistics)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ngpus), "--steps", "12", "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ngpus), "--steps", "12", "--warmup", "2", "--full", "--no-cpu-baseline",
                         "--ess-burn", "0", "--ess-window", "3000"] + args,
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -6,8 +6,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/sweep_$TAG
 mkdir -p $OUT
 cd $ROOT
-b() { local name=$1; shift; python bench.py --also off "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$?"; }
-python bench.py --steps 20 --warmup 5 > $OUT/driver.json 2> $OUT/driver.err; echo "driver rc=$?"   # exactly what the driver runs (CPU baseline + the legs of the other configs under "also")
+b() { local name=$1; shift; python bench.py --full --also off "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$?"; }
+python bench.py --full --steps 20 --warmup 5 > $OUT/driver.json 2> $OUT/driver.err; echo "driver rc=$?"   # the short line with everything --full adds (CPU baseline + the legs of the other configs under "also")
 b scam --no-cpu-baseline                                         # config 2, default length (200 steps after 100)
 b mix_chain --no-cpu-baseline --mix default --steps 100 --warmup 110
 b mix_walker --no-cpu-baseline --mix default --pick walker --steps 100 --warmup 110
