@@ -594,10 +594,16 @@ __device__ __forceinline__ void draws_for_step(DrawBatch<STR, GW> &b, Draws &dr,
 
 // SCAM-only cycles with one parameter group (the config-2 / config-3 bench kernels): everything of the proposal that is a
 // scalar of the chain -- scale branch, eigen-direction k, amplitude z cd sqrt(S_k) (PT:843-873) -- is computed IN the draw
-// pass, where the four lanes of a chain work on different (iteration, slot) pairs, instead of four times over in the
-// step.  A step then takes three values from the batch (log u from the chain's lane 0; amplitude and direction from lane 1)
-// with five lane moves, and after the first of the two steps the batch rotates by two lanes.  Same operations in the same
-// order as propose(): bit-identical.
+// pass, where the four lanes of a chain work on different iterations, instead of four times over in the step.  Same
+// operations in the same order as propose(): bit-identical.
+// Contiguous layout (QUAD): lane j owns iteration it + j outright -- both Philox slots, the accept test's log u (slot 0 w1),
+// the scale branch (slot 0 w0), the radius log, angle and direction (slot 1) -- so a pass serves four steps with ONE
+// Box-Muller tail per iteration; step s of the pass takes its three values from the chain's lane s (five DPP moves), and
+// the caller refills at the head of every pass of four steps (mh_steps_kernel).  Where lane j evaluated slot j & 1 of
+// iteration it + (j >> 1) instead, every lane ran the whole stream and the even lanes' Box-Muller tails were thrown away.
+// Strided layout (the dense SCAM kernel): the two-iteration pass -- lane j -> slot j & 1 of iteration it + (j >> 1); a step
+// reads log u from the chain's lane 0, amplitude and direction from lane 1; after the first of the two steps the batch
+// rotates by two lanes.
 struct ScamDraw { double log_u, amp; int k; };
 template <bool STR, int GW = 4 /* > 4: wide batch over all GW lanes of the chain */>
 struct ScamBatch {
@@ -616,10 +622,40 @@ struct ScamBatch {
     }
     // root_s(k): sqrt of the k-th eigenvalue of the chain's table; ng: directions to pick from
     // TM / tsm: where the draw tables are read (draw_table): 0 = global memory, 2 = the block's LDS copy when a.tab_off >= 0
+    static constexpr bool QUAD = !STR && GW == 4;
     template <int TM, class RS>
     __device__ __forceinline__ void refill(const KArgs &a, long long it, u32 sid, int gl, const ChainConst &cc, int ng, RS root_s, const double *tsm)
     {
         const int j = GW > 4 ? gl : (gl & 3);
+        if constexpr (QUAD) {
+            // the two generators of iteration it + j interleaved round by round (independent chains of dependent products)
+            PhiloxState ps, qs;
+            philox_begin(ps, a.seed, (u64)(it + j), sid, 0u);
+            philox_begin(qs, a.seed, (u64)(it + j), sid, 1u);
+#pragma unroll
+            for (int r = 0; r < 10; ++r) { philox_round(ps); philox_round(qs); }
+            u64 p0, p1, q0, q1;
+            philox_end(ps, p0, p1);
+            philox_end(qs, q0, q1);
+            u32 aj;
+            double at;
+            unit_angle32((u32)q1, aj, at);
+            const UnitLogArg gu = unit_log_arg(p1), gr = unit_log_arg(q0);     // accept uniform, Box-Muller radius: (0,1] ones
+            double sb, cb;
+            const ptmi_dev_d2 tu = draw_table<TM>(tsm, a.tab_off, gu.slice), tr = draw_table<TM>(tsm, a.tab_off, gr.slice),
+                              tb = draw_table<TM>(tsm, a.tab_off, 32u + aj);      // all reads first
+            kdir = (int)h2index((u32)(q1 >> 32), (u32)ng);              // PT:868
+            const double rs = root_s(kdir);
+            constexpr u32 T97 = (u32)(0.97 * 4294967296.0), T90 = (u32)(0.9 * 4294967296.0);
+            const u32 plo = (u32)p0;                                     // the scale branch (PT:843-858)
+            const int br = plo > T97 ? 0 : (plo > T90 ? 1 : 2);
+            unit_rotation(at, sb, cb);
+            lg = unit_log_finish(gu, tu);                               // log u of the accept test
+            const double lr = unit_log_finish(gr, tr);
+            const double z = det_sqrt(-2.0 * lr) * unit_cos_finish(tb, sb, cb);
+            amp = z * cc.cd_scam(br) * rs;                              // PT:873
+            return;
+        }
         u64 w0, w1;
         philox_words(a.seed, (u64)(it + (j >> 1)), sid, (u32)(j & 1), w0, w1);
         u32 aj;
@@ -652,6 +688,22 @@ struct ScamBatch {
         if constexpr (STR) d.k = __shfl(kdir, (int)(threadIdx.x & 15) + 16, 64);
         else d.k = (int)dpp32<0x55>((u32)kdir);
     }
+    template <int S>
+    __device__ __forceinline__ void take_lane(ScamDraw &d) const             // QUAD: the values of the chain's lane S
+    {
+        d.log_u = dppf64<S * 0x55>(lg);                             // quad_perm [S,S,S,S]
+        d.amp = dppf64<S * 0x55>(amp);
+        d.k = (int)dpp32<S * 0x55>((u32)kdir);
+    }
+    __device__ __forceinline__ void take_quad(ScamDraw &d, int s) const      // QUAD: step s of the pass (wave-uniform)
+    {
+        switch (s) {
+        case 0: take_lane<0>(d); break;
+        case 1: take_lane<1>(d); break;
+        case 2: take_lane<2>(d); break;
+        default: take_lane<3>(d); break;
+        }
+    }
     __device__ __forceinline__ void take_wide(ScamDraw &d, int s) const      // step s of the pass
     {
         d.log_u = chain_lanef<GW>(lg, 2 * s);
@@ -665,6 +717,10 @@ __device__ __forceinline__ void scam_draws_for_step(ScamBatch<STR, GW> &b, ScamD
 {
     if constexpr (GW > 4) {                            // the caller refills at the head of every pass of GW / 2 steps (mh_steps_kernel)
         b.take_wide(dr, k & (GW / 2 - 1));
+        return;
+    }
+    if constexpr (ScamBatch<STR, GW>::QUAD) {          // the caller refills at the head of every pass of four steps (mh_steps_kernel)
+        b.take_quad(dr, k & 3);
         return;
     }
     if ((k & 1) == 0) b.template refill<TM>(a, a.iter0 + k, sid, gl, cc, ng, root_s, tsm);
@@ -1288,13 +1344,31 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
 
     // Wide draw batches: a pass serves GW / 2 steps, so the steps run as an inner loop under a loop over the passes -- with the
     // refill as a rarely taken branch of ONE loop the compiler hoisted the pass's invariants (Philox key schedule, polynomial
-    // constants, per-slot bounds) over the steps and spilled the steps' own values to make room (73 registers at a budget of 128)
-    constexpr int KPASS = GW > 4 ? GW / 2 : (1 << 30);
+    // constants, per-slot bounds) over the steps and spilled the steps' own values to make room (73 registers at a budget of 128).
+    // The four-lane SCAM batch of the contiguous layout (ScamBatch::QUAD) likewise: a pass of four steps, one iteration per lane.
+    // A launch whose length is no multiple of four ends in a short pass whose extra lanes computed draws nobody reads.
+    constexpr bool SQUAD = SCAMFAST && ScamBatch<STR, GW>::QUAD;
+    constexpr bool PASSES = GW > 4 || SQUAD;
+    constexpr int KPASS = GW > 4 ? GW / 2 : (SQUAD ? 4 : (1 << 30));
+    // sqrt(S_k): from the block's LDS copy where it has one, else from the chain's table (sqrt is correctly rounded: same bits)
+    // ULDS: the draw tables too come from the block's LDS when the host found room (a.tab_off >= 0).  Global reads share
+    // the in-order vector-memory counter with the cold chain's AM-row stores: in the block's one cold wave every draw
+    // pass waited for 25 stores to retire first
+    // PERS: the host always places the tables (launch_mh_k), so the read is an LDS read at COMPILE time: with the run-time
+    // choice (TM = 2) the two paths merged in an s_waitcnt vmcnt(0) -- every draw pass of a cold wave waited for its AM-row
+    // stores to retire, although it never took the global path
+    constexpr int STM = (PERS || TLDS) ? 1 : (ULDS ? 2 : 0);
+    auto scam_root_s = [&](int kk) {
+        if (ULDS && !ulds_box) return smem[d * d + kk];
+        return det_sqrt(S[kk]);
+    };
     for (int k0 = 0; k0 < a.nsteps; k0 += KPASS) {
-    const int kend = (GW > 4 && a.nsteps - k0 > KPASS) ? k0 + KPASS : a.nsteps;
+    const int kend = (PASSES && a.nsteps - k0 > KPASS) ? k0 + KPASS : a.nsteps;
     if constexpr (GW > 4) {
         if constexpr (SCAMFAST) sbatch.template refill<0>(a, a.iter0 + k0, sid, gl, cc, d, [&](int kk) { return det_sqrt(S[kk]); }, nullptr);
         else batch.template refill<TM>(a, a.iter0 + k0, sid, gl, tsm);
+    } else if constexpr (SQUAD) {
+        sbatch.template refill<STM>(a, a.iter0 + k0, sid, gl, cc, d, scam_root_s, smem);
     }
     for (int k = k0; k < kend; ++k) {
         const long long it = a.iter0 + k;
@@ -1357,17 +1431,7 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
         double scam_amp = 0.0, box_reach = 0.0;
         if constexpr (SCAMFAST) {
             ScamDraw sd;
-            // sqrt(S_k): from the block's LDS copy where it has one, else from the chain's table (sqrt is correctly rounded: same bits)
-            // ULDS: the draw tables too come from the block's LDS when the host found room (a.tab_off >= 0).  Global reads share
-            // the in-order vector-memory counter with the cold chain's AM-row stores: in the block's one cold wave every draw
-            // pass waited for 25 stores to retire first
-            // PERS: the host always places the tables (launch_mh_k), so the read is an LDS read at COMPILE time: with the run-time
-            // choice (TM = 2) the two paths merged in an s_waitcnt vmcnt(0) -- every draw pass of a cold wave waited for its AM-row
-            // stores to retire, although it never took the global path
-            scam_draws_for_step<STR, (PERS || TLDS) ? 1 : (ULDS ? 2 : 0), GW>(sbatch, sd, a, k, sid, gl, cc, d, [&](int kk) {
-                if (ULDS && !ulds_box) return smem[d * d + kk];
-                return det_sqrt(S[kk]);
-            }, smem);
+            scam_draws_for_step<STR, STM, GW>(sbatch, sd, a, k, sid, gl, cc, d, scam_root_s, smem);
             log_u = sd.log_u;
             if constexpr (PAIRED) {
                 const double *row = smem + (size_t)sd.k * d;
