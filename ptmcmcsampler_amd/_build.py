@@ -12,13 +12,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 OUT = os.path.join(HERE, "libptmi.so")
+MAP = os.path.join(CSRC, "ptmi.map")     # linker version script: the C ABI (ptmi_*) is the library's only export
 
 
 def deps():
-    """Every source the library is built from: all of csrc/*.hip, csrc/*.h and the public header."""
+    """Every source the library is built from: all of csrc/*.hip, csrc/*.h, the version script and the public header."""
     import glob
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h"))) + [
-        os.path.join(os.path.dirname(HERE), "include", "ptmi.h")]
+        MAP, os.path.join(os.path.dirname(HERE), "include", "ptmi.h")]
 
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"] + os.environ.get("PTMI_EXTRA_CXXFLAGS", "").split()
@@ -80,7 +81,7 @@ def build(force=False, verbose=False, jobs=None):
         print("compiling %d translation units with %d workers" % (len(work), jobs))
     with concurrent.futures.ThreadPoolExecutor(jobs) as pool:
         objs = list(pool.map(_compile, work))
-    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT + ".tmp"] + objs)
+    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + MAP, "-o", OUT + ".tmp"] + objs)
     os.replace(OUT + ".tmp", OUT)
     return OUT
 

@@ -2,7 +2,6 @@
 // (swap sweep, Welford / pooling, DE ring, self-tests).  See include/ptmi.h for the boundary and DESIGN.md.
 #include <math.h>
 #include <stdlib.h>
-#include <dlfcn.h>
 
 #include <new>
 #include <mutex>
@@ -10,8 +9,6 @@
 
 #include <type_traits>
 
-#include <rocblas/internal/rocblas-types.h>          // enum values only (ptmi_eig_sytrd calls the library through dlsym, nothing is linked)
-#include <rocsolver/rocsolver-extra-types.h>
 #include "ptmi_common.h"
 
 // ------------------------------------------------------------------ errors
@@ -2289,10 +2286,6 @@ static KArgs make_args(ptmi_engine *h)
     const ptmi_buffers &b = h->buf;
     a.X = b.X; a.lnL = b.lnL; a.lp = b.lp; a.temp_of = b.temp_of; a.slot_of = b.slot_of;
     a.Ut = b.Ut; a.S = b.S; a.DE = b.DE; a.AM = c.temp0 == 0 ? b.AM : nullptr; a.AMaux = c.temp0 == 0 ? b.AMaux : nullptr;
-#ifdef PTMI_MEASURE      // measurement builds only (-DPTMI_MEASURE; results are wrong): what the AM-row stores of the step kernels cost
-    static const bool no_am = getenv("PTMI_MEASURE_NO_AM") != nullptr;
-    if (no_am) a.AM = nullptr;
-#endif
     a.AMflag = c.temp0 == 0 ? (AmFlag *)b.AMflag : nullptr;
     a.rp_draws = h->rp_draws;
     a.nacc = (u64 *)b.nacc; a.jstat = (u64 *)b.jstat;
@@ -2338,10 +2331,6 @@ static int set_step_args(const ptmi_engine *h, KArgs *a)
 {
     const ptmi_config &c = h->cfg;
     a->am_row0 = (int)(a->iter0 % c.cov_update);
-#ifdef PTMI_MEASURE      // measurement builds only (-DPTMI_MEASURE; results are wrong): every AM row of a walker into ONE cache-resident row
-    static const bool am_small = getenv("PTMI_MEASURE_AM_SMALL") != nullptr;
-    if (am_small) { a->cov_update = 1; a->am_row0 = 0; }
-#endif
     if (a->AMflag != nullptr && a->nsteps > 0 && (a->iter0 - 1) / c.cov_update != (a->iter0 + a->nsteps - 2) / c.cov_update && a->iter0 > 0)
         return fail(PTMI_EINVAL, "with AM row flags a launch may not cross a multiple of cov_update (iterations %lld..%lld, cov_update=%d)",
                     a->iter0, a->iter0 + a->nsteps - 1, c.cov_update);
@@ -2579,25 +2568,23 @@ int ptmi_create(const ptmi_config *cfg, const ptmi_buffers *buf, ptmi_handle *ou
         const size_t nvec = (size_t)GJV_TOP + (size_t)GJL_VECS * (c.nuts_maxdepth + 1);
         hipError_t e3 = hipMalloc((void **)&h->d_gj_scr, sizeof(double) * nvec * lanes * nch);
         if (e3 == hipSuccess) e3 = hipMalloc((void **)&h->d_gj_scal, sizeof(double) * (size_t)GJS_SCALARS * (c.nuts_maxdepth + 1) * nch);
-        static const bool unordered = getenv("PTMI_GJ_UNORDERED") != nullptr;        // measurement switch: same results either way
         // chains with a wave of their own (the longest trees of the launch order): up to 1024, a 32nd of the chains at most (config-5 share
         // with 0 / 128 / 512 / 1024 / 2048 of 65 536: 4.67e8 / 4.92e8 / 4.82e8 / 5.37e8 / 5.18e8 updates/s); PTMI_GJ_SOLO=n overrides (0: none; a
-        // measurement / test switch: the order never enters a chain's arithmetic)
+        // test hook: the order never enters a chain's arithmetic)
         const int cpw = 64 / s.G;
-        long long solo = cpw > 1 ? (long long)(nch / 32 < 1024 ? nch / 32 : 1024) : 0;
-        if (const char *ev = getenv("PTMI_GJ_SOLO")) solo = cpw > 1 ? atoll(ev) : 0;
+        long long solo = cpw > 1 ? (long long)ptmi_env("PTMI_GJ_SOLO", (double)(nch / 32 < 1024 ? nch / 32 : 1024)) : 0;
         if (solo > (long long)nch) solo = (long long)nch;
         if (solo < 0) solo = 0;
         h->gj_solo = (int)solo;
-        if (e3 == hipSuccess && !unordered) e3 = hipMalloc((void **)&h->d_gj_order, sizeof(int32_t) * (nch + (size_t)solo * cpw + cpw));
-        if (e3 == hipSuccess && !unordered) e3 = hipMalloc((void **)&h->d_gj_bucket, sizeof(int32_t) * 3 * GJ_BUCKETS);
+        if (e3 == hipSuccess) e3 = hipMalloc((void **)&h->d_gj_order, sizeof(int32_t) * (nch + (size_t)solo * cpw + cpw));
+        if (e3 == hipSuccess) e3 = hipMalloc((void **)&h->d_gj_bucket, sizeof(int32_t) * 3 * GJ_BUCKETS);
         if (e3 != hipSuccess || (rc = upload(&h->d_gj_tab, c.gj_tab, 3LL * c.ndim * c.ndim))) {
             ptmi_destroy(h);
             return e3 != hipSuccess ? fail(PTMI_EHIP, "gradient-jump scratch: %s", hipGetErrorString(e3)) : rc;
         }
         // diagonal whitening (cov0 diagonal: the curved-likelihood runs start from the identity): a product is d multiplications
-        // (the oracle's tab_vec defines the same rule); PTMI_GJ_NODIAG: the general product (a measurement / test switch)
-        h->gj_diag = getenv("PTMI_GJ_NODIAG") == nullptr;
+        // (the oracle's tab_vec defines the same rule)
+        h->gj_diag = 1;
         for (long long i = 0; i < 3LL * c.ndim * c.ndim && h->gj_diag; ++i) {
             const long long r = (i / c.ndim) % c.ndim, col = i % c.ndim;
             if (r != col && c.gj_tab[i] != 0.0) h->gj_diag = 0;
@@ -2629,12 +2616,12 @@ int ptmi_create(const ptmi_config *cfg, const ptmi_buffers *buf, ptmi_handle *ou
     // -- and the SPLIT path of every shape (ptmi_propose / ptmi_accept_propose on contiguous rows, csrc/ptmi_split.hip): an AM pick's 2 d^2
     // flop belong on the matrix cores there too; the row kernel reads the increment as it reads a SCAM direction.  For handles the fused
     // kernels do not take this way (4 lanes per chain, one group: their own matrix-core product) the scratch serves the split path alone.
-    const bool am_main = c.w_am > 0 && (c.ngroups > 1 || s.G > 4) && c.ndim <= 1024 && c.w_host == 0 && !getenv("PTMI_NO_AM_AHEAD");
-    const bool am_split = !am_main && buf->Q != nullptr && c.w_am > 0 && c.ndim <= 1024 && c.w_host == 0 && !getenv("PTMI_NO_SPLIT_AM");
+    const bool am_main = c.w_am > 0 && (c.ngroups > 1 || s.G > 4) && c.ndim <= 1024 && c.w_host == 0;
+    const bool am_split = !am_main && buf->Q != nullptr && c.w_am > 0 && c.ndim <= 1024 && c.w_host == 0;
     if (e == hipSuccess && (am_main || am_split)) {
         const long long nch = (long long)c.nwalkers * c.ntemps;
-        const char *mb = getenv(am_main ? "PTMI_AM_BUDGET_MB" : "PTMI_SPLIT_AM_BUDGET_MB");     // scratch for the increments of one piece (default 6 GB; 2 GB for the split path alone)
-        const double budget = (mb ? atof(mb) : (am_main ? 6144.0 : 2048.0)) * 1048576.0;
+        // scratch for the increments of one piece (6 GB; 2 GB for the split path alone)
+        const double budget = (am_main ? ptmi_env("PTMI_AM_BUDGET_MB", 6144.0) : ptmi_env("PTMI_SPLIT_AM_BUDGET_MB", 2048.0)) * 1048576.0;
         long long piece = (long long)(budget / ((double)c.ndim * 8.0 * (double)nch));
         piece = piece < 1 ? 1 : (piece > 64 ? 64 : piece);
         if ((c.ngroups > 1 || c.cov_per_walker) && nch * piece > 0x7FFFFFFFLL) piece = 0x7FFFFFFFLL / nch;      // (the group lists index the events with 32 bits; nch itself is below 2^32 / ntemps)
@@ -2688,11 +2675,6 @@ int ptmi_destroy(ptmi_handle h)
     free(h->gsize_host);
     dc_plan_free(h);
     if (h->h_sy_info) (void)hipHostFree(h->h_sy_info);
-    if (h->sy_lib) {                                                // SyLib: the library's handle, its destructor
-        void **sl = (void **)h->sy_lib;
-        if (sl[0] && sl[1]) ((int (*)(void *))sl[1])(sl[0]);
-        free(h->sy_lib);
-    }
     (void)hipFree(h->d_rle_ent); (void)hipFree(h->d_rle_cnt);
     (void)hipFree(h->d_am_ev); (void)hipFree(h->d_am_count); (void)hipFree(h->d_am_base); (void)hipFree(h->d_am_inc);
     (void)hipFree(h->d_am_grp); (void)hipFree(h->d_am_perm); (void)hipFree(h->d_am_kbase); (void)hipFree(h->d_am_next); (void)hipFree(h->d_iter);
@@ -2754,8 +2736,7 @@ static int make_ut_pad(ptmi_engine *h, KArgs *a)
     a->UtPad = nullptr;
     a->ut_pad_ld = 0;
     a->ut_absmax = nullptr;
-    static const bool off = getenv("PTMI_NO_UTPAD") != nullptr;       // measurement / test switch: same results either way
-    if (h->G <= 4 || c.cov_per_walker || c.ngroups > 1 || off) return PTMI_OK;
+    if (h->G <= 4 || c.cov_per_walker || c.ngroups > 1) return PTMI_OK;
     const int ld = h->G * h->EPL;
     if (!h->d_utpad) HIPCHK(hipMalloc((void **)&h->d_utpad, sizeof(double) * ((size_t)c.ndim * ld + 2)));
     unsigned long long *amax = (unsigned long long *)(h->d_utpad + (size_t)c.ndim * ld);
@@ -3092,7 +3073,7 @@ static int launch_swap_sweep(ptmi_engine *h, int W, int n, const SwapPre *pre, i
 
 // The sweep with its records made in the block (swap_fused_kernel) when its tables and the ring fit the LDS; *used says whether it
 // was launched (else the caller runs swap_prepare_kernel + swap_sweep_kernel).  PTMI_SWAP_FUSED=0: the two-kernel form (a
-// measurement / test switch, same results).
+// test hook, same results).
 static int launch_swap_fused(ptmi_engine *h, int W, int n, const SwapSrc &src, int32_t *slot_of, int32_t *temp_of, int32_t *map, u64 *nswap,
                              int local0, int nlocal, int parity, int32_t *inv, int hop_nt, bool *hop_done, const SwapAmRow *amr, bool *am_done,
                              bool *used)
@@ -3100,12 +3081,11 @@ static int launch_swap_fused(ptmi_engine *h, int W, int n, const SwapSrc &src, i
     *used = false;
     if (hop_done) *hop_done = false;
     if (am_done) *am_done = false;
-    const char *sw = getenv("PTMI_SWAP_FUSED");                     // read per call: the tests switch it
-    if (sw && atoi(sw) == 0) return PTMI_OK;
+    if (!ptmi_env("PTMI_SWAP_FUSED", 1)) return PTMI_OK;
     // walkers per block: 16 puts the 4096 walkers of config 2 on every CU (64 per block ran on 64 CUs: 31 -> 24 us per swap epoch
-    // at 64 ranks; 8 starve the producers: 38); long ladders are cut further by the LDS their tables need.  PTMI_SWF_WPB: a measurement switch
-    int wpb = 64, lg = 6, want = n <= 128 ? 16 : 32;               // 256 ranks: 94 us with 32 or 64, 104 with 16
-    if (const char *wv = getenv("PTMI_SWF_WPB")) want = atoi(wv);
+    // at 64 ranks; 8 starve the producers: 38); long ladders are cut further by the LDS their tables need
+    int wpb = 64, lg = 6;
+    const int want = n <= 128 ? 16 : 32;                           // 256 ranks: 94 us with 32 or 64, 104 with 16
     while (wpb > 8 && wpb > want) { wpb /= 2; --lg; }
     while (wpb > 8 && swf_lds_bytes(wpb, n) > 160 * 1024) { wpb /= 2; --lg; }
     const size_t lds = swf_lds_bytes(wpb, n);
@@ -3441,7 +3421,7 @@ int ptmi_update_cov_on(ptmi_handle hh, int64_t iter, void *stream, const double 
     if (iter < c.cov_update || iter % c.cov_update) return fail(PTMI_EINVAL, "iter must be a positive multiple of cov_update");
     const int d = c.ndim, nt = (d + WTILE - 1) / WTILE;
     if (c.cov_per_walker) {
-        if (d <= 100 && !getenv("PTMI_WELFORD_TILES"))
+        if (d <= 100)
             hipLaunchKernelGGL((welford_rows_kernel<25, 10, 4, 10>), dim3((c.nwalkers + 1) / 2), dim3(768), 0, h->stream, (const double *)h->buf.AM,
                                h->buf.mu, h->buf.M2, h->buf.cov, d, c.cov_update, (long long)iter, d * d, am_row_epl(h->G, h->EPL), c.nwalkers);
         else
@@ -3532,8 +3512,7 @@ static int eig_ql_run(ptmi_engine *h, int n, int nmat, const double *cov, double
     const int d = n, dmax = c.ndim;
     const size_t lds = sizeof(double) * ((((size_t)d * d + 1) & ~(size_t)1) + 2 * (size_t)d);
     if (lds > 160 * 1024 || d > 128) return fail(PTMI_EUNSUPPORTED, "the QL eigensolver keeps the %d x %d matrix in LDS: ndim <= 128", d, d);
-    const char *sp = getenv("PTMI_QL_SPLIT");                           // 1 / 0 forces the three-kernel / the one-kernel form (tests, measurements)
-    const bool split = sp ? atoi(sp) != 0 : nmat >= 64;
+    const bool split = ptmi_env("PTMI_QL_SPLIT", nmat >= 64) != 0;    // 1 / 0 forces the three-kernel / the one-kernel form (a test hook)
     if (split) {
         // many matrices: reduce -> the scalar chains of all of them at once -> apply (see eig_ql_chain_kernel)
         const int cap = 3 * d * d, capit = 8 * d;
@@ -3559,7 +3538,7 @@ static int eig_ql_run(ptmi_engine *h, int n, int nmat, const double *cov, double
         }
         hipLaunchKernelGGL(eig_ql_reduce_kernel, dim3(nmat), dim3(QLR_THREADS), lds, h->stream, cov, d, q);
         hipLaunchKernelGGL(eig_ql_chain_kernel, dim3(nmat), dim3(64), sizeof(double) * 2 * (size_t)d, h->stream, d, q);
-        const bool regs = d <= QLA_N && !getenv("PTMI_QL_APPLY_LDS");
+        const bool regs = d <= QLA_N;
         if (regs)
             hipLaunchKernelGGL(eig_ql_apply_reg_kernel, dim3(nmat), dim3(128), 0, h->stream, Ut, S, d, d * d, d, (const double *)q.z,
                                (const double *)q.ev, (const qls_d2 *)q.rot, (const int32_t *)q.hdr, (const int32_t *)q.cnt, cap, capit);
@@ -3658,8 +3637,8 @@ int ptmi_eig_ql_from(ptmi_handle h, void *stream, const double *cov_in, double *
 //   every block: p_j = tau (column j . v) for ITS columns (A symmetric: column j is row j)  -> p to all      [grid barrier]
 //   every block: w = p - (tau/2 p.v) v, its columns -= v w_j + w v_j
 // -- no reduction across blocks, two barriers per column (a few microseconds each on an atomic counter).  Output in LAPACK's
-// dsytrd format (uplo = lower: d, e, tau, the reflectors below the subdiagonal), so that the library's divide-and-conquer solver
-// for the tridiagonal matrix (rocsolver_dstedc) and its back-transformation (rocsolver_dormtr) take it from there.
+// dsytrd format (uplo = lower: d, e, tau, the reflectors below the subdiagonal), from which the divide-and-conquer solver for the
+// tridiagonal matrix and its back-transformation through the reflectors (dc_solve) take it.
 struct SytrdArgs {
     double *A;             // [n][n] column-major = row-major (symmetric in); out: the reflectors
     double *D, *E, *tau;   // [n], [n - 1], [n - 1]
@@ -3967,39 +3946,6 @@ static int dc_solve(ptmi_engine *h, hipStream_t st, int n, const double *D, cons
     return PTMI_OK;
 }
 
-// the library's entry points, looked up in the copies the process has loaded already (torch brings its own librocsolver / librocblas;
-// a second copy from /opt/rocm beside them is not wanted)
-struct SyLib {
-    void *blas_handle;                     // first two members: ptmi_destroy releases the handle through them
-    int (*destroy_handle)(void *);
-    int (*create_handle)(void **);
-    int (*set_stream)(void *, hipStream_t);
-    int (*dstedc)(void *, int, int, double *, double *, double *, int, int *);
-    int (*dormtr)(void *, int, int, int, int, int, double *, int, double *, double *, int);
-};
-static int sy_lib_get(ptmi_engine *h, SyLib **out)
-{
-    if (h->sy_lib) { *out = (SyLib *)h->sy_lib; return PTMI_OK; }
-    void *sol = nullptr, *bla = nullptr;
-    for (const char *nm : {"librocsolver.so.0", "librocsolver.so"}) if (!sol) sol = dlopen(nm, RTLD_NOW | RTLD_NOLOAD);
-    for (const char *nm : {"librocblas.so.5", "librocblas.so.4", "librocblas.so"}) if (!bla) bla = dlopen(nm, RTLD_NOW | RTLD_NOLOAD);
-    if (!sol) sol = dlopen("librocsolver.so.0", RTLD_NOW);
-    if (!bla) bla = dlopen("librocblas.so.5", RTLD_NOW);
-    if (!sol || !bla) return fail(PTMI_EUNSUPPORTED, "ptmi_eig_sytrd needs the ROCm libraries librocsolver / librocblas in the process (import torch first): %s", dlerror());
-    SyLib *L = (SyLib *)calloc(1, sizeof(SyLib));
-    if (!L) return fail(PTMI_EHIP, "out of memory");
-    L->destroy_handle = (int (*)(void *))dlsym(bla, "rocblas_destroy_handle");
-    L->create_handle = (int (*)(void **))dlsym(bla, "rocblas_create_handle");
-    L->set_stream = (int (*)(void *, hipStream_t))dlsym(bla, "rocblas_set_stream");
-    L->dstedc = (int (*)(void *, int, int, double *, double *, double *, int, int *))dlsym(sol, "rocsolver_dstedc");
-    L->dormtr = (int (*)(void *, int, int, int, int, int, double *, int, double *, double *, int))dlsym(sol, "rocsolver_dormtr");
-    if (!L->create_handle || !L->set_stream || !L->dstedc || !L->dormtr) { free(L); return fail(PTMI_EUNSUPPORTED, "rocsolver_dstedc / rocsolver_dormtr not found"); }
-    if (L->create_handle(&L->blas_handle) != 0) { free(L); return fail(PTMI_EHIP, "rocblas_create_handle failed"); }
-    h->sy_lib = L;
-    *out = L;
-    return PTMI_OK;
-}
-
 int ptmi_eig_sytrd(ptmi_handle h, void *stream, double *Ut_out, double *S_out) { return ptmi_eig_sytrd_from(h, stream, nullptr, Ut_out, S_out); }
 
 int ptmi_eig_sytrd_from(ptmi_handle h, void *stream, const double *cov_in, double *Ut_out, double *S_out)
@@ -4018,7 +3964,6 @@ int ptmi_eig_sytrd_from(ptmi_handle h, void *stream, const double *cov_in, doubl
     HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
     int nb = ncu / 4 > 0 ? ncu / 4 : 1;                             // 64 blocks: the barrier's cost grows with them (21.1 ms at 64, 23.1 at 128, 27.8 at 256)
     while ((n + nb - 1) / nb > SY_CMAX && nb < ncu) nb *= 2;
-    if (const char *e = getenv("PTMI_SYTRD_BLOCKS")) nb = atoi(e);
     if (nb > ncu) nb = ncu;
     if (nb > n) nb = n;
     if (n < 3 || (n + nb - 1) / nb > SY_CMAX) return fail(PTMI_EUNSUPPORTED, "ptmi_eig_sytrd: 3 <= ndim <= %d on this device", SY_CMAX * nb);
@@ -4027,8 +3972,8 @@ int ptmi_eig_sytrd_from(ptmi_handle h, void *stream, const double *cov_in, doubl
     if (lds > 160 * 1024 || n > 1024) return fail(PTMI_EUNSUPPORTED, "ptmi_eig_sytrd: ndim = %d does not fit the LDS", n);
     (void)cpb;
     const size_t nn = (size_t)n * n;
-    if (!h->d_sy_scr) HIPCHK(hipMalloc(&h->d_sy_scr, sizeof(double) * (2 * nn + 8 * (size_t)n + 64) + 256));
-    double *A = (double *)h->d_sy_scr, *Cm = A + nn, *D = Cm + nn, *E = D + n, *tau = E + n, *vbuf = tau + n, *pbuf = vbuf + 2 * (n + 2);
+    if (!h->d_sy_scr) HIPCHK(hipMalloc(&h->d_sy_scr, sizeof(double) * (nn + 8 * (size_t)n + 64) + 256));
+    double *A = (double *)h->d_sy_scr, *D = A + nn, *E = D + n, *tau = E + n, *vbuf = tau + n, *pbuf = vbuf + 2 * (n + 2);
     unsigned *bar = (unsigned *)(pbuf + 2 * n + 2);
     int *info = (int *)(bar + 4);
     HIPCHK(hipMemcpyAsync(A, cov_in, sizeof(double) * nn, hipMemcpyDeviceToDevice, st));
@@ -4055,37 +4000,18 @@ int ptmi_eig_sytrd_from(ptmi_handle h, void *stream, const double *cov_in, doubl
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(last[di], st));
     }
-    static const bool use_lib = getenv("PTMI_SYTRD_LIB") != nullptr;   // measurement switch: round 4's path, the library's divide-and-conquer solver and back-transformation
-    if (!use_lib) {
-        // the tridiagonal matrix's eigenvectors by the engine's own divide-and-conquer kernels, back-transformed through the reflectors
-        const double *Dres = nullptr, *Zres = nullptr;
-        if (int rc = dc_solve(h, st, n, D, E, A, tau, &Dres, &Zres, info)) return rc;
-        hipLaunchKernelGGL(eig_sort_rows_kernel, dim3(n), dim3(256), 0, st, Dres, Zres, n, Uo, So);
-        HIPCHK(hipGetLastError());
-        // the convergence word (a leaf's QL iteration: dc::leaf_kernel) follows the result to the host on the same stream
-        if (!h->h_sy_info) {
-            HIPCHK(hipHostMalloc((void **)&h->h_sy_info, 2 * sizeof(int32_t)));
-            h->h_sy_info[0] = 0; h->h_sy_info[1] = 0;
-        }
-        HIPCHK(hipMemcpyAsync(h->h_sy_info, info, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        return PTMI_OK;
-    }
-    SyLib *L = nullptr;
-    if (int rc = sy_lib_get(h, &L)) return rc;
-    if (L->set_stream(L->blas_handle, st) != 0) return fail(PTMI_EHIP, "rocblas_set_stream failed");
-    // eigenvectors of the tridiagonal matrix (columns of C), then C := Q C with the reflectors of the reduction
-    int rs = L->dstedc(L->blas_handle, (int)rocblas_evect_tridiagonal, n, D, E, Cm, n, info);
-    if (rs != 0) return fail(PTMI_EHIP, "rocsolver_dstedc: status %d", rs);
-    // the solver's convergence word follows the result to the host on the same stream (ptmi_eig_sytrd_info reads the last one that arrived)
+    // the tridiagonal matrix's eigenvectors by the engine's own divide-and-conquer kernels, back-transformed through the reflectors
+    const double *Dres = nullptr, *Zres = nullptr;
+    if (int rc = dc_solve(h, st, n, D, E, A, tau, &Dres, &Zres, info)) return rc;
+    hipLaunchKernelGGL(eig_sort_rows_kernel, dim3(n), dim3(256), 0, st, Dres, Zres, n, Uo, So);
+    HIPCHK(hipGetLastError());
+    // the convergence word (a leaf's QL iteration: dc::leaf_kernel) follows the result to the host on the same stream
+    // (ptmi_eig_sytrd_info reads the last one that arrived)
     if (!h->h_sy_info) {
         HIPCHK(hipHostMalloc((void **)&h->h_sy_info, 2 * sizeof(int32_t)));
         h->h_sy_info[0] = 0; h->h_sy_info[1] = 0;
     }
     HIPCHK(hipMemcpyAsync(h->h_sy_info, info, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    rs = L->dormtr(L->blas_handle, (int)rocblas_side_left, (int)rocblas_fill_lower, (int)rocblas_operation_none, n, n, A, n, tau, Cm, n);
-    if (rs != 0) return fail(PTMI_EHIP, "rocsolver_dormtr: status %d", rs);
-    hipLaunchKernelGGL(eig_sort_rows_kernel, dim3(n), dim3(256), 0, st, (const double *)D, (const double *)Cm, n, Uo, So);
-    HIPCHK(hipGetLastError());
     return PTMI_OK;
 }
 

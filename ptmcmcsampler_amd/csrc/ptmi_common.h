@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/ptmi.h"
@@ -13,6 +14,26 @@ using namespace ptmi;
 // thread-local error message of the C ABI (defined in ptmi_abi.hip)
 int ptmi_fail(int code, const char *fmt, ...);
 #define fail ptmi_fail
+// Test hooks: environment variables that let the tests reach a variant on a small configuration.  Each one only selects which
+// kernel or which launch layout runs: the results are the same bits for any value.  They are read at the point of use, on every
+// call, so that a test may switch them between calls.  Unset: the default in brackets.
+//   PTMI_NO_PC               nonzero: AM cycles keep the one-wave staged kernel with its AM queue, not mh_pc_kernel [0]
+//   PTMI_SWAP_FUSED          0: the swap as swap_prepare_kernel + swap_sweep_kernel, not swap_fused_kernel [1]
+//   PTMI_ULDS_PERS           0: SCAM-only cycles with one table take a table copy per block, not the persistent kernel [1]
+//   PTMI_SPLIT_ROWS          0: the split path through the shape kernels' propose / accept, not the row kernels [1]
+//   PTMI_QL_SPLIT            1 / 0: ptmi_eig_ql as reduce -> chain -> apply / as one kernel per matrix [1 from 64 matrices on]
+//   PTMI_GJ_SOLO             chains with a wave of their own in the gradient-jump launch order [a 32nd of the chains, at most 1024]
+//   PTMI_GJ_LDS_LEVELS       heights of the NUTS tree stack kept in LDS, the rest in global scratch [11]
+//   PTMI_GJ_NOPAIR           nonzero: diagonal tables at 4 lanes per chain run one chain per wave, not two [0]
+//   PTMI_GJ_NOWIDE16         nonzero: the 16-lane gradient-jump shape runs the per-chain layout, not the whole-wave one [0]
+//   PTMI_AM_BUDGET_MB        MB of scratch for the AM increments computed ahead of a launch (smaller: more pieces) [6144]
+//   PTMI_SPLIT_AM_BUDGET_MB  the same for the split path alone [2048]
+inline double ptmi_env(const char *name, double dflt)
+{
+    const char *v = getenv(name);
+    return v ? strtod(v, nullptr) : dflt;
+}
+
 #define HIPCHK(expr)                                                                          \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
@@ -163,7 +184,6 @@ struct ptmi_engine {
     double *d_utpad;             // zero-padded copy of the pooled eigenvector table for the 16- / 64-lane shapes (KArgs::UtPad)
     void *d_sy_scr;              // ptmi_eig_sytrd: the working matrix, d / e / tau, the eigenvectors, the exchange vectors and the barrier word
     void *dc_plan;               // ... the divide-and-conquer solver's tree and scratch (DcPlan, ptmi_abi.hip)
-    void *sy_lib;                // ... and the ROCm library's entry points (SyLib, ptmi_abi.hip; PTMI_SYTRD_LIB=1 only)
     int32_t *h_sy_info;          // pinned: the divide-and-conquer solver's convergence word of the last factorization that has finished
     void *d_qlg_scr;             // ptmi_eig_ql with parameter groups: a group's packed matrices, their eigenvectors and eigenvalues
     int32_t *gsize_host;         // [Ng] parameters per group (host copy of d_gsize)

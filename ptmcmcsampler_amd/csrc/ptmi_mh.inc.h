@@ -1542,11 +1542,11 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
             if constexpr (BOXFAST) box_margin = (box_margin - box_reach - box_guard) * (1.0 - 0x1.0p-40);
         }
         // PT:327-328 (the post-swap row of a swap iteration is written by the swap).  These 25 stores of four active lanes, in ONE
-        // wave of every block, are 15 % of the config-2 kernel (0.90 -> 0.77 ms without them, PTMI_MEASURE_NO_AM): the wave is its
-        // block's straggler.  Sending the row through LDS and out as two coalesced stores of the whole wave was built twice -- stored
+        // wave of every block, are 15 % of the config-2 kernel (0.90 -> 0.77 ms without them, in a measurement build): the wave is
+        // its block's straggler.  Sending the row through LDS and out as two coalesced stores of the whole wave was built twice -- stored
         // in the same step, and one step late so that no wait sits on the critical path -- and measured slower both times (1.00 ms).
         // Round 3 (persistent blocks, cold-first walk): 0.783 ms with the stores, 0.751 with every row of a walker sent to ONE
-        // cache-resident row (PTMI_MEASURE_AM_SMALL), 0.697 without them.  Units of 16 rank-0 chains of 16 different walkers -- the
+        // cache-resident row, 0.697 without them.  Units of 16 rank-0 chains of 16 different walkers -- the
         // same rows as 13 stores of a FULL wave in one unit of 64 instead of 13 four-lane stores in one unit of four -- measured
         // 0.780 against 0.778: the cost is the bytes through the CU's store path (1.28 MB per CU and launch) and the scattered
         // 64-byte writes behind it, not the issue slots of the instructions.
@@ -2227,24 +2227,21 @@ static int launch_mh_k(ptmi_engine *h, KArgs &a, int grid)
             a.box_off = (int)even(lds2 / sizeof(double));
             lds2 = sizeof(double) * (size_t)a.box_off + box_bytes;
         }
-        static const char *blk = getenv("PTMI_DENSE_BLK");              // measurement switch: 256, 512 (default) or 0 = the older kernel
-        const int want = blk ? atoi(blk) : 512;
-        const bool shared = c.ngroups <= 1 && (!c.cov_per_walker || c.ntemps % (want / G) == 0);
-        if (want && shared && lds2 <= 160 * 1024) {
+        const bool shared = c.ngroups <= 1 && (!c.cov_per_walker || c.ntemps % (512 / G) == 0);
+        if (shared && lds2 <= 160 * 1024) {
             const long long nch = (long long)c.nwalkers * c.ntemps;
-            auto launch = [&](auto kern, int BLKv) -> int {
+            auto launch = [&](auto kern) -> int {
                 if (lds2 > 64 * 1024) {
                     hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
                     if (e != hipSuccess) return fail(PTMI_EHIP, "hipFuncSetAttribute(%zu B of LDS): %s", lds2, hipGetErrorString(e));
                 }
-                const int cpb = BLKv / G;
-                hipLaunchKernelGGL(kern, dim3((unsigned)((nch + cpb - 1) / cpb)), dim3(BLKv), lds2, h->stream, a);
+                const int cpb = 512 / G;
+                hipLaunchKernelGGL(kern, dim3((unsigned)((nch + cpb - 1) / cpb)), dim3(512), lds2, h->stream, a);
                 h->last_variant = PTMI_VAR_STAGED | PTMI_VAR_LDS_UT | PTMI_VAR_DENSE_SCAM | (a.box_off >= 0 ? PTMI_VAR_LDS_BOX : 0);
                 return PTMI_OK;
             };
-            if (c.logp_kind == PTMI_LOGP_BOX)
-                return want == 256 ? launch(mh_dense_scam_kernel<EPL, 256, true>, 256) : launch(mh_dense_scam_kernel<EPL, 512, true>, 512);
-            return want == 256 ? launch(mh_dense_scam_kernel<EPL, 256, false>, 256) : launch(mh_dense_scam_kernel<EPL, 512, false>, 512);
+            if (c.logp_kind == PTMI_LOGP_BOX) return launch(mh_dense_scam_kernel<EPL, 512, true>);
+            return launch(mh_dense_scam_kernel<EPL, 512, false>);
         }
     }
     if constexpr (WANTS) {
@@ -2255,7 +2252,7 @@ static int launch_mh_k(ptmi_engine *h, KArgs &a, int grid)
         // (dense likelihood with AM in the cycle: the producer / consumer kernel below keeps the likelihood's table in LDS and reads the
         // eigenvectors from global memory at every ndim -- with both tables in LDS the smaller shapes fell back to the one-wave kernel:
         // 11.8 / 18.8 ms per 100 steps at 50 / 80-d against 14.2 at 100-d, now 7.5 / 11.6; up to 32-d the one-wave kernel stays ahead)
-        const bool dense_pc = FULL && LOGL == PTMI_LOGL_DENSE && EPL >= 14 && c.w_am > 0 && one_table_per_block && getenv("PTMI_NO_PC") == nullptr;
+        const bool dense_pc = FULL && LOGL == PTMI_LOGL_DENSE && EPL >= 14 && c.w_am > 0 && one_table_per_block && !ptmi_env("PTMI_NO_PC", 0);
         if (FULL && !dense_pc && lds + tab + sizeof(double) * c.ndim <= 160 * 1024) { a.lds_u = 1; lds += tab; }      // else Ut is read from global (L2)
         if (FULL) lds += sizeof(double) * c.ndim;                               // sqrt(eigenvalues)
         // AM queue of the block's four waves: 16 increments of 4 EPL + 2 doubles and 128 event entries each
@@ -2279,9 +2276,9 @@ static int launch_mh_k(ptmi_engine *h, KArgs &a, int grid)
                 lds = sizeof(double) * (size_t)a.tab_off + DRAWT;
             }
             // AM in the cycle: the producer / consumer form (mh_pc_kernel) when its lists fit beside the ring;
-            // PTMI_NO_PC=1 keeps the one-wave kernel (a measurement / test switch, same results)
+            // PTMI_NO_PC=1 keeps the one-wave kernel (a test hook, same results)
             if constexpr (FULL) {
-                const bool no_pc = getenv("PTMI_NO_PC") != nullptr;                      // read per launch: the tests switch it
+                const bool no_pc = ptmi_env("PTMI_NO_PC", 0) != 0;
                 // cd of the listed events, the pairs' two counters; dense: the likelihood's mean behind them
                 const size_t lists = sizeof(double) * 4 * 128 + sizeof(int) * 8 + (LOGL == PTMI_LOGL_DENSE ? sizeof(double) * 4 * EPL : 0);
                 // iso / curved: the eigenvector table in LDS; dense: the likelihood's table there, the eigenvectors read from global memory
@@ -2293,11 +2290,10 @@ static int launch_mh_k(ptmi_engine *h, KArgs &a, int grid)
                     if (a.box_off >= 0) a.box_off += shift;
                     a.tab_off += shift;
                     const size_t ldp = lds + lists;
-                    // ONE table for the launch (pooled covariance): persistent blocks, one per CU (PTMI_PC_PERS=0: a block per 64 chains)
+                    // ONE table for the launch (pooled covariance): persistent blocks, one per CU (per-walker tables: a block per 64 chains)
                     static int ncu = 0;
                     if (!ncu && (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.device) != hipSuccess || ncu < 1)) ncu = 256;
-                    const char *pe = getenv("PTMI_PC_PERS");
-                    const bool pers = !c.cov_per_walker && !(pe && atoi(pe) == 0);
+                    const bool pers = !c.cov_per_walker;
                     const int gridp = pers ? (grid < ncu ? grid : ncu) : grid;
                     auto launch_pc = [&](auto kp) -> int {
                         if (ldp > 64 * 1024) {
@@ -2332,14 +2328,11 @@ static int launch_mh_k(ptmi_engine *h, KArgs &a, int grid)
     if constexpr (!FULL && LOGL != PTMI_LOGL_DENSE) {
         size_t tab = sizeof(double) * ((size_t)c.ndim * c.ndim + c.ndim);
         const bool one_table = c.ngroups <= 1 && (!c.cov_per_walker || c.ntemps % (256 / G) == 0);
-        static const bool off = getenv("PTMI_NO_ULDS") != nullptr;      // measurement switch: same results either way
         // ONE table for the whole launch (pooled covariance): persistent blocks, one per CU over one LDS copy of the table
-        // (PTMI_ULDS_PERS = 0: the kernel with a table copy per block, a measurement / test switch; 768 threads -- three waves per
+        // (PTMI_ULDS_PERS = 0: the kernel with a table copy per block, a test hook; 768 threads -- three waves per
         // SIMD inside 168 registers -- measured 0.849 against 0.824 ms per 100 steps: the kernel is issue-bound)
         if constexpr (G == 4) {
-            const char *pe = getenv("PTMI_ULDS_PERS");       // read per launch: the tests switch it
-            const int pers = pe ? atoi(pe) : 512;
-            if (c.ngroups <= 1 && !c.cov_per_walker && pers && !off && (c.logp_kind == PTMI_LOGP_FLAT || c.logp_kind == PTMI_LOGP_BOX)) {
+            if (c.ngroups <= 1 && !c.cov_per_walker && ptmi_env("PTMI_ULDS_PERS", 1) && (c.logp_kind == PTMI_LOGP_FLAT || c.logp_kind == PTMI_LOGP_BOX)) {
                 static int ncu = 0;
                 if (!ncu) {
                     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.device) != hipSuccess || ncu < 1) ncu = 256;
@@ -2382,9 +2375,8 @@ static int launch_mh_k(ptmi_engine *h, KArgs &a, int grid)
                 tab = ut + box_bytes;
             }
         }
-        if (one_table && 2 * tab <= 160 * 1024 && !off) {
-            static const bool no_ldst = getenv("PTMI_NO_ULDS_DRAWT") != nullptr;     // measurement switch: same results either way
-            if (!no_ldst && 2 * (sizeof(double) * even(tab / sizeof(double)) + DRAWT) <= 160 * 1024) {
+        if (one_table && 2 * tab <= 160 * 1024) {
+            if (2 * (sizeof(double) * even(tab / sizeof(double)) + DRAWT) <= 160 * 1024) {
                 a.tab_off = (int)even(tab / sizeof(double));
                 tab = sizeof(double) * (size_t)a.tab_off + DRAWT;
             }

@@ -43,34 +43,32 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
             size_t off = 0;
             bool pair = false, w16 = false;
             const size_t box = h->cfg.logp_kind == PTMI_LOGP_BOX ? (size_t)box_table_doubles(G, E) : 0;
-            static const char *lv = getenv("PTMI_GJ_LDS_LEVELS");       // measurement / test switch: same results for any value
+            const int lv = (int)ptmi_env("PTMI_GJ_LDS_LEVELS", 1 << 30);    // a test hook: same results for any value
             if constexpr (G == 4) {
                 off = a.gj_diag ? (size_t)(3 * 4 * E) : (size_t)gjw_table_doubles(E);    // diagonal whitening: the three diagonals only
                 a.gj_stack_off = (int)off;
-                static const char *lvd = getenv("PTMI_GJ_LDS_DEFAULT");                  // measurement switch: heights kept in LDS by default
-                const int lmax = lvd ? atoi(lvd) : 11;
-                int levels = h->cfg.nuts_maxdepth + 1 < lmax ? h->cfg.nuts_maxdepth + 1 : lmax;    // heights 0..10 in LDS, the rest in global scratch
-                if (lv) levels = atoi(lv) < levels ? atoi(lv) : levels;
+                int levels = h->cfg.nuts_maxdepth + 1 < 11 ? h->cfg.nuts_maxdepth + 1 : 11;    // heights 0..10 in LDS, the rest in global scratch
+                if (lv < levels) levels = lv;
                 a.gj_lds_levels = levels;
                 // two jumps at a time, a half-wave each (GradJumpPair): diagonal whitening, no dense products; PTMI_GJ_NOPAIR: the
-                // one-chain-per-wave layout (a measurement / test switch, same results)
-                pair = a.gj_diag && L != PTMI_LOGL_DENSE && getenv("PTMI_GJ_NOPAIR") == nullptr;
+                // one-chain-per-wave layout (a test hook, same results)
+                pair = a.gj_diag && L != PTMI_LOGL_DENSE && !ptmi_env("PTMI_GJ_NOPAIR", 0);
                 off += (size_t)(pair ? 2 : 1) * a.gj_lds_levels * gjw_level_doubles(E) + (pair ? 72 + 2 * GJ_BLOCK : 64);       // pair: + the 16 chains' step-size states
-            } else if (G == 16 && a.d <= 64 && getenv("PTMI_GJ_NOWIDE16") == nullptr) {
+            } else if (G == 16 && a.d <= 64 && !ptmi_env("PTMI_GJ_NOWIDE16", 0)) {
                 // the 16-lane shape at ndim <= 64: a gradient jump takes the whole wave (GradJumpWide<16, L, 16>, one element per lane);
-                // PTMI_GJ_NOWIDE16: the per-chain layout (a measurement / test switch, same results)
+                // PTMI_GJ_NOWIDE16: the per-chain layout (a test hook, same results)
                 w16 = true;
                 off = a.gj_diag ? (size_t)(3 * 64) : 0;                     // the three diagonals (full tables stay in global memory)
                 a.gj_stack_off = (int)off;
                 int levels = h->cfg.nuts_maxdepth + 1 < 11 ? h->cfg.nuts_maxdepth + 1 : 11;
-                if (lv) levels = atoi(lv) < levels ? atoi(lv) : levels;
+                if (lv < levels) levels = lv;
                 a.gj_lds_levels = levels;
                 off += (size_t)levels * gjw_level_doubles(16) + 64;
             } else {
                 const size_t budget = 40 * 1024 / sizeof(double);           // one wave per SIMD (register count): a quarter of the CU's LDS each
                 int levels = box < budget ? (int)((budget - box) / gj_level_doubles(E)) : 0;
                 if (levels > h->cfg.nuts_maxdepth + 1) levels = h->cfg.nuts_maxdepth + 1;
-                if (lv) levels = atoi(lv) < levels ? atoi(lv) : levels;
+                if (lv < levels) levels = lv;
                 a.gj_stack_off = 0;
                 a.gj_lds_levels = levels;
                 off = (size_t)levels * gj_level_doubles(E);

@@ -381,12 +381,11 @@ int launch_rows(ptmi_engine *h, const KArgs &a, int mode)
 
 }  // namespace
 
-// Does this handle's split path run on the row kernels?  (No AM entries in the cycle; PTMI_SPLIT_ROWS=0: the shape kernels, an A/B
-// and test switch -- same results.)
+// Does this handle's split path run on the row kernels?  (No AM entries in the cycle; PTMI_SPLIT_ROWS=0: the shape kernels, a test
+// hook -- same results.)
 bool ptmi_split_rows_ok(const ptmi_engine *h)
 {
-    const char *e = getenv("PTMI_SPLIT_ROWS");                   // read per call: the tests switch it
-    if (e && atoi(e) == 0) return false;
+    if (!ptmi_env("PTMI_SPLIT_ROWS", 1)) return false;
     return (h->cfg.w_am == 0 || h->split_am_piece > 0) && h->cfg.ndim >= 1;
 }
 

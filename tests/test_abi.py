@@ -141,3 +141,32 @@ def test_product_ladder_matches_the_reference_fixture(lib, golden):
     assert one.dtype.kind == "i" and "chain_{0}.txt".format(one[0]) == "chain_1.txt"      # PTMCMCSampler.py:285, :718
     assert "chain_{0}.txt".format(temperature_ladder(2, 2)[0]) == "chain_1.0.txt"
     assert np.allclose(temperature_ladder(4, 10, 1, None, 2.0), [1, 2, 4, 8])
+
+
+def test_only_the_c_abi_is_exported(lib):
+    """The linker version script (csrc/ptmi.map) keeps the C ABI global and everything else -- C++ helpers, kernel handles,
+    device stubs -- local to the library."""
+    import shutil
+    import subprocess
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.check_output([nm, "-D", "--defined-only", lib.SO], text=True)
+    assert {ln.split()[-1] for ln in out.splitlines() if ln.strip()} == set(lib.SYMBOLS)
+
+
+HOOKS = {"PTMI_NO_PC", "PTMI_SWAP_FUSED", "PTMI_ULDS_PERS", "PTMI_SPLIT_ROWS", "PTMI_QL_SPLIT", "PTMI_GJ_SOLO", "PTMI_GJ_LDS_LEVELS",
+         "PTMI_GJ_NOPAIR", "PTMI_GJ_NOWIDE16", "PTMI_AM_BUDGET_MB", "PTMI_SPLIT_AM_BUDGET_MB"}
+
+
+def test_the_library_reads_only_the_documented_test_hooks():
+    """Every environment variable the native code reads goes through ptmi_env (csrc/ptmi_common.h) and is one of the test hooks
+    listed above it: no A/B switch comes back unnoticed."""
+    import glob
+    csrc = os.path.join(ROOT, "ptmcmcsampler_amd", "csrc")
+    read = set()
+    for path in glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")):
+        txt = open(path).read()
+        read |= set(re.findall(r"\bptmi_env\(\s*\"(\w+)\"", txt))
+        assert re.findall(r"\bgetenv\(([^)]*)\)", txt) == (["name"] if path.endswith("ptmi_common.h") else []), path
+    common = open(os.path.join(csrc, "ptmi_common.h")).read()
+    documented = set(re.findall(r"^//\s+(PTMI_\w+)\s", common[:common.index("inline double ptmi_env(")], flags=re.M))
+    assert read == documented == HOOKS

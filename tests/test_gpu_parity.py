@@ -346,8 +346,8 @@ def test_wide_shapes_scam_only_on_the_padded_table(mods, d, nt, W, cu, tskip, pr
     """16 and 64 lanes per chain (ndim > 104), SCAM-only cycle, ONE table for the launch (pooled covariance): the wide draw batches
     (all lanes of a chain draw: 8 / 32 iterations per pass; PTMCMCSampler.py:820-876) and the direction read from the library's
     zero-padded copy of the table (include/ptmi.h PTMI_VAR_UTPAD).  Launch lengths that are no multiple of a pass, launches longer
-    than one (tskip = 0: a launch per covariance period), covariance epochs between the launches (the copy follows the table); the
-    same run with the copy switched off (PTMI_NO_UTPAD is read once per process, so that variant is checked through per-walker tables)."""
+    than one (tskip = 0: a launch per covariance period), covariance epochs between the launches (the copy follows the table).  The
+    kernel without the copy is checked through per-walker tables (test_wide_draw_batches_in_the_other_wide_kernels)."""
     orc, _lib, PTEngine = mods
     kw = dict(weights=(20, 0, 0), cov_update=cu, burn=1000, tskip=tskip, seed=d * 10 + nt, rs=d + 2, cov_mode="pooled")
     if prior == "box":
@@ -507,7 +507,7 @@ def test_parameter_groups_with_am_increments_ahead_of_the_launch(mods, d, groups
     own table, so the step kernels' matrix-core product (one table for the 16 chains of a wave) does not apply; the increments
     U_g (cd sqrt(S_g) z) of a piece of the launch are computed ahead of it by am_gemm_kernel, one launch per group over the listed
     picks (round 5; every shape, 4 / 16 / 64 lanes per chain) -- the same k-ascending fma chain over the group's rows as the step
-    kernel's own vector-pipe product, which the same cases run with PTMI_NO_AM_AHEAD through the oracle.  `pieces`: a scratch of
+    kernel's own vector-pipe product, held to the oracle bit for bit.  `pieces`: a scratch of
     1 MB cuts the launches into single steps.  cov_mode "per_walker" (what real PTA runs combine: groups and a covariance per
     replica): an event's table is its walker's group table, the lists are per (walker, group), a grid row of the product per walker."""
     if pieces:

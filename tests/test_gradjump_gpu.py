@@ -79,8 +79,12 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "d%d-%s%s%s%s" % (c["d"], c["logl"][0], "-cap%d" % c["nuts_maxdepth"] if "nuts_maxdepth" in c else "",
-                                                                       "-diag" if c.get("diag") else "", ("" if sum(c["grad_weights"]) else "-nogj") + ("-nowide16" if c.get("nowide16") else "") + ("-solo%d" % c["solo"] if "solo" in c else "") + ("-" + c["cov_mode"] if "cov_mode" in c else "") + ("-pieces" if "am_budget" in c else "")))
+def _case_id(c):
+    return "d%d-%s%s%s%s" % (c["d"], c["logl"][0], "-cap%d" % c["nuts_maxdepth"] if "nuts_maxdepth" in c else "",
+                             "-diag" if c.get("diag") else "", ("" if sum(c["grad_weights"]) else "-nogj") + ("-nowide16" if c.get("nowide16") else "") + ("-solo%d" % c["solo"] if "solo" in c else "") + ("-" + c["cov_mode"] if "cov_mode" in c else "") + ("-pieces" if "am_budget" in c else ""))
+
+
+@pytest.mark.parametrize("case", CASES, ids=_case_id)
 def test_device_gradient_jumps_bit_exact(case, monkeypatch):
     c = dict(case)
     d, nt, W = c.pop("d"), c.pop("nt"), c.pop("W")
@@ -201,15 +205,13 @@ def test_facade_runs_device_gradient_jumps(tmp_path):
     assert chain.shape[1] == d + 4 and len(chain) in (400, 401) and np.isfinite(chain).all()
 
 
-def test_tree_levels_beyond_the_lds_budget_live_in_global_scratch():
+def test_tree_levels_beyond_the_lds_budget_live_in_global_scratch(monkeypatch):
     """The tree stack keeps the low heights in LDS and the rest -- heights 11 .. 24 by default, never reached by a sane run --
-    in global scratch.  With PTMI_GJ_LDS_LEVELS=1 (read once per process, hence the child) every height above 0 takes the
-    global path: the same parity cases must still hold bit for bit, in the whole-wave layout and in the per-chain one."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gradjump_gpu.py"), "-m", "gpu", "-q", "-x", "-k",
-                        "test_device_gradient_jumps_bit_exact and (d20-curved or d5-iso or d40-dense or d2-curved)"],
-                       capture_output=True, text=True, timeout=900, env=dict(os.environ, PTMI_GJ_LDS_LEVELS="1"), cwd=root)
-    assert r.returncode == 0 and " passed" in r.stdout and "failed" not in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    in global scratch.  With PTMI_GJ_LDS_LEVELS=1 every height above 0 takes the global path: the same parity cases must still
+    hold bit for bit, in the whole-wave layout and in the per-chain one."""
+    cases = [c for c in CASES if any(k in _case_id(c) for k in ("d20-curved", "d5-iso", "d40-dense", "d2-curved"))]
+    assert len(cases) >= 4
+    for case in cases:
+        with monkeypatch.context() as mp:
+            mp.setenv("PTMI_GJ_LDS_LEVELS", "1")
+            test_device_gradient_jumps_bit_exact(case, mp)

@@ -33,7 +33,6 @@ b c5_share --no-cpu-baseline --logl curved --ndim 20 --ntemps 16 --mix nuts --st
 b oddeven --no-cpu-baseline --swap-mode oddeven --steps 100 --warmup 20 --ess-window 0
 b scam_stats_async --no-cpu-baseline --stats-async on --eig-lag 2 --ess-window 0     # statistics on a side stream (two AM rings): measured, not the default
 b c4_share_stats_async --no-cpu-baseline --ndim 1000 --nwalkers 512 --steps 40 --warmup 20 --stats-async on --ess-window 0
-PTMI_SYTRD_LIB=1 b c4_share_library_dc --no-cpu-baseline --ndim 1000 --nwalkers 512 --steps 40 --warmup 20 --ess-window 0     # PTMI_SYTRD_LIB set below: rocsolver's dstedc / dormtr (round 4)
 python - <<PY
 import json, glob, os
 out = {}

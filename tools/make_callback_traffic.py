@@ -39,7 +39,8 @@ for kind, tag in (("hip", "callback"), ("norm", "callbacktorch")):
         "traffic_bytes_per_iteration": per_iter,
         "correction": "gfx950: FETCH_SIZE reports half of a wide coalesced read stream (MI355X_MICROARCH.md, HBM section): x2; WRITE_SIZE uncorrected",
         "source": ["profiles/r06_%s_fetch.txt" % tag, "profiles/r06_%s_write.txt" % tag],
-        "command": "bash tools/r6_callback.sh (rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE in separate passes over bench.py --callback)",
+        "command": ("rocprofv3 --kernel-trace --pmc FETCH_SIZE, then --pmc WRITE_SIZE, in separate passes over python bench.py --callback "
+                    "--steps 20 --warmup 5 --no-cpu-baseline --ess-window 0 --also off; tools/rocpd_summary.py over the timed region"),
     }
 json.dump(res, open(os.path.join(ROOT, "profiles", "r06_callback_traffic.json"), "w"), indent=1)
 print(json.dumps(res, indent=1))
