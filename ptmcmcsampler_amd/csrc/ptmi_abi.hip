@@ -2678,6 +2678,7 @@ int ptmi_destroy(ptmi_handle h)
     (void)hipFree(h->d_rle_ent); (void)hipFree(h->d_rle_cnt);
     (void)hipFree(h->d_am_ev); (void)hipFree(h->d_am_count); (void)hipFree(h->d_am_base); (void)hipFree(h->d_am_inc);
     (void)hipFree(h->d_am_grp); (void)hipFree(h->d_am_perm); (void)hipFree(h->d_am_kbase); (void)hipFree(h->d_am_next); (void)hipFree(h->d_iter);
+    if (h->h_gj_n) (void)hipHostFree(h->h_gj_n);
     (void)hipFree(h->d_gj_tab); (void)hipFree(h->d_gj_scr); (void)hipFree(h->d_gj_scal); (void)hipFree(h->d_gj_order); (void)hipFree(h->d_gj_bucket);
     if (h->side) { (void)hipStreamDestroy(h->side); (void)hipEventDestroy(h->side_go); (void)hipEventDestroy(h->side_done); }
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -2856,6 +2857,21 @@ int ptmi_last_mh_variant(ptmi_handle h, int32_t *variant)
     return PTMI_OK;
 }
 
+// HMC on the split path (ptmi_gjcb.hip): proposals of `iter` were just made -- with HMC in the cycle their gradient stage is pending
+static void gj_proposed(ptmi_engine *h, long long iter)
+{
+    h->gj_phase = h->cfg.w_hmc > 0 ? PTMI_GJ_PENDING : PTMI_GJ_NONE;
+    h->gj_iter = iter;
+}
+// ... and an accept test may only read them once that stage is over
+static int gj_stage_over(const ptmi_engine *h, const char *who, int64_t iter)
+{
+    if (h->gj_phase == PTMI_GJ_PENDING || h->gj_phase == PTMI_GJ_ROUNDS)
+        return fail(PTMI_EINVAL, "%s(%lld): the HMC proposals of iteration %lld are not made yet -- ptmi_gj_begin and ptmi_gj_step until n = 0 first",
+                    who, (long long)iter, h->gj_iter);
+    return PTMI_OK;
+}
+
 // ptmi_device_iter: the split calls' `iter` is an offset from the counter in device memory (launches captured in a graph).  The row
 // kernels derive the ring row and the swap-iteration test from the counter themselves; what the host cannot know then it cannot check.
 static int split_iter_args(ptmi_engine *h, KArgs *a, int mode)
@@ -2885,6 +2901,7 @@ int ptmi_propose(ptmi_handle h, int64_t iter)
 {
     if (!h) return fail(PTMI_EINVAL, "NULL handle");
     if (!h->buf.Q || !h->buf.qaux) return fail(PTMI_EINVAL, "split path needs the Q and qaux buffers");
+    if (int rc = ptmi_gj_split_check(h)) return rc;
     KArgs a = make_args(h);
     a.iter0 = iter; a.nsteps = 1;
     if (int rc = split_iter_args(h, &a, 0)) return rc;
@@ -2898,6 +2915,7 @@ int ptmi_propose(ptmi_handle h, int64_t iter)
         if (int rc = run_shape(h, PTMI_OP_PROPOSE, a, grid, true)) return rc;
     }
     HIPCHK(hipGetLastError());
+    gj_proposed(h, iter);
     return PTMI_OK;
 }
 
@@ -2905,6 +2923,7 @@ int ptmi_accept(ptmi_handle h, int64_t iter, const double *newlnL, const double 
 {
     if (!h) return fail(PTMI_EINVAL, "NULL handle");
     if (!h->buf.Q || !h->buf.qaux || !newlnL || !newlp) return fail(PTMI_EINVAL, "split path buffers missing");
+    if (int rc = gj_stage_over(h, "ptmi_accept", iter)) return rc;
     KArgs a = make_args(h);
     a.iter0 = iter; a.nsteps = 1; a.newlnL = newlnL; a.newlp = newlp;
     if (int rc = split_iter_args(h, &a, 1)) return rc;
@@ -2917,6 +2936,7 @@ int ptmi_accept(ptmi_handle h, int64_t iter, const double *newlnL, const double 
         if (int rc = run_shape(h, PTMI_OP_ACCEPT, a, grid, true)) return rc;
     }
     HIPCHK(hipGetLastError());
+    h->gj_phase = PTMI_GJ_NONE;
     return PTMI_OK;
 }
 
@@ -2929,6 +2949,8 @@ int ptmi_accept_propose(ptmi_handle h, int64_t iter, const double *newlnL, const
     // change the tables the proposal of iter + 1 reads)
     if (!h->dev_iter && c.tskip > 0 && c.ntemps_global > 1 && iter % c.tskip == 0)
         return fail(PTMI_EINVAL, "ptmi_accept_propose(%lld): a swap iteration (Tskip=%d) is accepted with ptmi_accept, the swap follows", (long long)iter, c.tskip);
+    if (int rc = ptmi_gj_split_check(h)) return rc;
+    if (int rc = gj_stage_over(h, "ptmi_accept_propose", iter)) return rc;
     KArgs a = make_args(h);
     a.iter0 = iter; a.nsteps = 1; a.newlnL = newlnL; a.newlp = newlp;
     if (int rc = split_iter_args(h, &a, 2)) return rc;
@@ -2939,6 +2961,7 @@ int ptmi_accept_propose(ptmi_handle h, int64_t iter, const double *newlnL, const
         if (int rc = ptmi_split_rows(h, a, 2)) return rc;
         h->q_cur = a.q_tgt;
         HIPCHK(hipGetLastError());
+        gj_proposed(h, iter + 1);
         return PTMI_OK;
     }
     // configurations the row kernels do not serve (AM entries in the cycle): the two shape kernels back to back

@@ -199,7 +199,16 @@ struct ptmi_engine {
     long long *d_iter;           // split path: the iteration counter in device memory (ptmi_set_device_iter) ...
     int dev_iter;                // ... and whether the split calls' `iter` arguments are offsets from it (ptmi_device_iter)
     int q_cur;                   // split path: the proposal buffer (0 = Q, 1 = Q2) that holds the current proposals (ptmi_proposals)
+    // split path with HMC in the cycle (ptmi_gjcb.hip): where the gradient stage of the current proposals is (PTMI_GJ_*), their
+    // iteration, the chains listed in the open round, the caller's work area, and the pinned word the round's count is read into
+    int gj_phase;
+    long long gj_iter, gj_n;
+    void *gj_work;
+    long long *h_gj_n;
 };
+enum { PTMI_GJ_NONE = 0, PTMI_GJ_PENDING = 1 /* proposals made, ptmi_gj_begin not yet called */, PTMI_GJ_ROUNDS = 2, PTMI_GJ_DONE = 3 };
+// the split path's refusals for gradient jumps (0: served; else the code, with the message set)
+int ptmi_gj_split_check(const ptmi_engine *h);
 
 
 // split path on contiguous rows (ptmi_split.hip): does the handle's configuration run there; mode 0 propose(iter0), 1 accept(iter0),

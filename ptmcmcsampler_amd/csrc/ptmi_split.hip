@@ -180,12 +180,15 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const KArgs a)
                 z = rp_val;
                 pickw = (u32)(P0 >> 32);
             }
-            // cycle pick (PT:1058) and scale branch (PT:846-858), as propose()
+            // cycle pick (PT:1058) and scale branch (PT:846-858), as propose() -- with the gradient jumps behind the others as
+            // propose<..., GJ=true> draws them (PT:225-258): such a pick hands the state back unchanged, the gradient stage
+            // (ptmi_gjcb.hip) then replaces its proposal.  Zero gradient weights leave L and every pick as they were.
             const int w_de = a.de_on ? a.w_de : 0;
-            const int L = a.w_host + a.w_scam + a.w_am + w_de;
+            const int L = a.w_host + a.w_scam + a.w_am + w_de + a.w_nuts + a.w_hmc;
             const int pick = (int)h2index(pickw, (u32)L);
             const int ind = pick - a.w_host;
             int jt = ind < a.w_scam ? PTMI_J_SCAM : (ind < a.w_scam + a.w_am ? PTMI_J_AM : PTMI_J_DE);
+            if (ind >= a.w_scam + a.w_am + w_de) jt = ind < a.w_scam + a.w_am + w_de + a.w_nuts ? PTMI_J_NUTS : PTMI_J_HMC;
             if (ind < 0) jt = PTMI_J_NTYPES + pick;              // a host-served cycle entry: the state is handed back unchanged
             const u32 plo = (u32)P0;
             constexpr u32 T97 = (u32)(0.97 * 4294967296.0), T90 = (u32)(0.9 * 4294967296.0), T50 = 0x80000000u;

@@ -208,6 +208,8 @@ class PTEngine(object):
         # gradient jumps on the built-in likelihoods (PTMCMCSampler.py:225-258): (NUTSweight, HMCweight); the whitening
         # comes from the INITIAL covariance and is never adapted (nutsjump.py:45, 53-54)
         self.grad_weights = tuple(int(w) for w in grad_weights)
+        if split and self.grad_weights[0] > 0:
+            raise ValueError("the callback path (split=True) runs HMC with batched gradient callbacks, not NUTS: grad_weights=(0, w_hmc)")
         has_gj = sum(self.grad_weights) > 0
         self.gj_tab = np.zeros(0)
         if has_gj:
@@ -888,12 +890,60 @@ class PTEngine(object):
         self._store_initial(i0)
         self.iter = int(i0)
 
-    def split_step(self, it, logl, logp):
-        """One iteration of every chain with batched callbacks: ptmi_propose -> callbacks on the device tensor of
-        proposals -> ptmi_accept.  All on the engine's stream; no host copy of the proposals."""
+    def _cb_grad(self, r, n, what):
+        """A batched gradient callback's return value ``(value [n], gradient [n, d])`` as contiguous f64 tensors on this GPU (no copy
+        when they already are)."""
+        torch = _torch()
+        if not isinstance(r, (tuple, list)) or len(r) != 2:
+            raise ValueError("%s must return (value[n], gradient[n, ndim])" % what)
+        v, g = r
+        if not (torch.is_tensor(v) and v.dtype == torch.float64 and v.device == self.device and v.is_contiguous()):
+            v = torch.as_tensor(v, dtype=torch.float64, device=self.device).contiguous()
+        if not (torch.is_tensor(g) and g.dtype == torch.float64 and g.device == self.device and g.is_contiguous()):
+            g = torch.as_tensor(g, dtype=torch.float64, device=self.device).contiguous()
+        if v.numel() != n or tuple(g.shape) != (n, self.d):
+            raise ValueError("%s returned value %s and gradient %s for %d rows of %d parameters: expected [%d] and [%d, %d]"
+                             % (what, tuple(v.shape), tuple(g.shape), n, self.d, n, n, self.d))
+        return v, g
+
+    def gradient_stage(self, it, logl_grad, logp_grad=None):
+        """The HMC picks of the proposals of iteration ``it`` (just made by ptmi_propose / ptmi_accept_propose): rounds of
+        ``logl_grad(X[n, d]) -> (lnL[n], dlnL[n, d])`` (and ``logp_grad``, the same shape; None: a flat prior, no launch) on the rows the
+        library lists (``ptmi_gj_begin`` / ``ptmi_gj_step``, include/ptmi.h), until every chain's trajectory has ended.  Returns the
+        number of rounds.  A no-op without HMC in the cycle."""
+        if self.grad_weights[1] <= 0:
+            return 0
+        if logl_grad is None:
+            raise ValueError("HMC is in the cycle (grad_weights=%r): the callback path needs logl_grad" % (self.grad_weights,))
+        torch = _torch()
+        if getattr(self, "_gj_work", None) is None:
+            nb = C.c_size_t(0)
+            _lib.check(self.lib.ptmi_gj_work_bytes(self.h, C.byref(nb)))
+            self._gj_work = torch.empty(nb.value, dtype=torch.uint8, device=self.device)
+            self._gj_rows = torch.empty((self.W * self.nt, self.d), dtype=torch.float64, device=self.device)
+        lib, h, work, rows = self.lib, self.h, self._gj_work.data_ptr(), self._gj_rows
+        n = C.c_int64(0)
+        _lib.check(lib.ptmi_gj_begin(h, it, work, rows.data_ptr(), C.byref(n)))
+        rounds = 0
+        while n.value > 0:
+            X = rows[:n.value]
+            ll, gl = self._cb_grad(logl_grad(X), n.value, "logl_grad")
+            lp = gp = None
+            if logp_grad is not None:
+                lp, gp = self._cb_grad(logp_grad(X), n.value, "logp_grad")
+            _lib.check(lib.ptmi_gj_step(h, work, ll.data_ptr(), gl.data_ptr(), lp.data_ptr() if lp is not None else None,
+                                        gp.data_ptr() if gp is not None else None, rows.data_ptr(), C.byref(n)))
+            rounds += 1
+        return rounds
+
+    def split_step(self, it, logl, logp, logl_grad=None, logp_grad=None):
+        """One iteration of every chain with batched callbacks: ptmi_propose -> (HMC in the cycle: the gradient stage,
+        ``gradient_stage``) -> callbacks on the device tensor of proposals -> ptmi_accept.  All on the engine's stream; no host copy of
+        the proposals."""
         if self.t["Q"] is None:
             raise _lib.PtmiError("the callback path needs the engine built with split=True")
         _lib.check(self.lib.ptmi_propose(self.h, it))
+        self.gradient_stage(it, logl_grad, logp_grad)
         ll, lp = self.eval_callback(self.t["Q"], logl, logp)
         _lib.check(self.lib.ptmi_accept(self.h, it, ll.data_ptr(), lp.data_ptr()))
 
@@ -933,11 +983,12 @@ class PTEngine(object):
         q2 = self.t["Q2"]
         return q2 if q2 is not None and p.value == q2.data_ptr() else self.t["Q"]
 
-    def callback_segment(self, it, end, logl, logp):
+    def callback_segment(self, it, end, logl, logp, logl_grad=None, logp_grad=None):
         """Iterations ``it .. end`` with nothing between them (no epoch, no swap: a segment of ``run``): ONE proposal launch, then per
         iteration the callbacks on the device tensor of proposals and ptmi_accept_propose -- the accept test of iteration j and the
         proposal of j + 1 in one launch, a chain's row in once and out once (csrc/ptmi_split.hip) -- and ptmi_accept behind the last.
-        The same chains as ``split_step`` iteration by iteration, bit for bit."""
+        With HMC in the cycle every proposal launch is followed by its gradient stage (``gradient_stage``: the batched gradient
+        callbacks ``logl_grad`` / ``logp_grad``).  The same chains as ``split_step`` iteration by iteration, bit for bit."""
         if self.t["Q"] is None:
             raise _lib.PtmiError("the callback path needs the engine built with split=True")
         lib, h = self.lib, self.h
@@ -950,11 +1001,13 @@ class PTEngine(object):
         if piece:
             _lib.check(lib.ptmi_split_am_prepare(h, it, min(piece, end - it + 1)))
         _lib.check(lib.ptmi_propose(h, it))
+        self.gradient_stage(it, logl_grad, logp_grad)
         for j in range(it, end):
             ll, lp = self.eval_callback(self.proposals(), logl, logp)
             if piece and (j + 1 - it) % piece == 0:                   # the proposal of j + 1 opens the next piece
                 _lib.check(lib.ptmi_split_am_prepare(h, j + 1, min(piece, end - j)))
             _lib.check(lib.ptmi_accept_propose(h, j, ll.data_ptr(), lp.data_ptr()))       # (between here and ptmi_accept X is not the state: sloc)
+            self.gradient_stage(j + 1, logl_grad, logp_grad)
         ll, lp = self.eval_callback(self.proposals(), logl, logp)
         _lib.check(lib.ptmi_accept(h, end, ll.data_ptr(), lp.data_ptr()))
 
@@ -966,9 +1019,10 @@ class PTEngine(object):
         must be graph-safe (no host synchronisation, the same launches for every batch: any fixed torch expression or device
         kernel is).  What the captured launches bake in -- the DE ring's head, whether DE is in the cycle -- is part of the cache
         key.  Returns False where it does not apply (AM entries in the cycle: their increments are listed on the host's iteration;
-        configurations the row kernels do not serve): the caller then runs ``callback_segment``.  Same results, bit for bit."""
+        configurations the row kernels do not serve; HMC in the cycle: its rounds are counted on the host): the caller then runs
+        ``callback_segment``.  Same results, bit for bit."""
         torch = _torch()
-        if self.t["Q2"] is None or self.weights[1] > 0:
+        if self.t["Q2"] is None or self.weights[1] > 0 or self.grad_weights[1] > 0:
             return False
         if getattr(self, "_graphs", None) is None:
             self._graphs = {}
@@ -1005,11 +1059,13 @@ class PTEngine(object):
         _lib.check(lib.ptmi_set_proposals(h, g[1]))
         return True
 
-    def run_callback(self, niter, logl, logp, fused=True, graph=False):
+    def run_callback(self, niter, logl, logp, fused=True, graph=False, logl_grad=None, logp_grad=None):
         """``run`` with the likelihood and the prior in batched callbacks: the same segments (epochs and swaps between them, the
         late table of ``eig_lag`` counted in segments as ``run`` counts it in launches).  ``fused=False``: propose / accept as two
         launches per iteration (``split_step``; same results).  ``graph=True``: every segment one hipGraph launch
-        (``callback_segment_graph``: for small, launch-bound batches with graph-safe callbacks; same results)."""
+        (``callback_segment_graph``: for small, launch-bound batches with graph-safe callbacks; same results).  HMC in the cycle
+        (``grad_weights=(0, w)``): ``logl_grad(X[n, d]) -> (lnL[n], dlnL[n, d])`` and ``logp_grad`` (None: a flat prior) serve its
+        trajectories (``gradient_stage``)."""
         last = self.iter + niter
         it = self.iter + 1
         while it <= last:
@@ -1018,10 +1074,10 @@ class PTEngine(object):
             if fused and graph and self.callback_segment_graph(it, end, logl, logp):
                 pass
             elif fused:
-                self.callback_segment(it, end, logl, logp)
+                self.callback_segment(it, end, logl, logp, logl_grad, logp_grad)
             else:
                 for j in range(it, end + 1):
-                    self.split_step(j, logl, logp)
+                    self.split_step(j, logl, logp, logl_grad, logp_grad)
             if self.tskip > 0 and self.ntg > 1 and end % self.tskip == 0:
                 self.swap(end)
             if self._eig_pending:

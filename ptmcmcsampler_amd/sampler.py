@@ -19,7 +19,9 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
 * ``batched=True``: ``logl`` / ``logp`` are called once per iteration with the device tensor of all proposals,
   ``f(X[n, ndim]) -> [n]`` (torch in, torch out; loglargs / loglkwargs still apply) -- the same boundary as the reference's
   ``_function_wrapper`` (PTMCMCSampler.py:1072-1086), one call per batch instead of one per chain, nothing copied to the
-  host; custom Python jumps cannot be mixed in;
+  host; custom Python jumps cannot be mixed in.  With ``logl_grad`` / ``logp_grad`` as batched callbacks too --
+  ``f(X[n, ndim]) -> (value[n], gradient[n, ndim])`` -- HMC (``HMCweight``) runs on the device with the callbacks' gradients
+  (``PTEngine.gradient_stage``); NUTS is not built for them (pass ``NUTSweight=0``);
 * engine options: ``cov_mode="pooled"`` (one covariance adapted from all walkers instead of one per walker),
   ``swap_mode="oddeven"`` (disjoint swap pairs instead of the reference's hot -> cold sweep), ``pick_mode="walker"`` (one
   proposal-type draw per walker and iteration), ``eig_mode="ql"`` / ``"jacobi"`` / ``"sytrd"`` / ``"hipsolver"`` (covariance epochs factorized on the device: per-walker matrices by
@@ -218,6 +220,12 @@ class PTSampler(object):
                    AMweight=20, DEweight=50, NUTSweight=20, HMCweight=20, MALAweight=0, burn=50000, HMCstepsize=0.1,
                    HMCsteps=300, maxIter=None, thin=10, i0=0, neff=None, writeHotChains=False, hotChain=False):
         from .engine import PTEngine
+        # batched gradient callbacks (batched=True with logl_grad / logp_grad): HMC runs on the device between the proposal launch and
+        # the likelihood callback, the gradients from the callbacks (PTEngine.gradient_stage); NUTS is not built for them
+        self._batched_grads = self.batched and self.logl_grad is not None and self.logp_grad is not None
+        if self._batched_grads and NUTSweight > 0:
+            raise NotImplementedError("batched gradient callbacks (batched=True with logl_grad / logp_grad) run HMC only: NUTS is not "
+                                      "built for them (NUTSweight=%r); pass NUTSweight=0" % (NUTSweight,))
         if maxIter is None:
             maxIter = Niter
         self.ladder, self.covUpdate, self.burn, self.Tskip = ladder, covUpdate, burn, Tskip
@@ -230,7 +238,7 @@ class PTSampler(object):
         self._chain, self._lnlike, self._lnprob = self._chains[0], self._lnlikes[0], self._lnprobs[0]
         self.ind_next_write = 0
         self.naccepted = self.swapProposed = self.nswap_accepted = 0
-        if self.logl_grad is not None and self.logp_grad is not None:                  # :226-258, same order
+        if self.logl_grad is not None and self.logp_grad is not None and not self._batched_grads:   # :226-258, same order
             from .gradjump import HMCJump, NUTSJump
             lg, pg, cov, nb = self.logl_grad, self.logp_grad, self.cov, self.burn
             if MALAweight > 0 and self.verbose:                                        # :229-235
@@ -244,7 +252,7 @@ class PTSampler(object):
                                                                            write_burnin=False, force_trajlen=None,
                                                                            force_epsilon=None, delta=0.6)), NUTSweight)
         self._grad_weights = (0, 0)
-        if self.device_grads:                                                          # :226-258 on the device (csrc/ptmi_gj.inc.h)
+        if self.device_grads or self._batched_grads:                                   # :226-258 on the device (csrc/ptmi_gj.inc.h, ptmi_gjcb.hip)
             if MALAweight > 0 and self.verbose:
                 print("WARNING: MALAJump is not built for the device likelihoods (the reference flags it as not working, "
                       "PTMCMCSampler.py:230-231): MALAweight ignored")
@@ -403,7 +411,7 @@ class PTSampler(object):
                 end = min(eng._segment_end(it, self.Niter), ((it - 1) // self.isave + 1) * self.isave)
                 if self._hot_names:
                     end = min(end, ((it - 1) // self.thin + 1) * self.thin)
-                eng.callback_segment(it, end, self.logl, self.logp)
+                eng.callback_segment(it, end, self.logl, self.logp, *self._grad_callbacks())
             elif self.split:
                 end = it
                 self._split_step(it)
@@ -727,6 +735,10 @@ class PTSampler(object):
                     ll[w, s] = self.logl(Q[w, s])
         return ll, lp
 
+    def _grad_callbacks(self):
+        """(logl_grad, logp_grad) for the engine's gradient stage: the batched callbacks when HMC runs on them, else (None, None)."""
+        return (self.logl_grad, self.logp_grad) if getattr(self, "_batched_grads", False) else (None, None)
+
     def _init_split(self, p0, i0=0):
         import torch
         eng = self.engine
@@ -746,7 +758,7 @@ class PTSampler(object):
         import torch
         eng = self.engine
         if self.batched:
-            eng.split_step(it, self.logl, self.logp)
+            eng.split_step(it, self.logl, self.logp, *self._grad_callbacks())
             return
         _lib.check(eng.lib.ptmi_propose(eng.h, it))
         Q, qa = eng.t["Q"].cpu().numpy(), eng.t["qaux"].cpu().numpy()

@@ -1,0 +1,142 @@
+#!/usr/bin/env python
+"""HMC through batched gradient callbacks (PTEngine.gradient_stage, csrc/ptmi_gjcb.hip) at full size: updates/s, leapfrogs/s, callback
+rounds per iteration, and -- with --profile -- the library's kernels' share of the wall time against the callback's.
+
+    python tools/gj_callback_timing.py [--ntemps 64 --nwalkers 1024 --ndim 40 --iters 50 --warmup 10] [--profile]
+
+Two callbacks, each with two cycles (SCAM + HMC, HMC only):
+  * interval: the reference's own gradient workload (tests/test_nuts.py: a unit Gaussian behind intervalTransform on (0, 10)) as a
+    torch expression, its gradient by autograd;
+  * iso: the built-in isotropic Gaussian (ptmi_rows_logl, one pass over the rows) with -X as its gradient -- the stage's own cost
+    with the cheapest callback there is.
+--profile runs each case again in a fresh child under ``rocprofv3 --kernel-trace --stats`` and sums the kernels of the timed region
+(from the marker launch on) by owner: the library's (split_rows / gj_* / rows_iso / am_*) and everything else (the callback's)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sqlite3
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+LIB_KERNELS = ("split_rows_kernel", "gj_begin_kernel", "gj_step_kernel", "gj_count_kernel", "gj_fill_kernel", "rows_iso_kernel", "am_",
+               "set_iter_kernel")
+
+
+def interval_callbacks(d, a=0.0, b=10.0):
+    import torch
+    c = 0.5 * np.log(2 * np.pi)
+    lw = float(np.log(b - a))
+
+    def logl(X):
+        x = a + (b - a) * torch.sigmoid(X)
+        return (-0.5 * x * x - c).sum(-1) + (lw + torch.nn.functional.logsigmoid(X) + torch.nn.functional.logsigmoid(-X)).sum(-1)
+
+    def logl_grad(X):
+        Xg = X.detach().requires_grad_(True)
+        with torch.enable_grad():
+            ll = logl(Xg)
+            g, = torch.autograd.grad(ll.sum(), Xg)
+        return ll.detach(), g
+
+    return logl, logl_grad
+
+
+def run_case(args, which, cycle):
+    import torch
+    from ptmcmcsampler_amd import _lib
+    from ptmcmcsampler_amd.engine import PTEngine
+    d, nt, W = args.ndim, args.ntemps, args.nwalkers
+    weights = (20, 0, 0) if cycle == "scam_hmc" else (0, 0, 0)
+    logl_name = ("iso",) if which == "iso" else ("interval", 0.0, 10.0)
+    g = PTEngine(d, nt, W, np.eye(d) * (0.5 if which == "interval" else 1.0), logl=logl_name, weights=weights, grad_weights=(0, 20),
+                 hmc=(args.eps, 2, args.hmc_steps), cov_update=100000, burn=100000, tskip=0, seed=5, split=True, cov_mode="pooled",
+                 am_mode="rows")
+    if which == "iso":
+        bl = g.builtin_logl()
+        logl = bl
+
+        def logl_grad(X):
+            return bl(X), -X
+        p0 = np.random.RandomState(0).randn(W, nt, d)
+    else:
+        logl, logl_grad = interval_callbacks(d)
+        x = np.clip(np.abs(np.random.RandomState(0).randn(W, nt, d)), 1e-6, 9.999)
+        p0 = np.log(x / 10.0) - np.log1p(-x / 10.0)
+    calls = [0]
+
+    def counted(X):
+        calls[0] += 1
+        return logl_grad(X)
+
+    g.init_state_callback(p0, logl, None)
+    g.run_callback(args.warmup, logl, None, logl_grad=counted)
+    g.sync()
+    nleap0 = g.get("gj")[..., _lib.GJ_NLEAP].sum()
+    calls[0] = 0
+    _lib.check(g.lib.ptmi_set_device_iter(g.h, 0))               # a marker launch: the timed region starts behind it
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    g.run_callback(args.iters, logl, None, logl_grad=counted)
+    g.sync()
+    wall = time.perf_counter() - t0
+    nleap = g.get("gj")[..., _lib.GJ_NLEAP].sum() - nleap0
+    js = g.get("jstat").astype(np.int64)
+    return dict(callback=which, cycle=cycle, ndim=d, ntemps=nt, nwalkers=W, iters=args.iters, wall_s=wall,
+                updates_per_s=W * nt * args.iters / wall, leapfrogs_per_s=float(nleap) / wall,
+                rounds_per_iter=calls[0] / args.iters, hmc_share=float(js[..., 4, 0].sum() / js[..., 0].sum()),
+                hmc_accept=float(js[..., 4, 1].sum() / max(1, js[..., 4, 0].sum())))
+
+
+def kernel_share(db, wall_s):
+    c = sqlite3.connect(db)
+    t0 = c.execute("select max(start) from kernels where name like '%set_iter_kernel%'").fetchone()[0]
+    rows = c.execute("select name, sum(end-start) from kernels where start >= ? group by name", (t0,)).fetchall()
+    lib = sum(r[1] for r in rows if any(k in r[0] for k in LIB_KERNELS)) / 1e9
+    other = sum(r[1] for r in rows if not any(k in r[0] for k in LIB_KERNELS)) / 1e9
+    top = sorted(rows, key=lambda r: -r[1])[:6]
+    return dict(library_kernels_s=lib, callback_kernels_s=other, library_share_of_wall=lib / wall_s, callback_share_of_wall=other / wall_s,
+                top=[(r[0][:80], r[1] / 1e9) for r in top])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ndim", type=int, default=40)
+    ap.add_argument("--ntemps", type=int, default=64)
+    ap.add_argument("--nwalkers", type=int, default=1024)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--eps", type=float, default=0.4)
+    ap.add_argument("--hmc-steps", type=int, default=50)
+    ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--only", nargs=2, metavar=("CALLBACK", "CYCLE"))
+    ap.add_argument("--out", default=None, help="profile databases go under this directory (default: a temporary one)")
+    args = ap.parse_args()
+    cases = [tuple(args.only)] if args.only else [(w, c) for w in ("interval", "iso") for c in ("scam_hmc", "hmc")]
+    for which, cycle in cases:
+        r = run_case(args, which, cycle)
+        if args.profile:
+            import tempfile
+            out = args.out or tempfile.mkdtemp()
+            name = "%s_%s" % (which, cycle)
+            cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", os.path.join(out, name), "-o", name, "--", sys.executable,
+                   os.path.abspath(__file__), "--only", which, cycle] + [
+                "--%s=%s" % (k.replace("_", "-"), getattr(args, k)) for k in ("ndim", "ntemps", "nwalkers", "iters", "warmup", "eps", "hmc_steps")]
+            p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+            if p.returncode != 0:
+                print(p.stdout[-3000:])
+                raise SystemExit("rocprofv3 run failed (%d)" % p.returncode)
+            prof = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+            dbs = [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(out, name)) for f in fs if f.endswith("_results.db")]
+            r["profiled_wall_s"] = prof["wall_s"]
+            r.update(kernel_share(dbs[0], prof["wall_s"]))
+        print(json.dumps(r), flush=True)
+
+
+if __name__ == "__main__":
+    main()
