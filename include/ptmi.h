@@ -379,12 +379,12 @@ int ptmi_proposals(ptmi_handle h, double **q);
  * costs one pass over the proposals.  PTMI_LOGL_ISO only.  On the handle's stream. */
 int ptmi_rows_logl(ptmi_handle h, const double *rows /* dev [n][ndim] */, int64_t n, double *out /* dev [n] */);
 
-/* HMC with the caller's batched GRADIENT callbacks on the split path (csrc/ptmi_gjcb.hip): HMCJump.__call__ of the reference
- * (NJ:238-291, NJ = PTMCMCSampler/nutsjump.py; whitening NJ:51-54, 71-90; leapfrog NJ:149-169) for every chain whose pick of the
- * iteration is HMC, with beta logL + logp and its gradient from the caller instead of a built-in family.  A split handle with
- * w_hmc > 0 draws the pick over w_scam + w_am + w_de + w_nuts + w_hmc (PT:225-258, as ptmi_mh_steps does); an HMC pick's proposal
- * row is the state itself until the stage below replaces it.  Per proposal launch (ptmi_propose(iter), or the propose half of
- * ptmi_accept_propose(iter - 1)):
+/* HMC and NUTS with the caller's batched GRADIENT callbacks on the split path (csrc/ptmi_gjcb.hip): HMCJump.__call__ (NJ:238-291,
+ * NJ = PTMCMCSampler/nutsjump.py; whitening NJ:51-54, 71-90; leapfrog NJ:149-169) and NUTSJump.__call__ (NJ:654-840) of the reference
+ * for every chain whose pick of the iteration is HMC or NUTS, with beta logL + logp and its gradient from the caller instead of a
+ * built-in family.  A split handle with w_nuts + w_hmc > 0 draws the pick over w_scam + w_am + w_de + w_nuts + w_hmc (PT:225-258, as
+ * ptmi_mh_steps does); an HMC or NUTS pick's proposal row is the state itself until the stage below replaces it.  Per proposal launch
+ * (ptmi_propose(iter), or the propose half of ptmi_accept_propose(iter - 1)):
  *
  *     ptmi_gj_begin(h, iter, work, rows, &n);
  *     while (n > 0) {
@@ -393,21 +393,32 @@ int ptmi_rows_logl(ptmi_handle h, const double *rows /* dev [n][ndim] */, int64_
  *     }
  *     likelihood callback on the proposals (ptmi_proposals), then ptmi_accept / ptmi_accept_propose
  *
- * ptmi_gj_begin lists the HMC chains in ascending chain slot (w * T + s: a stable compaction, no atomics: the rows come in the same
- * order on every run) and writes backward(forward(x)) of each into rows [n][ndim] -- L^T L^-T x, not x bitwise: the reference
- * evaluates func_grad_white(q0).  Each ptmi_gj_step is one round: it takes the callback's values for the n rows of the round before,
- * draws the momenta and nsteps = randint(hmc_min, hmc_max) at a chain's first round, finishes its leapfrog, applies the energy guard
- * (joint1 - 1000 < joint0, NJ:284-286) and either lists the chain again with its next drift or writes backward(q) into its row of
- * the current proposal buffer, qxy = joint1 - joint0 into qaux[.][0], and its calls / leapfrogs into gj[.][GJ_HITER] / [GJ_NLEAP].
- * The stage is over when n comes back 0.  The arithmetic is GradJump::hmc's (csrc/ptmi_gj.inc.h) operation for operation: given the
- * oracle's values and gradients the proposals are the bits of the fused kernels (tests/test_gj_callback_gpu.py).
+ * ptmi_gj_begin lists the HMC and NUTS chains in ascending chain slot (w * T + s: a stable compaction, no atomics: the rows come in the
+ * same order on every run) and writes backward(forward(x)) of each into rows [n][ndim] -- L^T L^-T x, not x bitwise: the reference
+ * evaluates func_grad_white(q0).  Each ptmi_gj_step is one round: it takes the callback's values for the n rows of the round before
+ * and advances each listed chain to its next gradient evaluation or the end of its call.  HMC: the momenta and nsteps = randint(hmc_min,
+ * hmc_max) at a chain's first round, then per round one leapfrog and the energy guard (joint1 - 1000 < joint0, NJ:284-286); at the end
+ * backward(q) into its row of the current proposal buffer, qxy = joint1 - joint0 into qaux[.][0], its calls / leapfrogs into
+ * gj[.][GJ_HITER] / [GJ_NLEAP].  NUTS: one round per leapfrog of the call -- on a chain's first NUTS call (gj[.][GJ_HAVE_EPS] = 0) the
+ * step-size search's (find_reasonable_epsilon, NJ:435-463, both loops bounded at 100 turns: up to ~200 rounds), then one per leaf of
+ * the doublings (NJ:716-802; heights 0..nuts_maxdepth); the merges with the pending left subtrees, the stop criteria and the draws run
+ * between them; at the end the dual averaging into gj[.][GJ_EPS..GJ_NITER], backward(sample) into the proposal buffer, qxy = logp0 -
+ * lnprob into qaux[.][0], the leapfrogs into gj[.][GJ_NLEAP].  The stage is over when n comes back 0.  The arithmetic is GradJump::hmc /
+ * ::nuts of csrc/ptmi_gj.inc.h operation for operation, the same Philox slots: given the oracle's values and gradients the proposals
+ * and the jump state are the bits of the fused kernels (tests/test_gj_callback_gpu.py, tests/test_gj_nuts_callback_gpu.py).
  *
  * work: caller-owned device memory of ptmi_gj_work_bytes bytes (the chains' whitened q and p, their stage scalars, the round's chain
- * list); rows: device [W*T][ndim] (a round lists at most every chain).  Each call reads n back to the host: one stream
- * synchronisation per round, the only one the stage adds.  ptmi_accept / ptmi_accept_propose refuse (PTMI_EINVAL) while the stage of
- * the current proposals has not ended; so do these calls out of sequence.  w_nuts > 0 on the split path, the shape kernels' split
- * path (PTMI_SPLIT_ROWS=0, or a handle ptmi_split_rows_ok does not take), ptmi_device_iter mode and parameter groups are refused
- * (PTMI_EUNSUPPORTED).  On the handle's stream. */
+ * list; with w_nuts > 0 also every chain's NUTS call and tree stack).  With nch = nwalkers * ntemps, d = ndim, al(b) = b rounded up to
+ * 16 bytes and L = nuts_maxdepth + 1:
+ *     HMC only:    al(8 nch d) * 3 + al(8 nch) + al(16 nch) + al(4 nch) + al(4 ceil(nch / 1024)) + 16
+ *     w_nuts > 0:  the above + al(8 (10 + 3 L) nch d) + al(72 nch) + al(40 nch) + al(32 L nch)
+ * i.e. 10 + 3 L vectors of d doubles per chain for NUTS (the call's initial point, gradient and search momenta, the sample, both ends
+ * of the trajectory with their momenta and gradients; per stack height a pending left subtree's far end, its momentum and candidate)
+ * -- 88 vectors with the HMC ones at nuts_maxdepth = 24: 1.85 GB at 64 x 1024 chains of 40 parameters.  rows: device [W*T][ndim] (a
+ * round lists at most every chain).  Each call reads n back to the host: one stream synchronisation per round, the only one the stage
+ * adds.  ptmi_accept / ptmi_accept_propose refuse (PTMI_EINVAL) while the stage of the current proposals has not ended; so do these
+ * calls out of sequence.  The shape kernels' split path (PTMI_SPLIT_ROWS=0, or a handle ptmi_split_rows_ok does not take),
+ * ptmi_device_iter mode and parameter groups are refused (PTMI_EUNSUPPORTED).  On the handle's stream. */
 int ptmi_gj_work_bytes(ptmi_handle h, size_t *bytes);
 int ptmi_gj_begin(ptmi_handle h, int64_t iter, void *work, double *rows /* dev [W*T][ndim] */, int64_t *n);
 int ptmi_gj_step(ptmi_handle h, void *work, const double *lnl /* dev [n] */, const double *dlnl /* dev [n][ndim] */,

@@ -2857,17 +2857,18 @@ int ptmi_last_mh_variant(ptmi_handle h, int32_t *variant)
     return PTMI_OK;
 }
 
-// HMC on the split path (ptmi_gjcb.hip): proposals of `iter` were just made -- with HMC in the cycle their gradient stage is pending
+// HMC and NUTS on the split path (ptmi_gjcb.hip): proposals of `iter` were just made -- with gradient jumps in the cycle their gradient
+// stage is pending
 static void gj_proposed(ptmi_engine *h, long long iter)
 {
-    h->gj_phase = h->cfg.w_hmc > 0 ? PTMI_GJ_PENDING : PTMI_GJ_NONE;
+    h->gj_phase = h->cfg.w_nuts + h->cfg.w_hmc > 0 ? PTMI_GJ_PENDING : PTMI_GJ_NONE;
     h->gj_iter = iter;
 }
 // ... and an accept test may only read them once that stage is over
 static int gj_stage_over(const ptmi_engine *h, const char *who, int64_t iter)
 {
     if (h->gj_phase == PTMI_GJ_PENDING || h->gj_phase == PTMI_GJ_ROUNDS)
-        return fail(PTMI_EINVAL, "%s(%lld): the HMC proposals of iteration %lld are not made yet -- ptmi_gj_begin and ptmi_gj_step until n = 0 first",
+        return fail(PTMI_EINVAL, "%s(%lld): the HMC / NUTS proposals of iteration %lld are not made yet -- ptmi_gj_begin and ptmi_gj_step until n = 0 first",
                     who, (long long)iter, h->gj_iter);
     return PTMI_OK;
 }

@@ -109,6 +109,10 @@ class PTEngine(object):
     reference's behaviour.  A lower value is an engine option (bounded cost per call).  Memory: the tree scratch holds
     7 + 4 (maxdepth + 1) vectors of ndim doubles and 4 (maxdepth + 1) scalars per chain (107 vectors at 24, 51 at 10):
     86 KB per chain at ndim = 100, i.e. 22 GB for 262 144 chains -- lower it for very large batches.
+    ``split_nuts=True`` (with ``split=True``): NUTS on the callback path too -- ``grad_weights=(w_nuts, w_hmc)`` with ``w_nuts > 0``,
+    the trees built round by round from the batched gradient callbacks (``gradient_stage``).  Opt-in: an iteration then takes as
+    many host-synchronised callback rounds as its deepest tree has leaves (a chain's first NUTS call up to ~200 more for the
+    step-size search), and the stage's work area grows with ``nuts_maxdepth`` (include/ptmi.h ``ptmi_gj_work_bytes``).
     ``eig_mode``: who factorizes the adapted covariance at a covariance epoch (PTMCMCSampler.py:797-803): ``"lapack"`` = the
     host, exactly as the reference (``np.linalg.svd`` per walker); ``"jacobi"`` = ``ptmi_eig_jacobi`` on the device, one
     block per walker, no host round trip (ndim <= 101, one parameter group; same subspaces, its own sign rule); ``"ql"`` =
@@ -153,7 +157,7 @@ class PTEngine(object):
                  ntemps_global=None, temp0=0, walker0=0, device=0, split=False, use_de_buffer=None,
                  w_host=0, keep_lnl=False, groups=None, swap_mode="sweep",
                  grad_weights=(0, 0), hmc=(0.1, 2, 300), nuts_delta=0.6, nuts_maxdepth=24, pick_mode="chain",
-                 eig_mode="lapack", am_mode="auto", eig_lag=0, stats_async=False):
+                 eig_mode="lapack", am_mode="auto", eig_lag=0, stats_async=False, split_nuts=False):
         torch = _torch()
         self.lib = _lib.load()
         if not torch.cuda.is_available() or _lib.device_count() < 1:
@@ -208,8 +212,11 @@ class PTEngine(object):
         # gradient jumps on the built-in likelihoods (PTMCMCSampler.py:225-258): (NUTSweight, HMCweight); the whitening
         # comes from the INITIAL covariance and is never adapted (nutsjump.py:45, 53-54)
         self.grad_weights = tuple(int(w) for w in grad_weights)
-        if split and self.grad_weights[0] > 0:
+        if split_nuts and not split:
+            raise ValueError("split_nuts=True is NUTS on the callback path: it needs split=True")
+        if split and self.grad_weights[0] > 0 and not split_nuts:
             raise ValueError("the callback path (split=True) runs HMC with batched gradient callbacks, not NUTS: grad_weights=(0, w_hmc)")
+        self.split_nuts = bool(split_nuts)
         has_gj = sum(self.grad_weights) > 0
         self.gj_tab = np.zeros(0)
         if has_gj:
@@ -907,14 +914,14 @@ class PTEngine(object):
         return v, g
 
     def gradient_stage(self, it, logl_grad, logp_grad=None):
-        """The HMC picks of the proposals of iteration ``it`` (just made by ptmi_propose / ptmi_accept_propose): rounds of
+        """The HMC and NUTS picks of the proposals of iteration ``it`` (just made by ptmi_propose / ptmi_accept_propose): rounds of
         ``logl_grad(X[n, d]) -> (lnL[n], dlnL[n, d])`` (and ``logp_grad``, the same shape; None: a flat prior, no launch) on the rows the
-        library lists (``ptmi_gj_begin`` / ``ptmi_gj_step``, include/ptmi.h), until every chain's trajectory has ended.  Returns the
-        number of rounds.  A no-op without HMC in the cycle."""
-        if self.grad_weights[1] <= 0:
+        library lists (``ptmi_gj_begin`` / ``ptmi_gj_step``, include/ptmi.h), until every chain's trajectory or tree has ended: one
+        round per leapfrog of the longest.  Returns the number of rounds.  A no-op without gradient jumps in the cycle."""
+        if sum(self.grad_weights) <= 0:
             return 0
         if logl_grad is None:
-            raise ValueError("HMC is in the cycle (grad_weights=%r): the callback path needs logl_grad" % (self.grad_weights,))
+            raise ValueError("gradient jumps are in the cycle (grad_weights=%r): the callback path needs logl_grad" % (self.grad_weights,))
         torch = _torch()
         if getattr(self, "_gj_work", None) is None:
             nb = C.c_size_t(0)
@@ -937,7 +944,7 @@ class PTEngine(object):
         return rounds
 
     def split_step(self, it, logl, logp, logl_grad=None, logp_grad=None):
-        """One iteration of every chain with batched callbacks: ptmi_propose -> (HMC in the cycle: the gradient stage,
+        """One iteration of every chain with batched callbacks: ptmi_propose -> (HMC / NUTS in the cycle: the gradient stage,
         ``gradient_stage``) -> callbacks on the device tensor of proposals -> ptmi_accept.  All on the engine's stream; no host copy of
         the proposals."""
         if self.t["Q"] is None:
@@ -987,7 +994,7 @@ class PTEngine(object):
         """Iterations ``it .. end`` with nothing between them (no epoch, no swap: a segment of ``run``): ONE proposal launch, then per
         iteration the callbacks on the device tensor of proposals and ptmi_accept_propose -- the accept test of iteration j and the
         proposal of j + 1 in one launch, a chain's row in once and out once (csrc/ptmi_split.hip) -- and ptmi_accept behind the last.
-        With HMC in the cycle every proposal launch is followed by its gradient stage (``gradient_stage``: the batched gradient
+        With HMC or NUTS in the cycle every proposal launch is followed by its gradient stage (``gradient_stage``: the batched gradient
         callbacks ``logl_grad`` / ``logp_grad``).  The same chains as ``split_step`` iteration by iteration, bit for bit."""
         if self.t["Q"] is None:
             raise _lib.PtmiError("the callback path needs the engine built with split=True")
@@ -1019,10 +1026,10 @@ class PTEngine(object):
         must be graph-safe (no host synchronisation, the same launches for every batch: any fixed torch expression or device
         kernel is).  What the captured launches bake in -- the DE ring's head, whether DE is in the cycle -- is part of the cache
         key.  Returns False where it does not apply (AM entries in the cycle: their increments are listed on the host's iteration;
-        configurations the row kernels do not serve; HMC in the cycle: its rounds are counted on the host): the caller then runs
+        configurations the row kernels do not serve; HMC or NUTS in the cycle: their rounds are counted on the host): the caller then runs
         ``callback_segment``.  Same results, bit for bit."""
         torch = _torch()
-        if self.t["Q2"] is None or self.weights[1] > 0 or self.grad_weights[1] > 0:
+        if self.t["Q2"] is None or self.weights[1] > 0 or sum(self.grad_weights) > 0:
             return False
         if getattr(self, "_graphs", None) is None:
             self._graphs = {}
@@ -1064,8 +1071,8 @@ class PTEngine(object):
         late table of ``eig_lag`` counted in segments as ``run`` counts it in launches).  ``fused=False``: propose / accept as two
         launches per iteration (``split_step``; same results).  ``graph=True``: every segment one hipGraph launch
         (``callback_segment_graph``: for small, launch-bound batches with graph-safe callbacks; same results).  HMC in the cycle
-        (``grad_weights=(0, w)``): ``logl_grad(X[n, d]) -> (lnL[n], dlnL[n, d])`` and ``logp_grad`` (None: a flat prior) serve its
-        trajectories (``gradient_stage``)."""
+        (``grad_weights=(0, w)``), or NUTS too (``grad_weights=(w_nuts, w_hmc)``, ``split_nuts=True``): ``logl_grad(X[n, d]) ->
+        (lnL[n], dlnL[n, d])`` and ``logp_grad`` (None: a flat prior) serve their trajectories (``gradient_stage``)."""
         last = self.iter + niter
         it = self.iter + 1
         while it <= last:

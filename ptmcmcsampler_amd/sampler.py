@@ -21,7 +21,8 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
   ``_function_wrapper`` (PTMCMCSampler.py:1072-1086), one call per batch instead of one per chain, nothing copied to the
   host; custom Python jumps cannot be mixed in.  With ``logl_grad`` / ``logp_grad`` as batched callbacks too --
   ``f(X[n, ndim]) -> (value[n], gradient[n, ndim])`` -- HMC (``HMCweight``) runs on the device with the callbacks' gradients
-  (``PTEngine.gradient_stage``); NUTS is not built for them (pass ``NUTSweight=0``);
+  (``PTEngine.gradient_stage``); NUTS (``NUTSweight``) too with ``batched_nuts=True`` -- opt-in: an iteration takes as many
+  callback rounds as its deepest tree has leaves (without it pass ``NUTSweight=0``);
 * engine options: ``cov_mode="pooled"`` (one covariance adapted from all walkers instead of one per walker),
   ``swap_mode="oddeven"`` (disjoint swap pairs instead of the reference's hot -> cold sweep), ``pick_mode="walker"`` (one
   proposal-type draw per walker and iteration), ``eig_mode="ql"`` / ``"jacobi"`` / ``"sytrd"`` / ``"hipsolver"`` (covariance epochs factorized on the device: per-walker matrices by
@@ -120,7 +121,7 @@ class PTSampler(object):
     def __init__(self, ndim, logl, logp, cov, groups=None, loglargs=[], loglkwargs={}, logpargs=[], logpkwargs={},
                  logl_grad=None, logp_grad=None, comm=None, outDir="./chains", verbose=True, resume=False, seed=None,
                  nwalkers=1, ntemps=None, device=0, cov_mode="per_walker", keep_walkers=1, swap_mode="sweep",
-                 pick_mode="chain", eig_mode="lapack", checkpoint=None, batched=False, nuts_maxdepth=24):
+                 pick_mode="chain", eig_mode="lapack", checkpoint=None, batched=False, nuts_maxdepth=24, batched_nuts=False):
         self.comm = comm if comm is not None else _DummyComm()
         if self.comm.Get_size() != 1:
             raise NotImplementedError(
@@ -155,6 +156,11 @@ class PTSampler(object):
         if self.logl_spec is None and logl_grad is not None and logp_grad is not None:
             self.logl_grad = _function_wrapper(logl_grad, loglargs, loglkwargs)
             self.logp_grad = _function_wrapper(logp_grad, logpargs, logpkwargs)
+        # batched_nuts=True: NUTS on the batched gradient callbacks too (PTEngine(split_nuts=True))
+        self.batched_nuts = bool(batched_nuts)
+        if self.batched_nuts and not (self.batched and self.logl_grad is not None and self.logp_grad is not None):
+            raise ValueError("batched_nuts=True runs NUTS on batched gradient callbacks: it needs batched=True with callable logl_grad and "
+                             "logp_grad")
         self.outDir, self.verbose, self.resume = outDir, verbose, resume
         if not os.path.exists(self.outDir):
             try:
@@ -221,11 +227,12 @@ class PTSampler(object):
                    HMCsteps=300, maxIter=None, thin=10, i0=0, neff=None, writeHotChains=False, hotChain=False):
         from .engine import PTEngine
         # batched gradient callbacks (batched=True with logl_grad / logp_grad): HMC runs on the device between the proposal launch and
-        # the likelihood callback, the gradients from the callbacks (PTEngine.gradient_stage); NUTS is not built for them
+        # the likelihood callback, the gradients from the callbacks (PTEngine.gradient_stage); NUTS too with batched_nuts=True
         self._batched_grads = self.batched and self.logl_grad is not None and self.logp_grad is not None
-        if self._batched_grads and NUTSweight > 0:
-            raise NotImplementedError("batched gradient callbacks (batched=True with logl_grad / logp_grad) run HMC only: NUTS is not "
-                                      "built for them (NUTSweight=%r); pass NUTSweight=0" % (NUTSweight,))
+        if self._batched_grads and NUTSweight > 0 and not self.batched_nuts:
+            raise NotImplementedError("batched gradient callbacks (batched=True with logl_grad / logp_grad) run HMC only unless NUTS is "
+                                      "asked for (NUTSweight=%r): pass NUTSweight=0, or batched_nuts=True to build the NUTS trees "
+                                      "round by round from the callbacks" % (NUTSweight,))
         if maxIter is None:
             maxIter = Niter
         self.ladder, self.covUpdate, self.burn, self.Tskip = ladder, covUpdate, burn, Tskip
@@ -352,6 +359,7 @@ class PTSampler(object):
             weights=(self.SCAMweight, self.AMweight, self.DEweight), cov_update=covUpdate, burn=burn, tskip=Tskip,
             seed=self.seed, cov_mode=self.cov_mode, hot_chain=hotChain, device=self.device_index, split=self.split,
             swap_mode=self.swap_mode, pick_mode=self.pick_mode, eig_mode=self.eig_mode, grad_weights=self._grad_weights, hmc=(HMCstepsize, 2, HMCsteps), nuts_maxdepth=self.nuts_maxdepth,
+            split_nuts=self._batched_grads and self.batched_nuts,
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     # ------------------------------------------------------------------ sample (:374-528)
@@ -736,7 +744,7 @@ class PTSampler(object):
         return ll, lp
 
     def _grad_callbacks(self):
-        """(logl_grad, logp_grad) for the engine's gradient stage: the batched callbacks when HMC runs on them, else (None, None)."""
+        """(logl_grad, logp_grad) for the engine's gradient stage: the batched callbacks when HMC / NUTS run on them, else (None, None)."""
         return (self.logl_grad, self.logp_grad) if getattr(self, "_batched_grads", False) else (None, None)
 
     def _init_split(self, p0, i0=0):

@@ -1,10 +1,13 @@
 #!/usr/bin/env python
-"""HMC through batched gradient callbacks (PTEngine.gradient_stage, csrc/ptmi_gjcb.hip) at full size: updates/s, leapfrogs/s, callback
-rounds per iteration, and -- with --profile -- the library's kernels' share of the wall time against the callback's.
+"""HMC and NUTS through batched gradient callbacks (PTEngine.gradient_stage, csrc/ptmi_gjcb.hip) at full size: updates/s, leapfrogs/s,
+callback rounds per iteration (mean, max), rows per round (mean, and the share of rounds that list fewer than 1 % of the chains), and --
+with --profile -- the library's kernels' share of the wall time against the callback's.
 
-    python tools/gj_callback_timing.py [--ntemps 64 --nwalkers 1024 --ndim 40 --iters 50 --warmup 10] [--profile]
+    python tools/gj_callback_timing.py [--ntemps 64 --nwalkers 1024 --ndim 40 --iters 50 --warmup 10] [--profile] [--only CALLBACK CYCLE]
 
-Two callbacks, each with two cycles (SCAM + HMC, HMC only):
+Two callbacks, each with five cycles -- SCAM + HMC, HMC only, NUTS only, SCAM + NUTS, and sample()'s default mix SCAM = AM = DE = NUTS =
+HMC = 20 (NUTS on the split path: PTEngine(split_nuts=True)).  The NUTS cycles are timed in steady state: after --nuts-warmup
+iterations (default 30), when every chain has made its first NUTS call (its step-size search) -- the share that has is reported:
   * interval: the reference's own gradient workload (tests/test_nuts.py: a unit Gaussian behind intervalTransform on (0, 10)) as a
     torch expression, its gradient by autograd;
   * iso: the built-in isotropic Gaussian (ptmi_rows_logl, one pass over the rows) with -X as its gradient -- the stage's own cost
@@ -52,11 +55,15 @@ def run_case(args, which, cycle):
     from ptmcmcsampler_amd import _lib
     from ptmcmcsampler_amd.engine import PTEngine
     d, nt, W = args.ndim, args.ntemps, args.nwalkers
-    weights = (20, 0, 0) if cycle == "scam_hmc" else (0, 0, 0)
+    weights, grad_weights = CYCLES[cycle]
+    nuts = grad_weights[0] > 0
+    warmup = args.nuts_warmup if nuts else args.warmup
+    # the default mix: its covariance epoch, DE's start and the end of NUTS's step-size adaptation all fall inside the warm-up
+    burn = warmup if weights[1] + weights[2] > 0 else 100000
     logl_name = ("iso",) if which == "iso" else ("interval", 0.0, 10.0)
-    g = PTEngine(d, nt, W, np.eye(d) * (0.5 if which == "interval" else 1.0), logl=logl_name, weights=weights, grad_weights=(0, 20),
-                 hmc=(args.eps, 2, args.hmc_steps), cov_update=100000, burn=100000, tskip=0, seed=5, split=True, cov_mode="pooled",
-                 am_mode="rows")
+    g = PTEngine(d, nt, W, np.eye(d) * (0.5 if which == "interval" else 1.0), logl=logl_name, weights=weights, grad_weights=grad_weights,
+                 hmc=(args.eps, 2, args.hmc_steps), cov_update=burn, burn=burn, tskip=0, seed=5, split=True, split_nuts=nuts,
+                 cov_mode="pooled", am_mode="rows")
     if which == "iso":
         bl = g.builtin_logl()
         logl = bl
@@ -68,29 +75,52 @@ def run_case(args, which, cycle):
         logl, logl_grad = interval_callbacks(d)
         x = np.clip(np.abs(np.random.RandomState(0).randn(W, nt, d)), 1e-6, 9.999)
         p0 = np.log(x / 10.0) - np.log1p(-x / 10.0)
-    calls = [0]
+    rows = [[]]                                                  # rows of every round, per iteration (the likelihood callback ends one)
+
+    def counted_logl(X):
+        rows.append([])
+        return logl(X)
 
     def counted(X):
-        calls[0] += 1
+        rows[-1].append(X.shape[0])
         return logl_grad(X)
 
     g.init_state_callback(p0, logl, None)
-    g.run_callback(args.warmup, logl, None, logl_grad=counted)
+    g.run_callback(warmup, logl, None, logl_grad=counted)
     g.sync()
-    nleap0 = g.get("gj")[..., _lib.GJ_NLEAP].sum()
-    calls[0] = 0
+    gj0 = g.get("gj")
+    js0 = g.get("jstat").astype(np.int64)
+    rows[:] = [[]]
     _lib.check(g.lib.ptmi_set_device_iter(g.h, 0))               # a marker launch: the timed region starts behind it
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    g.run_callback(args.iters, logl, None, logl_grad=counted)
+    g.run_callback(args.iters, counted_logl, None, logl_grad=counted)
     g.sync()
     wall = time.perf_counter() - t0
-    nleap = g.get("gj")[..., _lib.GJ_NLEAP].sum() - nleap0
-    js = g.get("jstat").astype(np.int64)
-    return dict(callback=which, cycle=cycle, ndim=d, ntemps=nt, nwalkers=W, iters=args.iters, wall_s=wall,
-                updates_per_s=W * nt * args.iters / wall, leapfrogs_per_s=float(nleap) / wall,
-                rounds_per_iter=calls[0] / args.iters, hmc_share=float(js[..., 4, 0].sum() / js[..., 0].sum()),
-                hmc_accept=float(js[..., 4, 1].sum() / max(1, js[..., 4, 0].sum())))
+    gj = g.get("gj")
+    nleap = gj[..., _lib.GJ_NLEAP].sum() - gj0[..., _lib.GJ_NLEAP].sum()
+    js = g.get("jstat").astype(np.int64) - js0
+    # rows[k]: the rounds of iteration k + 1's stage (each likelihood call opens the next iteration's list; the last one stays empty)
+    nrounds = np.array([len(r) for r in rows[:args.iters]], dtype=np.int64)
+    allrows = np.array([n for r in rows for n in r], dtype=np.int64)
+    r = dict(callback=which, cycle=cycle, ndim=d, ntemps=nt, nwalkers=W, iters=args.iters, wall_s=wall,
+             updates_per_s=W * nt * args.iters / wall, leapfrogs_per_s=float(nleap) / wall,
+             rounds_per_iter=float(allrows.size) / args.iters, rounds_per_iter_max=int(nrounds.max()) if nrounds.size else 0,
+             rows_per_round=float(allrows.mean()) if allrows.size else 0.0,
+             rounds_under_1pct=float((allrows < 0.01 * W * nt).mean()) if allrows.size else 0.0,
+             hmc_share=float(js[..., 4, 0].sum() / js[..., 0].sum()), hmc_accept=float(js[..., 4, 1].sum() / max(1, js[..., 4, 0].sum())))
+    if nuts:
+        r.update(nuts_share=float(js[..., 3, 0].sum() / js[..., 0].sum()), nuts_accept=float(js[..., 3, 1].sum() / max(1, js[..., 3, 0].sum())),
+                 past_first_call=float((gj0[..., _lib.GJ_HAVE_EPS] == 1.0).mean()),
+                 leapfrogs_per_nuts_call=float((gj[..., _lib.GJ_NLEAP].sum() - gj0[..., _lib.GJ_NLEAP].sum()) /
+                                               max(1.0, gj[..., _lib.GJ_NITER].sum() + gj[..., _lib.GJ_HITER].sum()
+                                                   - gj0[..., _lib.GJ_NITER].sum() - gj0[..., _lib.GJ_HITER].sum())))
+    return r
+
+
+# cycle -> (SCAM, AM, DE weights), (NUTS, HMC weights)
+CYCLES = {"scam_hmc": ((20, 0, 0), (0, 20)), "hmc": ((0, 0, 0), (0, 20)), "nuts": ((0, 0, 0), (20, 0)), "scam_nuts": ((20, 0, 0), (20, 0)),
+          "default_mix": ((20, 20, 20), (20, 20))}
 
 
 def kernel_share(db, wall_s):
@@ -111,13 +141,14 @@ def main():
     ap.add_argument("--nwalkers", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--nuts-warmup", type=int, default=30)
     ap.add_argument("--eps", type=float, default=0.4)
     ap.add_argument("--hmc-steps", type=int, default=50)
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--only", nargs=2, metavar=("CALLBACK", "CYCLE"))
     ap.add_argument("--out", default=None, help="profile databases go under this directory (default: a temporary one)")
     args = ap.parse_args()
-    cases = [tuple(args.only)] if args.only else [(w, c) for w in ("interval", "iso") for c in ("scam_hmc", "hmc")]
+    cases = [tuple(args.only)] if args.only else [(w, c) for w in ("interval", "iso") for c in CYCLES]
     for which, cycle in cases:
         r = run_case(args, which, cycle)
         if args.profile:
@@ -126,7 +157,8 @@ def main():
             name = "%s_%s" % (which, cycle)
             cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", os.path.join(out, name), "-o", name, "--", sys.executable,
                    os.path.abspath(__file__), "--only", which, cycle] + [
-                "--%s=%s" % (k.replace("_", "-"), getattr(args, k)) for k in ("ndim", "ntemps", "nwalkers", "iters", "warmup", "eps", "hmc_steps")]
+                "--%s=%s" % (k.replace("_", "-"), getattr(args, k)) for k in ("ndim", "ntemps", "nwalkers", "iters", "warmup", "nuts_warmup", "eps",
+                                                                              "hmc_steps")]
             p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
             if p.returncode != 0:
                 print(p.stdout[-3000:])
