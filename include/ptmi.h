@@ -376,8 +376,19 @@ int ptmi_proposals(ptmi_handle h, double **q);
 /* The handle's built-in likelihood of n rows [n][ndim] anywhere on the device (the proposals, say), with the BITS the fused kernels
  * give it (the same lanes, the same summation order): a likelihood "callback" that is a device kernel behind the C ABI -- with it
  * the split path reproduces the fused path bit for bit at any size (tests), and bench.py times the split path with a callback that
- * costs one pass over the proposals.  PTMI_LOGL_ISO only.  On the handle's stream. */
+ * costs one pass over the proposals.  PTMI_LOGL_ISO (oracle/ptmcmc_oracle.c eval_logl: -lane_dot(x, x) / 2) and PTMI_LOGL_DENSE
+ * (eval_logl; the reference's tests/test_simple.py:14-41: r = x - mu, v = the k-ascending fma chains of r through the half table Tl,
+ * -lane_dot(r, v) -- on the matrix cores, csrc/ptmi_dense_rows.hip; any ndim the handle takes, rows with inf / NaN as the oracle
+ * gives them); the other families: PTMI_EUNSUPPORTED.  On the handle's stream, no host synchronisation, graph-capturable. */
 int ptmi_rows_logl(ptmi_handle h, const double *rows /* dev [n][ndim] */, int64_t n, double *out /* dev [n] */);
+/* ... and its gradient with it (oracle: eval_logl_grad, exported as orc_logl_grad): PTMI_LOGL_ISO -x (the reference's
+ * tests/test_nuts.py:22-25), PTMI_LOGL_DENSE -(Pt r), the FULL product with P as given, one k-ascending fma chain per element.
+ * (lnl, dlnl) is the form ptmi_gj_step takes.  Same stream rules. */
+int ptmi_rows_logl_grad(ptmi_handle h, const double *rows /* dev [n][ndim] */, int64_t n, double *lnl /* dev [n] */, double *dlnl /* dev [n][ndim] */);
+/* The handle's built-in prior of n rows (oracle: eval_logp; the reference's tests/test_simple.py:36-41): PTMI_LOGP_FLAT 0;
+ * PTMI_LOGP_BOX -inf unless lo <= x <= hi in every element (a NaN element: -inf).  dlp (or NULL): its gradient, zeros (func_grad_white
+ * of the oracle: "gradient of the built-in priors is zero").  Same stream rules. */
+int ptmi_rows_logp(ptmi_handle h, const double *rows /* dev [n][ndim] */, int64_t n, double *lp /* dev [n] */, double *dlp /* dev [n][ndim] or NULL */);
 
 /* HMC and NUTS with the caller's batched GRADIENT callbacks on the split path (csrc/ptmi_gjcb.hip): HMCJump.__call__ (NJ:238-291,
  * NJ = PTMCMCSampler/nutsjump.py; whitening NJ:51-54, 71-90; leapfrog NJ:149-169) and NUTSJump.__call__ (NJ:654-840) of the reference

@@ -2979,10 +2979,37 @@ int ptmi_accept_propose(ptmi_handle h, int64_t iter, const double *newlnL, const
 int ptmi_rows_logl(ptmi_handle h, const double *rows, int64_t n, double *out)
 {
     if (!h || !rows || !out || n < 0) return fail(PTMI_EINVAL, "bad argument");
-    if (h->cfg.logl_kind != PTMI_LOGL_ISO) return fail(PTMI_EUNSUPPORTED, "ptmi_rows_logl serves the isotropic Gaussian (PTMI_LOGL_ISO)");
+    const int L = h->cfg.logl_kind;
+    if (L != PTMI_LOGL_ISO && L != PTMI_LOGL_DENSE)
+        return fail(PTMI_EUNSUPPORTED, "ptmi_rows_logl serves the isotropic and the dense Gaussian (PTMI_LOGL_ISO, PTMI_LOGL_DENSE)");
     if (n == 0) return PTMI_OK;
-    if (int rc = ptmi_rows_iso(h, rows, (long long)n, out)) return rc;
+    if (int rc = L == PTMI_LOGL_ISO ? ptmi_rows_iso(h, rows, (long long)n, out) : ptmi_rows_dense(h, rows, (long long)n, out, nullptr)) return rc;
     HIPCHK(hipGetLastError());
+    return PTMI_OK;
+}
+
+int ptmi_rows_logl_grad(ptmi_handle h, const double *rows, int64_t n, double *lnl, double *dlnl)
+{
+    if (!h || !rows || !lnl || !dlnl || n < 0) return fail(PTMI_EINVAL, "bad argument");
+    const int L = h->cfg.logl_kind;
+    if (L != PTMI_LOGL_ISO && L != PTMI_LOGL_DENSE)
+        return fail(PTMI_EUNSUPPORTED, "ptmi_rows_logl_grad serves the isotropic and the dense Gaussian (PTMI_LOGL_ISO, PTMI_LOGL_DENSE)");
+    if (n == 0) return PTMI_OK;
+    if (L == PTMI_LOGL_ISO) {
+        if (int rc = ptmi_rows_iso(h, rows, (long long)n, lnl)) return rc;
+        if (int rc = ptmi_rows_neg(h, rows, (long long)n, dlnl)) return rc;
+    } else if (int rc = ptmi_rows_dense(h, rows, (long long)n, lnl, dlnl)) return rc;
+    HIPCHK(hipGetLastError());
+    return PTMI_OK;
+}
+
+int ptmi_rows_logp(ptmi_handle h, const double *rows, int64_t n, double *lp, double *dlp)
+{
+    if (!h || !rows || !lp || n < 0) return fail(PTMI_EINVAL, "bad argument");
+    if (n == 0) return PTMI_OK;
+    if (int rc = ptmi_rows_prior(h, rows, (long long)n, lp)) return rc;
+    HIPCHK(hipGetLastError());
+    if (dlp) HIPCHK(hipMemsetAsync(dlp, 0, sizeof(double) * (size_t)n * h->cfg.ndim, h->stream));      // the built-in priors are flat where finite
     return PTMI_OK;
 }
 

@@ -216,6 +216,10 @@ int ptmi_gj_split_check(const ptmi_engine *h);
 bool ptmi_split_rows_ok(const ptmi_engine *h);
 int ptmi_split_rows(ptmi_engine *h, const KArgs &a, int mode);
 int ptmi_rows_iso(ptmi_engine *h, const double *rows, long long n, double *out);
+// built-in dense Gaussian / priors over rows (ptmi_dense_rows.hip): value (+ gradient when grad != nullptr); -x; the prior's value
+int ptmi_rows_dense(ptmi_engine *h, const double *rows, long long n, double *out, double *grad);
+int ptmi_rows_neg(ptmi_engine *h, const double *rows, long long n, double *grad);
+int ptmi_rows_prior(ptmi_engine *h, const double *rows, long long n, double *lp);
 int ptmi_set_iter_device(ptmi_engine *h, long long *p, long long v);
 extern "C" int ptmi_split_am_prepare(ptmi_handle h, int64_t iter0, int32_t nsteps);
 

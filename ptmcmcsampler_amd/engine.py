@@ -143,6 +143,14 @@ class PTEngine(object):
     ``AMflag``; oracle: ``orc_pool_update_rle`` -- the same sample covariance, summed in another order).  Readers that want
     every row (``get("AM")``, the DE history, chain files) get the repeats copied forward first (``am_expand``).
     ``"auto"`` = ``"rle"`` where it applies.
+    ``rows_logl=True`` (``logl`` ("iso",) or ("dense", mu, P)): ``init_state`` / ``run`` / ``mh_steps`` take the split path -- propose, the
+    built-in likelihood and prior as ROW kernels over the launch's proposals (``ptmi_rows_logl``, ``ptmi_rows_logp``; for the dense
+    family one matrix-core product per iteration, csrc/ptmi_dense_rows.hip), accept -- instead of the fused step kernels, which beyond
+    104 parameters stream the d x d table per chain-step from L2.  The same chains bit for bit (the row kernels restate the oracle's
+    sums); HMC / NUTS in the cycle are served by ``ptmi_rows_logl_grad`` through the batched gradient stage (ndim <= 512).  Whatever
+    ``run_callback`` supports; not with ``w_host`` or a sharded ladder (``ntemps_global`` / ``temp0``).  ``am_mode="auto"`` is ``"rows"``
+    here (the split path stores every rank-0 row), so with a POOLED covariance the bits are those of the fused path with
+    ``am_mode="rows"``; its default ``"rle"`` sums the same pooled statistics in another order.
     ``stats_async`` (pooled covariance with ``eig_lag >= 1``): the statistics of a covariance period that is over need nothing the next
     launches touch once those write ANOTHER ring -- so the engine keeps two rings (``t["AM"]`` is always the one in use), switches at
     every covariance epoch, and runs the period's statistics (``ptmi_update_cov_on``) and the factorization behind them on a side
@@ -157,8 +165,21 @@ class PTEngine(object):
                  ntemps_global=None, temp0=0, walker0=0, device=0, split=False, use_de_buffer=None,
                  w_host=0, keep_lnl=False, groups=None, swap_mode="sweep",
                  grad_weights=(0, 0), hmc=(0.1, 2, 300), nuts_delta=0.6, nuts_maxdepth=24, pick_mode="chain",
-                 eig_mode="lapack", am_mode="auto", eig_lag=0, stats_async=False, split_nuts=False):
+                 eig_mode="lapack", am_mode="auto", eig_lag=0, stats_async=False, split_nuts=False, rows_logl=False):
         torch = _torch()
+        # rows_logl: the built-in likelihood as a row kernel on the split path (see the class docstring); refused before anything is built
+        self.rows_logl = bool(rows_logl)
+        if self.rows_logl:
+            if logl[0] not in ("iso", "dense"):
+                raise ValueError("rows_logl=True serves logl=('iso',) and ('dense', mu, P) (ptmi_rows_logl), not %r" % (logl[0],))
+            if int(w_host) > 0:
+                raise ValueError("rows_logl=True cannot be combined with w_host > 0: host-served jumps need the caller's own callbacks")
+            if (ntemps_global is not None and int(ntemps_global) != int(ntemps)) or int(temp0) != 0:
+                raise ValueError("rows_logl=True cannot be combined with ntemps_global / temp0 (a sharded ladder): run_callback swaps the whole ladder on one GPU")
+            split = True
+            split_nuts = split_nuts or int(grad_weights[0]) > 0
+            if am_mode == "auto":
+                am_mode = "rows"                                      # the split path stores every rank-0 row: the statistics sum in the rows' order
         self.lib = _lib.load()
         if not torch.cuda.is_available() or _lib.device_count() < 1:
             raise _lib.PtmiError("no MI355X visible: the engine has no CPU fallback")
@@ -575,6 +596,8 @@ class PTEngine(object):
         self.t["X"].copy_(torch.from_numpy(full))
         if self.t.get("sloc") is not None:
             self.t["sloc"].zero_()                                    # every state is in X (a segment of the split path abandoned half way left it otherwise)
+        if self.rows_logl:
+            return self.init_state_callback(full, *self._rows_callbacks()[:2], i0=i0)
         _lib.check(self.lib.ptmi_eval_state(self.h))                 # :479-487
         self._store_initial(i0)
         self.iter = int(i0)
@@ -828,7 +851,18 @@ class PTEngine(object):
 
     # ------------------------------------------------------------------ stepping
     def mh_steps(self, iter0, nsteps):
+        if self.rows_logl:                                            # the split path with the built-in row kernels: the same chains
+            return self.callback_segment(iter0, iter0 + nsteps - 1, *self._rows_callbacks())
         _lib.check(self.lib.ptmi_mh_steps(self.h, iter0, nsteps))
+
+    def _rows_callbacks(self):
+        """(logl, logp, logl_grad, logp_grad) of ``rows_logl=True``: the built-in row kernels; None where there is nothing to launch (a
+        flat prior; no gradient jumps in the cycle)."""
+        if getattr(self, "_rows_cb", None) is None:
+            box, gj = self._par_p.size > 0, sum(self.grad_weights) > 0
+            self._rows_cb = (self.builtin_logl(), self.builtin_logp() if box else None,
+                             self.builtin_logl_grad() if gj else None, self.builtin_logp_grad() if gj and box else None)
+        return self._rows_cb
 
     def last_variant(self):
         """Flags of the fused-kernel instantiation the last ``mh_steps`` launched (``_lib.VAR_*``), lanes, slots."""
@@ -955,8 +989,8 @@ class PTEngine(object):
         _lib.check(self.lib.ptmi_accept(self.h, it, ll.data_ptr(), lp.data_ptr()))
 
     def builtin_logl(self):
-        """The built-in isotropic Gaussian as a batched CALLBACK ``f(X[n, d]) -> [n]`` (``ptmi_rows_logl``: a device kernel behind the
-        C ABI, the fused kernels' bits): with it ``run_callback`` reproduces ``run`` bit for bit."""
+        """The built-in isotropic or dense Gaussian as a batched CALLBACK ``f(X[n, d]) -> [n]`` (``ptmi_rows_logl``: a device kernel
+        behind the C ABI, the fused kernels' bits): with it ``run_callback`` reproduces ``run`` bit for bit."""
         torch = _torch()
 
         def logl(X):
@@ -965,6 +999,42 @@ class PTEngine(object):
             return out
 
         return logl
+
+    def builtin_logl_grad(self):
+        """... and with its gradient, ``f(X[n, d]) -> (lnL[n], dlnL[n, d])`` (``ptmi_rows_logl_grad``): the ``logl_grad`` of
+        ``run_callback`` / ``gradient_stage`` for HMC and NUTS in the cycle."""
+        torch = _torch()
+
+        def logl_grad(X):
+            out = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
+            g = torch.empty((X.shape[0], self.d), dtype=torch.float64, device=X.device)
+            _lib.check(self.lib.ptmi_rows_logl_grad(self.h, X.data_ptr(), X.shape[0], out.data_ptr(), g.data_ptr()))
+            return out, g
+
+        return logl_grad
+
+    def builtin_logp(self):
+        """The built-in prior (flat or box) as a batched callback ``f(X[n, d]) -> [n]`` (``ptmi_rows_logp``)."""
+        torch = _torch()
+
+        def logp(X):
+            out = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
+            _lib.check(self.lib.ptmi_rows_logp(self.h, X.data_ptr(), X.shape[0], out.data_ptr(), None))
+            return out
+
+        return logp
+
+    def builtin_logp_grad(self):
+        """... and with its gradient (zeros), ``f(X[n, d]) -> (lp[n], dlp[n, d])``."""
+        torch = _torch()
+
+        def logp_grad(X):
+            out = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
+            g = torch.empty((X.shape[0], self.d), dtype=torch.float64, device=X.device)
+            _lib.check(self.lib.ptmi_rows_logp(self.h, X.data_ptr(), X.shape[0], out.data_ptr(), g.data_ptr()))
+            return out, g
+
+        return logp_grad
 
     def dense_logl_callback(self, mu, P):
         """The dense Gaussian -(x - mu)^T P (x - mu) / 2 (the reference's own test likelihood, tests/test_simple.py:14-41) as a batched

@@ -121,7 +121,10 @@ class PTSampler(object):
     def __init__(self, ndim, logl, logp, cov, groups=None, loglargs=[], loglkwargs={}, logpargs=[], logpkwargs={},
                  logl_grad=None, logp_grad=None, comm=None, outDir="./chains", verbose=True, resume=False, seed=None,
                  nwalkers=1, ntemps=None, device=0, cov_mode="per_walker", keep_walkers=1, swap_mode="sweep",
-                 pick_mode="chain", eig_mode="lapack", checkpoint=None, batched=False, nuts_maxdepth=24, batched_nuts=False):
+                 pick_mode="chain", eig_mode="lapack", checkpoint=None, batched=False, nuts_maxdepth=24, batched_nuts=False, rows_logl=None):
+        # rows_logl: the device likelihood as a row kernel over the launch's proposals (PTEngine(rows_logl=True): the same chains, one
+        # matrix-core product per iteration for the dense family); None: by itself where the fused kernels have no table in LDS
+        self.rows_logl = self.resolve_rows_logl(ndim, logl, logp, rows_logl)
         self.comm = comm if comm is not None else _DummyComm()
         if self.comm.Get_size() != 1:
             raise NotImplementedError(
@@ -180,6 +183,20 @@ class PTSampler(object):
         self.propCycle, self.jumpDict, self.aux = [], {}, []
         self.engine = None
         self._ctx = (0, 0)
+
+    @staticmethod
+    def resolve_rows_logl(ndim, logl, logp, rows_logl=None):
+        """Does ``PTSampler(ndim, logl, logp, ..., rows_logl=rows_logl)`` run the built-in likelihood as a row kernel on the split path
+        (``PTEngine(rows_logl=True)``)?  ``None``: yes for ``("dense", mu, P)`` beyond the 104 parameters whose table the fused kernels keep
+        in LDS, with a built-in prior; ``False``: never; ``True``: at any ndim -- for the families ``ptmi_rows_logl`` serves
+        (("iso",), ("dense", mu, P)) with a built-in prior, anything else raises."""
+        ok = isinstance(logl, tuple) and isinstance(logp, tuple) and len(logl) > 0 and logl[0] in ("iso", "dense")
+        if rows_logl is None:
+            return bool(ok and logl[0] == "dense" and int(ndim) > 104)
+        if rows_logl and not ok:
+            raise ValueError("rows_logl=True runs the built-in ('iso',) or ('dense', mu, P) likelihood with a built-in prior as row kernels: "
+                             "a Python-callable likelihood is served by the callback path (batched=True for device tensors)")
+        return bool(rows_logl)
 
     # ------------------------------------------------------------------ proposal cycle API
     def addProposalToCycle(self, func, weight):
@@ -359,7 +376,7 @@ class PTSampler(object):
             weights=(self.SCAMweight, self.AMweight, self.DEweight), cov_update=covUpdate, burn=burn, tskip=Tskip,
             seed=self.seed, cov_mode=self.cov_mode, hot_chain=hotChain, device=self.device_index, split=self.split,
             swap_mode=self.swap_mode, pick_mode=self.pick_mode, eig_mode=self.eig_mode, grad_weights=self._grad_weights, hmc=(HMCstepsize, 2, HMCsteps), nuts_maxdepth=self.nuts_maxdepth,
-            split_nuts=self._batched_grads and self.batched_nuts,
+            split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     # ------------------------------------------------------------------ sample (:374-528)
