@@ -310,7 +310,7 @@ int ptmi_eig_ql(ptmi_handle h);
  * (oracle: OracleEngine(eig_lag=L)).  One call at a time per handle. */
 int ptmi_eig_ql_from(ptmi_handle h, void *stream, const double *cov_in, double *Ut_out, double *S_out);
 /* The same for ONE large pooled covariance (3 <= ndim <= 1024; the engine's eig_mode "sytrd"), all of it the library's own kernels:
- * Householder tridiagonalization in ONE kernel with the matrix in the LDS of its blocks (csrc/ptmi_abi.hip sytrd_lds_kernel), the
+ * Householder tridiagonalization in ONE kernel with the matrix in the LDS of its blocks (csrc/ptmi_eig.hip sytrd_lds_kernel), the
  * tridiagonal matrix's eigenvectors by divide and conquer (csrc/ptmi_dc.inc.h: QL on leaves of 16 rows, rank-one merges with
  * deflation, roots of the secular equation by bisection, Gu / Eisenstat weights), back-transformed through the reflectors.
  * Replaces the np.linalg.svd of :797-803 where the ROCm library's eigensolver (torch.linalg.eigh: 35 ms of small kernels at

@@ -1233,7 +1233,7 @@ ORC_API double orc_logl_grad(const orc_cfg *c, const double *x, double *g)
 
 
 /* ------------------------------------------------ batched Jacobi eigensolver */
-/* The engine's device eigensolver (eig_mode "jacobi", csrc/ptmi_abi.hip eig_jacobi_kernel), restated operation for
+/* The engine's device eigensolver (eig_mode "jacobi", csrc/ptmi_eig.hip eig_jacobi_kernel), restated operation for
  * operation: it replaces np.linalg.svd(cov) of _updateRecursive (PT:797-803) where thousands of per-walker covariances
  * have to be factorized per epoch.  One-sided (Hestenes) Jacobi on the rows of W = V^T A, A symmetric positive
  * semi-definite: rotations of row pairs (p, q) in the round-robin order of the circle method, applied to W and to the
@@ -1301,7 +1301,7 @@ ORC_API int orc_eig_jacobi(int d, const double *cov, double *Ut, double *S, int 
 }
 
 /* ---------------------------------------------- tridiagonal QL eigensolver */
-/* The engine's eig_mode "ql" (ptmi_eig_ql, csrc/ptmi_abi.hip eig_ql_kernel): the eigendecomposition of a symmetric matrix by
+/* The engine's eig_mode "ql" (ptmi_eig_ql, csrc/ptmi_eig.hip eig_ql_kernel): the eigendecomposition of a symmetric matrix by
  * Householder tridiagonalization with the transformations accumulated, then implicit QL iterations with shifts on the tridiagonal
  * matrix (the classical tred2 / tql2 pair of the EISPACK literature, restated without the row scaling: covariances are of moderate
  * size) -- a few passes of O(n) dependent scalar work per eigenvalue, where the Jacobi sweeps of eig_mode "jacobi" take nine sweeps

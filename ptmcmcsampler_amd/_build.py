@@ -29,6 +29,22 @@ def hipcc():
     return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
+def _usable_cores():
+    """Visible CPUs, capped by the affinity mask and the cgroup CPU quota."""
+    n = os.cpu_count() or 1
+    try:
+        n = min(n, len(os.sched_getaffinity(0)))
+    except AttributeError:
+        pass
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(int(quota) / int(period))))
+    except (OSError, ValueError):
+        pass
+    return n
+
+
 def shapes():
     txt = open(os.path.join(CSRC, "ptmi_common.h")).read()
     line = re.search(r"#define PTMI_SHAPE_LIST\(X\)(.*)", txt).group(1)
@@ -59,6 +75,8 @@ def build(force=False, verbose=False, jobs=None):
         return OUT
     os.makedirs(OBJ, exist_ok=True)
     work = [(os.path.join(CSRC, "ptmi_abi.hip"), os.path.join(OBJ, "abi.o"), []),
+            (os.path.join(CSRC, "ptmi_eig.hip"), os.path.join(OBJ, "eig.o"), []),             # the device eigensolvers ("jacobi", "ql", "sytrd")
+            (os.path.join(CSRC, "ptmi_swap.hip"), os.path.join(OBJ, "swap.o"), []),           # the PT swap and the block-edge exchange
             (os.path.join(CSRC, "ptmi_split.hip"), os.path.join(OBJ, "split.o"), []),         # the split path's row kernels (shape-independent)
             (os.path.join(CSRC, "ptmi_gjcb.hip"), os.path.join(OBJ, "gjcb.o"), []),           # ... and its HMC stage for gradient callbacks
             (os.path.join(CSRC, "ptmi_dense_rows.hip"), os.path.join(OBJ, "dense_rows.o"), [])]   # ... and the built-in dense Gaussian / priors over rows
@@ -72,13 +90,13 @@ def build(force=False, verbose=False, jobs=None):
             # + the max-ILP scheduling strategy for the kernels of SCAM-only cycles of the same two families (part 0 of a shape:
             # config-2 kernel 0.797 -> 0.782 ms per 100 steps, dense 5.81 -> 5.72); the kernels of cycles with AM / DE entries
             # (part 1) measured 1-2 % slower with it and keep the default strategy.  max-memory-clause, metric bias 0, relaxed
-            # occupancy and no post-RA scheduling measured within 0.5 % of the default or worse.  PTMI_NO_ILP=1: an A/B build without it.
+            # occupancy and no post-RA scheduling measured within 0.5 % of the default or worse.
             track = ["-mllvm", "-amdgpu-use-amdgpu-trackers"] if fam < 2 else []
-            ilp = [] if os.environ.get("PTMI_NO_ILP") else (["-mllvm", "-amdgpu-sched-strategy=max-ilp"] if fam < 2 else [])
+            ilp = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"] if fam < 2 else []
             defs = ["-DPTMI_G=%d" % g, "-DPTMI_E=%d" % e, "-DPTMI_L=%d" % fam]
             work.append((os.path.join(CSRC, "ptmi_shape.hip"), os.path.join(OBJ, "shape_%d_%d_%d.o" % (g, e, fam)), defs + ["-DPTMI_PART=0"] + track + ilp))
             work.append((os.path.join(CSRC, "ptmi_shape.hip"), os.path.join(OBJ, "shape_full_%d_%d_%d.o" % (g, e, fam)), defs + ["-DPTMI_PART=1"] + track))
-    jobs = jobs or min(len(work), os.cpu_count() or 1)
+    jobs = jobs or min(len(work), _usable_cores())
     if verbose:
         print("compiling %d translation units with %d workers" % (len(work), jobs))
     with concurrent.futures.ThreadPoolExecutor(jobs) as pool:

@@ -1,10 +1,9 @@
-// ptmi_abi.hip -- the C ABI of libptmi.so, the engine object and the kernels that are not per-chain templates
-// (swap sweep, Welford / pooling, DE ring, self-tests).  See include/ptmi.h for the boundary and DESIGN.md.
+// ptmi_abi.hip -- the C ABI of libptmi.so, the engine object, and the kernels of the statistics (Welford / pooling), the AM
+// producers, the DE ring, the gradient-jump launch order and the self-tests.  See include/ptmi.h for the boundary and DESIGN.md.
 #include <math.h>
 #include <stdlib.h>
 
 #include <new>
-#include <mutex>
 #include <vector>
 
 #include <type_traits>
@@ -20,418 +19,6 @@ int ptmi_fail(int code, const char *fmt, ...)
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
-}
-
-// --------------------------------------------------------------------- swap
-__global__ void gather_lnl_kernel(const double *lnL, const int32_t *slot_of, double *out, long long n, int nt)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const long long w = i / nt;
-    out[i] = lnL[w * nt + slot_of[i]];
-}
-
-// PT:666-686 in two kernels.  swap_prepare_kernel (one thread per position and walker) does everything that does
-// not depend on the carried state: the LOGARITHM of the pair's uniform (PT:679's u <= exp(sum) is tested as log u <= sum,
-// as the oracle defines it: the transcendental leaves the recurrence) and every quotient of a position's OWN likelihood,
-// L[k] / T[k], L[k] / T[k+1] and L[k] / T[k-1].  swap_sweep_kernel (one lane per walker) then runs the hot -> cold
-// recurrence with the carried map.  Scratch: one 48-byte record per (position, walker), position-major [n][W], so a pair
-// costs the sweep three 16-byte loads per lane from one wave-uniform base and a wave reads 3 KB in a row.  When the whole
-// ladder is local (slot_of != nullptr) the slot tables are rewritten in place: position k+1 becomes final at step k and
-// positions <= k are still untouched.
-struct __attribute__((aligned(16))) SwapPre {
-    double lu, L;        // log of the pair's uniform; the position's likelihood
-    double a, b;         // -L/T[k], L/T[k+1]
-    double c;            // L/T[k-1]
-    int32_t row, pad;    // the slot that holds the position (whole ladder local)
-};
-static_assert(sizeof(SwapPre) == 48, "three 16-byte loads");
-// what a record is made from
-struct SwapSrc {
-    const double *ladder, *lnL_pos, *lnL_rows;
-    const int32_t *slot_of;      // whole ladder local: the slot tables (else nullptr: lnL_pos holds the likelihoods by position)
-    long long iter;
-    u64 seed;
-    int walker0;
-    int block_nt;                // > 0: lnL_pos is [n / block_nt][W][block_nt], as all-gathered
-    const double *u_over;        // TEST HOOK (ptmi_test_replay): the pair uniforms [W][n - 1] as recorded from the reference, or nullptr
-};
-__device__ __forceinline__ SwapPre swap_record(const SwapSrc &p, int W, int n, int k, int w)
-{
-    const bool fused = p.slot_of != nullptr;
-    const int row = fused ? p.slot_of[(size_t)w * n + k] : 0;
-    const double L = fused ? p.lnL_rows[(size_t)w * n + row]
-                   : (p.block_nt > 0 ? p.lnL_pos[((size_t)(k / p.block_nt) * W + w) * p.block_nt + k % p.block_nt] : p.lnL_pos[(size_t)w * n + k]);
-    double u = 0.0, b = 0.0, c = 0.0;
-    if (k < n - 1) {
-        const u32 sid = (u32)((u64)(p.walker0 + w) * (u32)n + 0u);    // rank 0's stream (PT:679)
-        u64 w0, w1;
-        philox_words(p.seed, (u64)p.iter, sid, SLOT_SWAP + (u32)k, w0, w1);
-        u = det_log(p.u_over ? p.u_over[(size_t)w * (n - 1) + k] : w2uniform(w0));   // log of the [0,1) uniform; -inf for u = 0: always accepted
-        b = L / p.ladder[k + 1];
-    }
-    if (k > 0) c = L / p.ladder[k - 1];
-    SwapPre r;
-    r.lu = u; r.L = L; r.a = -L / p.ladder[k]; r.b = b; r.c = c; r.row = fused ? row : k; r.pad = 0;
-    return r;
-}
-__global__ void swap_prepare_kernel(int W, int n, SwapSrc src, SwapPre *pre)
-{
-    // grid (walkers, positions); the 2 M records of a 512-rank ladder are 100 MB: this kernel is bound by writing them
-    const int k = (int)blockIdx.y, w = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (w >= W) return;
-    pre[(size_t)k * W + (size_t)w] = swap_record(src, W, n, k, w);
-}
-
-// The recurrence of pair k (positions k, k+1; carried state of likelihood Lc at k+1) is the reference's four-term sum in
-// its order, -L[k]/T[k] - Lc/T[k+1] + Lc/T[k] + L[k]/T[k+1], against log u.  The two quotients of Lc are carried along with
-// it: if the pair accepts, Lc moves on and pair k-1 needs Lc/T[k] (this pair's third term) and Lc/T[k-1] -- ONE new division,
-// independent of this pair's decision, so it runs in the shadow of the sums and the compare; if it rejects, the new carried
-// state is position k's own and both quotients come from the prepared arrays (-(-L[k]/T[k]) and L[k]/T[k-1]; negation is
-// exact).  Same operations on the same values as the oracle: bit-identical decisions.  Per pair the serial path is three
-// sums, a compare and the selects (0.65 us per pair with two divisions and an exp on it, round 2).
-// parity >= 0 (odd/even mode): only the pairs with k = parity (mod 2) are tried; an untried pair never accepts, so
-// the carried state is always position k+1's own and the recurrence degenerates into independent pair tests.
-// STG: the tables the sweep writes are [walker][position] -- a lane per walker scatters 4-byte stores 4 n bytes apart, 64
-// memory transactions per store instruction.  So the block (one wave = 64 walkers) keeps its walkers' forward table and
-// acceptance flags in LDS (rows of n + 1 ints: a lane per bank) and writes them out at the end with the lanes along the
-// position, building the inverse table there.  2 x wpb x (n + 1) ints: 64 walkers per block up to 319 ranks, 32 / 16 / 8
-// for longer ladders (512 ranks of an 8-GPU ladder: 32); beyond that the direct stores (STG = false).
-#ifndef PTMI_SWEEP_BATCH
-#define PTMI_SWEEP_BATCH 8
-#endif
-// the AM-buffer row of a swap iteration (PT:624-627, 327-328): the state that sits at rank 0 after the sweep
-struct SwapAmRow { const double *X, *lnL, *lp; double *AM, *AMaux; int d, cov_update, am_epl; long long iter; AmFlag *AMflag; };
-// the post-swap rows are KEY rows (AM row flags, ptmi_common.h)
-__device__ __forceinline__ void swap_am_key(const SwapAmRow &amr, int w0, int nw, int tid, int nthreads)
-{
-    if (amr.AMflag == nullptr) return;
-    const int ring = (int)(amr.iter % amr.cov_update);
-    for (int wl = tid; wl < nw; wl += nthreads) amr.AMflag[(size_t)(w0 + wl) * amr.cov_update + (size_t)ring] = AMROW_KEY;
-}
-template <bool STG>
-__global__ __launch_bounds__(STG ? 256 : 64) void swap_sweep_kernel(int W, int n, const double *ladder, const SwapPre *pre,
-                                  int32_t *slot_of, int32_t *temp_of, int32_t *map, u64 *nswap, int local0, int nlocal,
-                                  int parity, int32_t *inv /* with map: inv[w][map[w][j]] = j */,
-                                  int wpb /* walkers per block: 64, fewer when a long ladder's tables would not fit the LDS */,
-                                  int hop_nt, int32_t *hop_flag /* hop_nt > 0 (STG, map form): set *hop_flag when a state moves beyond a
-                                                                 * neighbouring block of hop_nt ranks (ptmi_exchange_multihop) */,
-                                  SwapAmRow amr /* STG, fused: the write-out also stores the swap iteration's AM row (am_write_kernel) */)
-{
-    // STG blocks have four waves: the first runs the recurrence (a lane per walker), all four write the tables out
-    extern __shared__ int32_t sw_lds[];
-    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-    const int w = (int)blockIdx.x * wpb + lane;
-    const bool fused = slot_of != nullptr;
-    const int ld = n + 1;
-    int32_t *const l0 = sw_lds + (size_t)lane * ld;                    // slot_of / map of this lane's walker
-    int32_t *const lf = sw_lds + (size_t)(wpb + lane) * ld;            // pair k accepted
-    if (wave == 0 && lane < wpb && w < W) {
-    int32_t *fw = STG ? l0 : (fused ? slot_of + (size_t)w * n : map + (size_t)w * n);     // forward table: row (fused) or source position
-    int32_t *bw = STG ? nullptr : (fused ? temp_of + (size_t)w * n : inv + (size_t)w * n); // its inverse (STG: built at write-out)
-    const SwapPre top = pre[(size_t)(n - 1) * W + w];
-    int crow = top.row;                    // what the forward table says about the state carried at k+1 (its slot, or its position)
-    double Lc = top.L;
-    double q1 = -top.a;                    // Lc / T[k+1]
-    double q0 = top.c;                     // Lc / T[k]
-    // Only (Lc, q1, q0) are carried from pair to pair.  The scratch of SW pairs is fetched at once into one of two register
-    // sets (this kernel runs one wave per SIMD: registers are free), the NEXT batch being requested before the current one
-    // is worked through, so that one memory latency is exposed per launch instead of one per batch (round 2's version
-    // requested T[k] through the scalar unit, one waited-for load per pair: 0.5 us per pair whatever the arithmetic).
-    // Indices below 0 are clamped, not branched around: their values are never used.
-    constexpr int SW = PTMI_SWEEP_BATCH;
-    struct Batch { double u[SW], L[SW], a[SW], b[SW], c[SW], T[SW]; int r[SW]; };
-    // addresses: the lane's record of position 0 (computed once) + a wave-uniform stride per position
-    const char *const lane0 = reinterpret_cast<const char *>(pre + ((size_t)blockIdx.x * wpb + (unsigned)lane));
-    const size_t kstride = (size_t)W * sizeof(SwapPre);
-    auto fetch = [&](int k0, Batch &B) {
-#pragma unroll
-        for (int j = 0; j < SW; ++j) {
-            const int kk = k0 - j > 0 ? k0 - j : 0;
-            const SwapPre r = *reinterpret_cast<const SwapPre *>(lane0 + (size_t)kk * kstride);
-            B.u[j] = r.lu; B.L[j] = r.L; B.a[j] = r.a; B.b[j] = r.b; B.c[j] = r.c; B.r[j] = r.row;
-            B.T[j] = ladder[kk > 0 ? kk - 1 : 0];                       // T[k-1] (uniform: a scalar load)
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto chain = [&](int k0, const Batch &B) {
-#pragma unroll
-        for (int j = 0; j < SW; ++j) {
-            const int k = k0 - j;
-            if (k < 0) break;
-            const double spec = Lc / B.T[j];   // Lc / T[k-1]: needed if this pair accepts; does not wait for its decision
-            double la = B.a[j];                // -L[k] / T[k]
-            la += -q1;                         // -Lc / T[k+1]
-            la += q0;                          //  Lc / T[k]
-            la += B.b[j];                      //  L[k] / T[k+1]
-            const bool acc = (parity < 0 || (k & 1) == parity) && B.u[j] <= la;      // log u <= sum
-            // position k+1 is final: it keeps the carried state, or takes position k's
-            const int fin = acc ? B.r[j] : crow;
-            fw[k + 1] = fin;
-            if (!STG) bw[fin] = k + 1;
-            if (STG) lf[k] = acc ? 1 : 0;
-            else if (acc && k >= local0 && k < local0 + nlocal) atomicAdd((unsigned long long *)&nswap[(size_t)w * n + k], 1ull);   // no-return atomic
-            q1 = acc ? q0 : -B.a[j];
-            q0 = acc ? spec : B.c[j];
-            Lc = acc ? Lc : B.L[j];
-            crow = acc ? crow : B.r[j];
-        }
-    };
-    Batch A, B;
-    fetch(n - 2, A);
-    for (int k0 = n - 2; k0 >= 0; k0 -= 2 * SW) {
-        if (k0 - SW >= 0) fetch(k0 - SW, B);
-        chain(k0, A);
-        if (k0 - SW < 0) break;
-        if (k0 - 2 * SW >= 0) fetch(k0 - 2 * SW, A);
-        chain(k0 - SW, B);
-    }
-    fw[0] = crow;
-    if (!STG) bw[crow] = 0;
-    }
-    // block of a position (the multi-hop scan of the write-out): filled by the waves that sit out the recurrence
-    int32_t *const blk = sw_lds + (size_t)2 * wpb * ld;
-    if (STG && hop_nt > 0 && wave > 0)
-        for (int k = (int)threadIdx.x - 64; k < n; k += 192) blk[k] = k / hop_nt;
-    if (STG) {
-        __syncthreads();
-        const int w0 = (int)blockIdx.x * wpb;
-        int32_t *g0 = fused ? slot_of : map, *g1 = fused ? temp_of : inv;
-        const int nw = W - w0 < wpb ? W - w0 : wpb;
-        bool far = false;
-        for (int wl = wave; wl < nw; wl += 4) {                        // a wave per walker, the lanes along the position
-            const size_t row = (size_t)(w0 + wl) * n;
-            for (int k = lane; k < n; k += 64) {
-                const int f = sw_lds[(size_t)wl * ld + k];
-                g0[row + k] = f;
-                g1[row + f] = k;                                       // the inverse table: a scatter inside the walker's own row
-                if (hop_nt > 0) { const int hop = blk[f] - blk[k]; far = far || hop > 1 || hop < -1; }
-                // a no-return atomic: fire and forget (a read-modify-write would wait for its load in every trip: 37 against 24 us)
-                if (k < n - 1 && k >= local0 && k < local0 + nlocal && sw_lds[(size_t)(wpb + wl) * ld + k])
-                    atomicAdd((unsigned long long *)&nswap[row + k], 1ull);
-            }
-        }
-        if (hop_nt > 0 && __ballot(far) != 0 && lane == 0) atomicOr(hop_flag, 1);   // once per wave at most
-        if (amr.AM != nullptr) {
-            // the rows now at rank 0 into the AM ring (am_write_kernel's copy): the block's nw rows as one list of elements, six
-            // reads in flight per thread (a wave per walker waited for sixteen round trips in turn)
-            constexpr int NB = 6;
-            const int tot = nw * amr.d, ring = (int)(amr.iter % amr.cov_update);
-            for (int base = (int)threadIdx.x; base < tot; base += 256 * NB) {
-                double v[NB];
-                size_t dst[NB];
-#pragma unroll
-                for (int u = 0; u < NB; ++u) {
-                    const int idx = base + 256 * u, ic = idx < tot ? idx : tot - 1;
-                    const int wl = ic / amr.d, i = ic % amr.d;
-                    const size_t r = (size_t)(w0 + wl) * n + (size_t)sw_lds[(size_t)wl * ld];
-                    v[u] = amr.X[r * amr.d + i];
-                    dst[u] = ((size_t)(w0 + wl) * amr.cov_update + (size_t)ring) * amr.d + (size_t)am_pos(i, amr.am_epl);
-                }
-#pragma unroll
-                for (int u = 0; u < NB; ++u)
-                    if (base + 256 * u < tot) amr.AM[dst[u]] = v[u];
-            }
-            if (amr.AMaux)
-                for (int wl = (int)threadIdx.x; wl < nw; wl += 256) {
-                    const size_t r = (size_t)(w0 + wl) * n + (size_t)sw_lds[(size_t)wl * ld];
-                    const size_t arow = (size_t)(w0 + wl) * amr.cov_update + (size_t)ring;
-                    amr.AMaux[arow * 2] = amr.lnL[r];
-                    amr.AMaux[arow * 2 + 1] = amr.lp[r];
-                }
-            swap_am_key(amr, w0, nw, (int)threadIdx.x, 256);
-        }
-    }
-}
-
-// The sweep with its records made in the block (no scratch in memory: the 48-byte records of a 512-rank ladder are 100 MB
-// written and read back, 34 us of the 160 us a swap epoch takes on one of eight GPUs; with 64 ranks the prepare kernel and its
-// launch gap are a third of the epoch).  Blocks of 512 threads: wave 0 runs the recurrence as in swap_sweep_kernel<true>, six
-// of the others (not wave 4, which sits on the recurrence's SIMD) make the records of the batch after next (eight pairs) into a
-// three-slot LDS ring while it works through the current one and reads the next into its second register set; one barrier
-// per batch.  Same records, same recurrence, same write-out: bit-identical.
-constexpr int SWF_BLK = 512;
-__host__ __device__ inline size_t swf_ring_offset(int wpb, int n) { return ((sizeof(int32_t) * (2 * (size_t)wpb * (size_t)(n + 1) + (size_t)n)) + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t swf_lds_bytes(int wpb, int n) { return swf_ring_offset(wpb, n) + sizeof(SwapPre) * (size_t)(3 * PTMI_SWEEP_BATCH + 1) * (size_t)wpb; }
-__global__ __launch_bounds__(SWF_BLK) void swap_fused_kernel(int W, int n, SwapSrc src, int32_t *slot_of, int32_t *temp_of, int32_t *map,
-                                                          u64 *nswap, int local0, int nlocal, int parity, int32_t *inv, int wpb, int wpb_log2,
-                                                          int hop_nt, int32_t *hop_flag, SwapAmRow amr)
-{
-    extern __shared__ int32_t sw_lds[];
-    constexpr int SW = PTMI_SWEEP_BATCH;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int w0 = (int)blockIdx.x * wpb, w = w0 + lane;
-    const bool fused = slot_of != nullptr;
-    const int ld = n + 1;
-    int32_t *const fw = sw_lds + (size_t)lane * ld;                    // slot_of / map of this lane's walker
-    int32_t *const lf = sw_lds + (size_t)(wpb + lane) * ld;            // pair k accepted
-    int32_t *const blk = sw_lds + (size_t)2 * wpb * ld;
-    SwapPre *const ring = reinterpret_cast<SwapPre *>(reinterpret_cast<char *>(sw_lds) + swf_ring_offset(wpb, n));   // [3][SW][wpb]
-    SwapPre *const topr = ring + (size_t)3 * SW * wpb;                 // [wpb]: the records of position n - 1
-    const int NB = (n - 1 + SW - 1) / SW;                              // batches of the pairs n - 2 .. 0
-    auto produce = [&](int b, int t0, int nthr) {                      // batch b by the threads t0 .. t0 + nthr - 1
-        const int k0 = n - 2 - b * SW;
-        for (int idx = tid - t0; idx < SW * wpb; idx += nthr) {
-            const int j = idx >> wpb_log2, wl = idx & (wpb - 1), k = k0 - j;
-            if (k >= 0 && w0 + wl < W) ring[((size_t)(b % 3) * SW + j) * wpb + wl] = swap_record(src, W, n, k, w0 + wl);
-        }
-    };
-    for (int wl = tid; wl < wpb; wl += SWF_BLK)
-        if (w0 + wl < W) topr[wl] = swap_record(src, W, n, n - 1, w0 + wl);
-    if (NB > 0) produce(0, 0, SWF_BLK);
-    if (NB > 1) produce(1, 0, SWF_BLK);
-    if (hop_nt > 0)
-        for (int k = tid; k < n; k += SWF_BLK) blk[k] = k / hop_nt;
-    __syncthreads();
-    const bool chainer = wave == 0 && lane < wpb && w < W;
-    if (wave == 0) __builtin_amdgcn_s_setprio(3);                      // the recurrence is the critical path of the block
-    int crow = 0;                          // what the forward table says about the state carried at k+1 (its slot, or its position)
-    double Lc = 0.0, q1 = 0.0, q0 = 0.0;   // its likelihood, Lc / T[k+1], Lc / T[k]
-    if (chainer) {
-        const SwapPre top = topr[lane];
-        crow = top.row; Lc = top.L; q1 = -top.a; q0 = top.c;
-    }
-    // The ring holds three batches: while the recurrence works through batch b out of one register set it reads batch b + 1
-    // (made during batch b - 1) into the other, and the makers fill the slot of batch b + 2 (last read during batch b - 2).
-    struct Batch { SwapPre R[SW]; double T[SW]; };
-    auto fetch = [&](int b, Batch &B) {
-        const int k0 = n - 2 - b * SW;
-        const SwapPre *rb = ring + (size_t)(b % 3) * SW * wpb + lane;
-#pragma unroll
-        for (int j = 0; j < SW; ++j) {
-            const int kk = k0 - j > 0 ? k0 - j : 0;
-            B.R[j] = rb[(size_t)(k0 - j >= 0 ? j : 0) * wpb];
-            B.T[j] = src.ladder[kk > 0 ? kk - 1 : 0];                  // T[k-1] (uniform: a scalar load)
-        }
-    };
-    auto chain = [&](int b, const Batch &B) {
-        const int k0 = n - 2 - b * SW;
-#pragma unroll
-        for (int j = 0; j < SW; ++j) {
-            const int k = k0 - j;
-            if (k < 0) break;
-            const double spec = Lc / B.T[j];     // Lc / T[k-1]: needed if this pair accepts; does not wait for its decision
-            double la = B.R[j].a;                // -L[k] / T[k]
-            la += -q1;                           // -Lc / T[k+1]
-            la += q0;                            //  Lc / T[k]
-            la += B.R[j].b;                      //  L[k] / T[k+1]
-            const bool acc = (parity < 0 || (k & 1) == parity) && B.R[j].lu <= la;     // log u <= sum
-            fw[k + 1] = acc ? B.R[j].row : crow; // position k+1 is final: it keeps the carried state, or takes position k's
-            lf[k] = acc ? 1 : 0;
-            q1 = acc ? q0 : -B.R[j].a;
-            q0 = acc ? spec : B.R[j].c;
-            Lc = acc ? Lc : B.R[j].L;
-            crow = acc ? crow : B.R[j].row;
-        }
-    };
-    auto turn = [&](int b, Batch &cur, Batch &nxt) {                   // one batch: every wave passes here, one barrier
-        if (wave == 0) {
-            if (chainer) {
-                if (b + 1 < NB) fetch(b + 1, nxt);
-                chain(b, cur);
-            }
-        } else if (wave != 4 && b + 2 < NB) {                          // wave 4 shares the recurrence's SIMD: it sits the batches out
-            produce(b + 2, wave < 4 ? 64 : 128, SWF_BLK - 128);
-        }
-        __syncthreads();
-    };
-    Batch A, B;
-    if (chainer && NB > 0) fetch(0, A);
-    for (int b = 0; b < NB; b += 2) {
-        turn(b, A, B);
-        if (b + 1 < NB) turn(b + 1, B, A);
-    }
-    if (chainer) fw[0] = crow;
-    __syncthreads();
-    // write-out: a wave per walker, the lanes along the position (as swap_sweep_kernel<true>)
-    int32_t *g0 = fused ? slot_of : map, *g1 = fused ? temp_of : inv;
-    const int nw = W - w0 < wpb ? W - w0 : wpb;
-    bool far = false;
-    for (int wl = wave; wl < nw; wl += SWF_BLK / 64) {
-        const size_t row = (size_t)(w0 + wl) * n;
-        for (int k = lane; k < n; k += 64) {
-            const int f = sw_lds[(size_t)wl * ld + k];
-            g0[row + k] = f;
-            g1[row + f] = k;                                           // the inverse table: a scatter inside the walker's own row
-            if (hop_nt > 0) { const int hop = blk[f] - blk[k]; far = far || hop > 1 || hop < -1; }
-            if (k < n - 1 && k >= local0 && k < local0 + nlocal && sw_lds[(size_t)(wpb + wl) * ld + k])
-                atomicAdd((unsigned long long *)&nswap[row + k], 1ull);
-        }
-    }
-    if (hop_nt > 0 && __ballot(far) != 0 && lane == 0) atomicOr(hop_flag, 1);   // once per wave at most
-    if (amr.AM != nullptr) {                                           // the rows now at rank 0 into the AM ring (as swap_sweep_kernel<true>)
-        constexpr int NB6 = 6;
-        const int tot = nw * amr.d, ringrow = (int)(amr.iter % amr.cov_update);
-        for (int base = tid; base < tot; base += SWF_BLK * NB6) {
-            double v[NB6];
-            size_t dst[NB6];
-#pragma unroll
-            for (int u = 0; u < NB6; ++u) {
-                const int idx = base + SWF_BLK * u, ic = idx < tot ? idx : tot - 1;
-                const int wl = ic / amr.d, i = ic % amr.d;
-                const size_t r = (size_t)(w0 + wl) * n + (size_t)sw_lds[(size_t)wl * ld];
-                v[u] = amr.X[r * amr.d + i];
-                dst[u] = ((size_t)(w0 + wl) * amr.cov_update + (size_t)ringrow) * amr.d + (size_t)am_pos(i, amr.am_epl);
-            }
-#pragma unroll
-            for (int u = 0; u < NB6; ++u)
-                if (base + SWF_BLK * u < tot) amr.AM[dst[u]] = v[u];
-        }
-        if (amr.AMaux)
-            for (int wl = tid; wl < nw; wl += SWF_BLK) {
-                const size_t r = (size_t)(w0 + wl) * n + (size_t)sw_lds[(size_t)wl * ld];
-                const size_t arow = (size_t)(w0 + wl) * amr.cov_update + (size_t)ringrow;
-                amr.AMaux[arow * 2] = amr.lnL[r];
-                amr.AMaux[arow * 2 + 1] = amr.lp[r];
-            }
-        swap_am_key(amr, w0, nw, tid, SWF_BLK);
-    }
-}
-
-// Odd/even mode with the whole ladder local: one thread per (walker, tried pair), the slot tables rewritten in place
-// (the pairs are disjoint).  The pair test is the sweep's, term by term.
-__global__ void swap_oddeven_kernel(int W, int n, const double *ladder, const double *lnL_rows, int32_t *slot_of,
-                                    int32_t *temp_of, u64 *nswap, long long iter, u64 seed, int walker0, int parity)
-{
-    const int npairs = (n - parity) / 2;                    // k = parity, parity + 2, ... <= n - 2
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)npairs * W) return;
-    const int w = (int)(idx / npairs), k = parity + 2 * (int)(idx % npairs);
-    int32_t *so = slot_of + (size_t)w * n, *to = temp_of + (size_t)w * n;
-    const int rk = so[k], rk1 = so[k + 1];
-    const double Lk = lnL_rows[(size_t)w * n + rk], Lk1 = lnL_rows[(size_t)w * n + rk1];
-    const u32 sid = (u32)((u64)(walker0 + w) * (u32)n + 0u);
-    u64 w0, w1;
-    philox_words(seed, (u64)iter, sid, SLOT_SWAP + (u32)k, w0, w1);
-    const double Tk = ladder[k], Tk1 = ladder[k + 1];
-    double la = -Lk / Tk;
-    la += -Lk1 / Tk1;
-    la += Lk1 / Tk;
-    la += Lk / Tk1;
-    if (det_log(w2uniform(w0)) <= la) {
-        so[k] = rk1;
-        so[k + 1] = rk;
-        to[rk1] = k;
-        to[rk] = k + 1;
-        nswap[(size_t)w * n + k] += 1;
-    }
-}
-
-// AM-buffer row of a swap iteration: the state that now sits at rank 0 (PT:624-627, 327-328)
-__global__ void am_write_kernel(const double *X, const double *lnL, const double *lp, const int32_t *slot_of, double *AM,
-                                double *AMaux, int W, int nt, int d, int cov_update, long long iter, int am_epl, AmFlag *AMflag)
-{
-    const int w = (int)blockIdx.x;
-    const size_t r = (size_t)w * nt + slot_of[(size_t)w * nt];
-    const double *row = X + r * d;
-    double *am = AM + ((size_t)w * cov_update + (size_t)(iter % cov_update)) * d;
-    for (int i = (int)threadIdx.x; i < d; i += (int)blockDim.x) am[am_pos(i, am_epl)] = row[i];
-    if (AMaux && threadIdx.x == 0) {
-        double *ax = AMaux + ((size_t)w * cov_update + (size_t)(iter % cov_update)) * 2;
-        ax[0] = lnL[r];
-        ax[1] = lp[r];
-    }
-    if (AMflag && threadIdx.x == 0) AMflag[(size_t)w * cov_update + (size_t)(iter % cov_update)] = AMROW_KEY;
 }
 
 // ------------------------------------------------------------------ Welford
@@ -1383,785 +970,6 @@ __global__ void de_update_kernel(double *DE, const double *AM, int d, int de_siz
 }
 
 
-// ---------------------------------------------------------- eigensolver
-// Batched symmetric eigensolver for the per-walker covariances (PT:797-803 calls LAPACK's SVD once per epoch; a batch of
-// thousands of walkers would queue thousands of host factorizations).  One block per matrix, one-sided (Hestenes) Jacobi
-// on the rows of W = V^T A with W and V^T both in LDS: in every round of the circle-method schedule the n/2 disjoint row
-// pairs are rotated at once, eight lanes per pair (lane l owns elements l, l+8, ... of both rows, cached in registers
-// for the three dot products and the rotation); one barrier per round.  Operation order = oracle/ptmcmc_oracle.c orc_eig_jacobi,
-// so the results are bit-identical to it.  Eigenvalues descending, eigenvectors as rows, largest component positive.
-constexpr int JAC_THREADS = 512;                            // 8 lanes per row pair, up to 64 pairs (ndim <= 101 uses 51)
-constexpr int JAC_L = 8;
-constexpr int JAC_MAX_SWEEPS = 30;
-// sum over the eight lanes of a pair: xor 4, xor 2, xor 1 (the oracle's ((s0+s4)+(s2+s6)) + ((s1+s5)+(s3+s7)))
-__device__ __forceinline__ double jac_oct_sum(double p)
-{
-    p = p + __shfl_xor(p, 4, 64);
-    p = p + dppf64<0x4E>(p);     // xor 2
-    p = p + dppf64<0xB1>(p);     // xor 1
-    return p;
-}
-__global__ __launch_bounds__(JAC_THREADS) void eig_jacobi_kernel(const double *cov, double *Ut, double *S, int d, int ut_stride, int s_stride)
-{
-    extern __shared__ __attribute__((aligned(16))) double jsm[];     // W[d][d], V[d][d]: all of the CU's LDS at d = 101
-    double *W = jsm, *V = jsm + (size_t)d * d;
-    constexpr int NE = 13;                                           // elements of a row per lane: l, l + 8, ... < 104
-    const int tid = (int)threadIdx.x;
-    const double *A = cov + (size_t)blockIdx.x * d * d;
-    for (int i = tid; i < d * d; i += JAC_THREADS) {
-        W[i] = A[i];
-        V[i] = (i / d == i % d) ? 1.0 : 0.0;
-    }
-    const int n = d + (d & 1), P = n / 2, rounds = n - 1;
-    const int pr = tid / JAC_L, l = tid % JAC_L;
-    __syncthreads();
-    for (int sweep = 0; sweep < JAC_MAX_SWEEPS; ++sweep) {
-        int rotated = 0;
-        for (int r = 0; r < rounds; ++r) {
-            if (pr < P) {                                            // P <= 51 pairs: eight lanes each
-                const int k = pr;
-                const int a = k == 0 ? n - 1 : (r + k) % (n - 1);
-                const int b = k == 0 ? r : (r - k + (n - 1)) % (n - 1);
-                const int p = a < b ? a : b, q = a < b ? b : a;
-                const bool real = q < d;                             // the bye of an odd dimension
-                double *wp = W + (size_t)p * d, *wq = W + (size_t)(real ? q : p) * d;
-                // both rows into registers once (zeros beyond the row: fma(0, 0, s) = s leaves the sums untouched)
-                double xp[NE], xq[NE];
-#pragma unroll
-                for (int j = 0; j < NE; ++j) {
-                    const int i = l + JAC_L * j;
-                    xp[j] = i < d ? wp[i] : 0.0;
-                    xq[j] = i < d ? wq[i] : 0.0;
-                }
-                double al = 0.0, be = 0.0, ga = 0.0;
-#pragma unroll
-                for (int j = 0; j < NE; ++j) {
-                    al = __builtin_fma(xp[j], xp[j], al);
-                    be = __builtin_fma(xq[j], xq[j], be);
-                    ga = __builtin_fma(xp[j], xq[j], ga);
-                }
-                al = jac_oct_sum(al); be = jac_oct_sum(be); ga = jac_oct_sum(ga);
-                if (real && __builtin_fabs(ga) > 0x1.0p-50 * det_sqrt(al * be)) {      // uniform over the pair's lanes
-                    const double zeta = (be - al) / (2.0 * ga);
-                    const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (__builtin_fabs(zeta) + det_sqrt(1.0 + zeta * zeta));
-                    const double c = 1.0 / det_sqrt(1.0 + t * t), sn = c * t;
-                    double *vp = V + (size_t)p * d, *vq = V + (size_t)q * d;
-#pragma unroll
-                    for (int j = 0; j < NE; ++j) {
-                        const int i = l + JAC_L * j;
-                        if (i < d) {
-                            const double u = vp[i], v = vq[i];
-                            wp[i] = c * xp[j] - sn * xq[j];
-                            wq[i] = sn * xp[j] + c * xq[j];
-                            vp[i] = c * u - sn * v;
-                            vq[i] = sn * u + c * v;
-                        }
-                    }
-                    rotated = 1;
-                }
-            }
-            __syncthreads();
-        }
-        if (!__syncthreads_or(rotated)) break;
-    }
-    // norms (eight lanes per row, same summation as above): first in registers, then -- W is dead -- in W[0..d)
-    double mynorm[2] = {0.0, 0.0};
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        const int k = pass * (JAC_THREADS / JAC_L) + pr;
-        double al = 0.0;
-        if (k < d)
-            for (int j = 0; j < NE; ++j) { const int i = l + JAC_L * j; const double x = i < d ? W[(size_t)k * d + i] : 0.0; al = __builtin_fma(x, x, al); }
-        mynorm[pass] = det_sqrt(jac_oct_sum(al));
-    }
-    __syncthreads();                                                 // every row of W has been read: W[0..d) now holds the norms
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        const int k = pass * (JAC_THREADS / JAC_L) + pr;
-        if (k < d && l == 0) W[k] = mynorm[pass];
-    }
-    __syncthreads();
-    const double *nrm = W;
-    double *Uo = Ut + (size_t)blockIdx.x * ut_stride, *So = S + (size_t)blockIdx.x * s_stride;
-    for (int k = pr; k < d; k += JAC_THREADS / JAC_L) {
-        const double mine = nrm[k];
-        int rank = 0;
-        for (int j = 0; j < d; ++j) rank += (nrm[j] > mine) || (nrm[j] == mine && j < k);
-        const double *vk = V + (size_t)k * d;
-        int im = 0;
-        for (int i = 1; i < d; ++i) if (__builtin_fabs(vk[i]) > __builtin_fabs(vk[im])) im = i;
-        const double sg = vk[im] < 0.0 ? -1.0 : 1.0;
-        for (int i = l; i < d; i += JAC_L) Uo[(size_t)rank * d + i] = sg * vk[i];
-        if (l == 0) So[rank] = mine;
-    }
-}
-
-// sqrt(x) and 1 / sqrt(x)'s partner 1 / r of a rotation, for x in the middle of the exponent range: the compiler's own correctly
-// rounded sequences (v_rsq_f64 / v_rcp_f64 + the fma refinements of its sqrt and division lowerings) without their range scaling,
-// special-value tests and fix-ups -- 17 instead of 29 instructions on the chain that bounds eig_ql_chain_kernel, the same bits
-// wherever no scaling would have been applied; anything else takes the plain operations.
-__device__ __forceinline__ void ql_root_and_reciprocal(double x, double &r, double &ri)
-{
-    if (x > 0x1p-600 && x < 0x1p600) {                              // uniform in the chain kernel
-        const double y = __builtin_amdgcn_rsq(x);
-        double g = x * y, hh = 0.5 * y;
-        const double r0 = __builtin_fma(-hh, g, 0.5);
-        g = __builtin_fma(g, r0, g);
-        hh = __builtin_fma(hh, r0, hh);
-        double dd = __builtin_fma(-g, g, x);
-        g = __builtin_fma(dd, hh, g);
-        dd = __builtin_fma(-g, g, x);
-        r = __builtin_fma(dd, hh, g);
-        double q = __builtin_amdgcn_rcp(r);
-        double e = __builtin_fma(-r, q, 1.0);
-        q = __builtin_fma(q, e, q);
-        e = __builtin_fma(-r, q, 1.0);
-        q = __builtin_fma(q, e, q);
-        e = __builtin_fma(-r, q, 1.0);
-        ri = __builtin_fma(e, q, q);
-    } else {
-        r = det_sqrt(x);
-        ri = 1.0 / r;
-    }
-}
-// ----------------------------------------------------------- tridiagonal QL eigensolver (eig_mode "ql")
-// The eigendecomposition of PT:797-803 by Householder tridiagonalization with the transformations accumulated, then implicit QL
-// iterations on the tridiagonal matrix (oracle: orc_eig_ql -- the kernel does the oracle's operations in the oracle's order, dot products
-// as eight interleaved fma chains, so both give the same bits).  eig_jacobi_kernel needs nine sweeps of n^2 / 2
-// rotations, each moving two rows of W and two of V through LDS (4.4 ms per 100 x 100 matrix, one matrix per CU), on the nearly
-// degenerate spectra an isotropic target adapts to; here the O(n^3) work is two passes over the matrix and the rest is a chain of
-// some 7500 plane rotations whose scalars depend on each other (one sqrt and one division each) while the columns they turn do not.
-// One block of two waves per matrix, two blocks per CU at ndim = 100 (the matrix, the subdiagonal and one work row: 81.6 KB):
-//  * reduction, row i = n-1 .. 1: every thread forms the row's scalars itself (broadcast reads: no barrier for them); thread j owns
-//    row j of the products p = A u / h and of the rank-two update;
-//  * accumulation, row i = 0 .. n-1: thread j owns column j of the leading block (its product and its update need nothing else);
-//  * QL: ONE wave (64 lanes, rows k and k + 64 of the eigenvector matrix each) runs the scalar recurrence in every lane and turns
-//    its rows; nothing is synchronised inside this phase.
-constexpr int QL_THREADS = 128;
-constexpr int QL_MAXIT = 60;
-// the oracle's QL_DOT8: eight interleaved fma chains, term k into chain k mod 8 (a dependent f64 operation costs a lone wave some 20
-// cycles: one chain of 100 terms is 2000 cycles, eight side by side 300)
-template <class FA, class FB>
-__device__ __forceinline__ double ql_dot8(int cnt, FA fa, FB fb)
-{
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
-    int k = 0;
-    for (; k + 8 <= cnt; k += 8) {
-        s0 = __builtin_fma(fa(k), fb(k), s0);
-        s1 = __builtin_fma(fa(k + 1), fb(k + 1), s1);
-        s2 = __builtin_fma(fa(k + 2), fb(k + 2), s2);
-        s3 = __builtin_fma(fa(k + 3), fb(k + 3), s3);
-        s4 = __builtin_fma(fa(k + 4), fb(k + 4), s4);
-        s5 = __builtin_fma(fa(k + 5), fb(k + 5), s5);
-        s6 = __builtin_fma(fa(k + 6), fb(k + 6), s6);
-        s7 = __builtin_fma(fa(k + 7), fb(k + 7), s7);
-    }
-    if (k < cnt) s0 = __builtin_fma(fa(k), fb(k), s0);
-    if (k + 1 < cnt) s1 = __builtin_fma(fa(k + 1), fb(k + 1), s1);
-    if (k + 2 < cnt) s2 = __builtin_fma(fa(k + 2), fb(k + 2), s2);
-    if (k + 3 < cnt) s3 = __builtin_fma(fa(k + 3), fb(k + 3), s3);
-    if (k + 4 < cnt) s4 = __builtin_fma(fa(k + 4), fb(k + 4), s4);
-    if (k + 5 < cnt) s5 = __builtin_fma(fa(k + 5), fb(k + 5), s5);
-    if (k + 6 < cnt) s6 = __builtin_fma(fa(k + 6), fb(k + 6), s6);
-    return ((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7));
-}
-// (Measured and dropped: the matrix in a global scratch with 3 n doubles of LDS per block, sixteen blocks per CU and all 4096 matrices
-// resident at once -- every broadcast read became an L2 round trip: 84 ms per epoch against 41.)
-__global__ __launch_bounds__(QL_THREADS) void eig_ql_kernel(const double *cov, double *Ut, double *S, int n, int ut_stride, int s_stride, int32_t *status)
-{
-    extern __shared__ __attribute__((aligned(16))) double qsm[];
-    double *z = qsm, *e = qsm + (((size_t)n * n + 1) & ~(size_t)1), *pq = e + n;     // pq: the products p / h, then q; after the accumulation: the diagonal d
-    const int t = (int)threadIdx.x;
-    const double *A = cov + (size_t)blockIdx.x * n * n;
-#define QZ(i, j) z[(i) * n + (j)]
-    for (int i = t; i < n * n; i += QL_THREADS) z[i] = A[i];
-#ifdef PTMI_QL_PROFILE
-    unsigned long long qt0 = __builtin_readcyclecounter(), qt1, qt2, qt3;
-#endif
-    unsigned long long hmask[2] = {0ull, 0ull};                   // rows whose reflector exists (the oracle's d[i] != 0), n <= 128
-    __syncthreads();
-    for (int i = n - 1; i >= 1; --i) {
-        const int l = i - 1;
-        double h = 0.0;
-        if (l > 0) h = ql_dot8(l + 1, [&](int k) { return QZ(i, k); }, [&](int k) { return QZ(i, k); });
-        if (l == 0 || h == 0.0) {                                 // uniform
-            if (t == 0) e[i] = QZ(i, l);
-            __syncthreads();
-            continue;
-        }
-        const double f0 = QZ(i, l);
-        const double g0 = f0 >= 0.0 ? -det_sqrt(h) : det_sqrt(h);
-        h = h - f0 * g0;
-        __syncthreads();                                          // every thread has read Z(i, l)
-        if (t == 0) { e[i] = g0; QZ(i, l) = f0 - g0; }
-        __syncthreads();
-        for (int j = t; j <= l; j += QL_THREADS) {
-            QZ(j, i) = QZ(i, j) / h;
-            const double g = ql_dot8(l + 1, [&](int k) { return k <= j ? QZ(j, k) : QZ(k, j); }, [&](int k) { return QZ(i, k); });
-            pq[j] = g / h;
-        }
-        __syncthreads();
-        const double f = ql_dot8(l + 1, [&](int k) { return pq[k]; }, [&](int k) { return QZ(i, k); });
-        const double hh = f / (h + h);
-        __syncthreads();                                          // every thread has its f
-        for (int j = t; j <= l; j += QL_THREADS) pq[j] = pq[j] - hh * QZ(i, j);
-        __syncthreads();
-        for (int j = t; j <= l; j += QL_THREADS) {
-            const double uj = QZ(i, j), qj = pq[j];
-            for (int k = 0; k <= j; ++k) QZ(j, k) = QZ(j, k) - (uj * pq[k] + qj * QZ(i, k));
-        }
-        hmask[i >> 6] |= 1ull << (i & 63);
-        __syncthreads();
-    }
-    if (t == 0) e[0] = 0.0;
-#ifdef PTMI_QL_PROFILE
-    qt1 = __builtin_readcyclecounter();
-#endif
-    // accumulation of the transformations
-    for (int i = 0; i < n; ++i) {
-        const int l = i - 1;
-        if ((hmask[i >> 6] >> (i & 63)) & 1ull) {
-            for (int j = t; j <= l; j += QL_THREADS) {
-                const double g = ql_dot8(l + 1, [&](int k) { return QZ(i, k); }, [&](int k) { return QZ(k, j); });
-                for (int k = 0; k <= l; ++k) QZ(k, j) = QZ(k, j) - g * QZ(k, i);
-            }
-        }
-        __syncthreads();
-        if (t == 0) { pq[i] = QZ(i, i); QZ(i, i) = 1.0; }
-        for (int j = t; j <= l; j += QL_THREADS) { QZ(j, i) = 0.0; QZ(i, j) = 0.0; }
-        __syncthreads();
-    }
-    // ---- implicit QL: one wave, no barrier; lane `t` turns rows t and t + 64.  The diagonal and the subdiagonal are re-laid as
-    // pairs {d[i], e[i]} over the 2 n doubles of e and pq (one 16-byte read and one 16-byte write per rotation); of the two
-    // columns a rotation turns, the lower one is the next rotation's upper one and stays in a register.
-    typedef double ql_d2 __attribute__((ext_vector_type(2)));
-    ql_d2 *de = reinterpret_cast<ql_d2 *>(e);
-    int iters = 0, failed = 0;
-#ifdef PTMI_QL_PROFILE
-    qt2 = __builtin_readcyclecounter();
-#endif
-    if (t < 64) {
-        const int k0 = t, k1 = t + 64;
-        const bool r0 = k0 < n, r1 = k1 < n;
-        {
-            // e[i - 1] = e[i], e[n - 1] = 0, then the pairs: every lane reads its entries before any lane writes
-            const int ia = t, ib = t + 64;
-            const double da = ia < n ? pq[ia] : 0.0, db = ib < n ? pq[ib] : 0.0;
-            const double ea = ia + 1 < n ? e[ia + 1] : 0.0, eb = ib + 1 < n ? e[ib + 1] : 0.0;
-            asm volatile("" ::: "memory");
-            if (ia < n) de[ia] = ql_d2{da, ea};
-            if (ib < n) de[ib] = ql_d2{db, eb};
-            asm volatile("" ::: "memory");
-        }
-#define QD(i) de[i].x
-#define QE(i) de[i].y
-        double f = 0.0, tst1 = 0.0;
-        for (int l = 0; l < n && !failed; ++l) {
-            const ql_d2 del = de[l];
-            const double t0 = __builtin_fabs(del.x) + __builtin_fabs(del.y);
-            if (tst1 < t0) tst1 = t0;
-            int m = l;
-            while (m < n - 1 && tst1 + __builtin_fabs(QE(m)) != tst1) ++m;
-            double dlf = del.x;                                  // d[l] as the iterations leave it
-            if (m > l) {
-                int it = 0;
-                double el;
-                do {
-                    if (++it > QL_MAXIT) { failed = 1; break; }
-                    ++iters;
-                    const ql_d2 pl = de[l], pl1 = de[l + 1];
-                    const double g = pl.x, e_l = pl.y;
-                    const double p0 = (pl1.x - g) / (2.0 * e_l);
-                    const double rr0 = det_sqrt(p0 * p0 + 1.0);
-                    const double pr = p0 + (p0 >= 0.0 ? rr0 : -rr0);
-                    const double dl = e_l / pr, dl1 = e_l * pr;
-                    const double h = g - dl;
-                    const double el1 = pl1.y;
-                    double p = QD(m);
-                    asm volatile("" ::: "memory");
-                    if (t == 0) { QD(l) = dl; QD(l + 1) = dl1; }
-                    for (int i = l + 2 + t; i < n; i += 64) QD(i) = QD(i) - h;
-                    asm volatile("" ::: "memory");
-                    f = f + h;
-                    if (m == l + 1) p = dl1; else if (m >= l + 2) p = p - h;     // d[m] as the updates above leave it
-                    double c = 1.0, c2 = 1.0, c3 = 1.0, s = 0.0, s2 = 0.0;
-                    ql_d2 nx = de[m - 1];                            // the next rotation's inputs are asked for a rotation ahead
-                    double zb0 = r0 ? z[k0 * n + m] : 0.0, zb1 = r1 ? z[k1 * n + m] : 0.0;     // column i + 1 of the lane's rows, carried
-                    for (int i = m - 1; i >= l; --i) {
-                        c3 = c2; c2 = c; s2 = s;
-                        const double di = nx.x, ei = nx.y;
-                        if (i > l) nx = de[i - 1];
-                        const double za0 = r0 ? z[k0 * n + i] : 0.0, za1 = r1 ? z[k1 * n + i] : 0.0;
-                        const double gg = c * ei, hh = c * p;
-                        double r, ri;
-                        ql_root_and_reciprocal(p * p + ei * ei, r, ri);
-                        const double e1 = s * r;
-                        s = ei * ri;
-                        c = p * ri;
-                        p = c * di - s * gg;
-                        const double d1 = hh + s * (c * gg + s * di);
-                        if (t == 0) de[i + 1] = ql_d2{d1, e1};
-                        if (r0) z[k0 * n + i + 1] = s * za0 + c * zb0;
-                        if (r1) z[k1 * n + i + 1] = s * za1 + c * zb1;
-                        zb0 = c * za0 - s * zb0;
-                        zb1 = c * za1 - s * zb1;
-                    }
-                    if (r0) z[k0 * n + l] = zb0;
-                    if (r1) z[k1 * n + l] = zb1;
-                    p = -s * s2 * c3 * el1 * e_l / dl1;
-                    el = s * p;
-                    dlf = c * p;
-                    asm volatile("" ::: "memory");
-                    if (t == 0) de[l] = ql_d2{dlf, el};
-                    asm volatile("" ::: "memory");
-                } while (tst1 + __builtin_fabs(el) != tst1);
-            }
-            asm volatile("" ::: "memory");
-            if (t == 0) de[l] = ql_d2{dlf + f, 0.0};
-            asm volatile("" ::: "memory");
-        }
-        if (t == 0 && status) {
-            if (failed) atomicOr(status, 1);
-        }
-    }
-    __syncthreads();
-#ifdef PTMI_QL_PROFILE
-    qt3 = __builtin_readcyclecounter();
-    if (t == 0 && (blockIdx.x == 0 || blockIdx.x == 3000)) printf("ql block %d: reduce %llu accumulate %llu ql %llu cycles, %d iterations\n", (int)blockIdx.x, qt1 - qt0, qt2 - qt1, qt3 - qt2, iters);
-#endif
-    // order and signs as eig_jacobi_kernel / orc_eig_ql
-    double *Uo = Ut + (size_t)blockIdx.x * ut_stride, *So = S + (size_t)blockIdx.x * s_stride;
-    for (int k = t; k < n; k += QL_THREADS) {
-        const double mine = __builtin_fabs(QD(k));
-        int rank = 0;
-        for (int j = 0; j < n; ++j) { const double o = __builtin_fabs(QD(j)); rank += (o > mine) || (o == mine && j < k); }
-        int im = 0;
-        for (int i = 1; i < n; ++i) if (__builtin_fabs(QZ(i, k)) > __builtin_fabs(QZ(im, k))) im = i;
-        const double sg = QZ(im, k) < 0.0 ? -1.0 : 1.0;
-        for (int i = 0; i < n; ++i) Uo[(size_t)rank * n + i] = sg * QZ(i, k);
-        So[rank] = mine;
-    }
-#undef QZ
-#undef QD
-#undef QE
-}
-
-// ---- the same in three kernels, for MANY matrices (per-walker covariances).  The QL phase is a chain of dependent scalar
-// operations (some 45 of them per rotation, ~20 cycles each for a lone wave: 900 cycles per rotation, 7.6 of the 10.3 M cycles a
-// matrix takes in eig_ql_kernel) and only two matrices fit a CU's LDS: 64 ms of chain per CU and epoch whatever is done to the rest.
-// But the chain needs the tridiagonal matrix alone -- 200 doubles, not the eigenvectors: eig_ql_chain_kernel runs the chains of ALL
-// matrices at once (a wave each, four per SIMD) and RECORDS the rotations (c, s) with the (l, m) of every iteration;
-// eig_ql_apply_kernel then turns the eigenvector rows with them, a thread per row and no scalar work.  Same operations on the
-// same values in the same order as orc_eig_ql: same bits.  A matrix whose rotations do not fit the record (3 n^2; nearly degenerate
-// 100 x 100 spectra take 0.8 n^2) is flagged and redone by the apply kernel with the chain and the rows together.
-typedef double qls_d2 __attribute__((ext_vector_type(2)));
-struct QlScratch {
-    double *z;          // [nmat][n][n]  the accumulated transformations, row-major
-    qls_d2 *de;         // [nmat][n]     {d[i], e[i]} (subdiagonal shifted: e[i] couples i and i + 1)
-    double *ev;         // [nmat][n]     the eigenvalues the chains end with
-    qls_d2 *rot;        // [nmat][cap]   the rotations, in the order they are applied
-    int32_t *hdr;       // [nmat][2 capit]  l, m of every QL iteration
-    int32_t *cnt;       // [nmat][2]     iterations recorded, overflow flag
-    int cap, capit;
-};
-// Reduction and accumulation for the three-kernel form, 256 threads: a dot product is the work of an OCT of lanes -- lane c runs chain
-// c of QL_DOT8 (terms k = c, c + 8, ...), the butterfly xor 4, xor 2, xor 1 is the oracle's ((s0 + s4) + (s2 + s6)) + ((s1 + s5) +
-// (s3 + s7)) in every lane -- 32 products at a time; the rank-two update and the column updates are 16 x 16 tilings of their
-// elements.  (A thread per row with the eight chains side by side left the threads of short rows idle and every wave alone on its
-// SIMD: 17 000 cycles per row of the reduction.)
-#ifndef PTMI_QLR_THREADS
-#define PTMI_QLR_THREADS 512
-#endif
-constexpr int QLR_THREADS = PTMI_QLR_THREADS, QLR_TY = QLR_THREADS / 16;
-__global__ __launch_bounds__(QLR_THREADS) void eig_ql_reduce_kernel(const double *cov, int n, QlScratch q)
-{
-    extern __shared__ __attribute__((aligned(16))) double qsm[];
-    double *z = qsm, *e = qsm + (((size_t)n * n + 1) & ~(size_t)1), *pq = e + n;
-    const int t = (int)threadIdx.x;
-    const int oct = t >> 3, c8 = t & 7, ty = t >> 4, tx = t & 15;
-    const double *A = cov + (size_t)blockIdx.x * n * n;
-#define QZ(i, j) z[(i) * n + (j)]
-    for (int i = t; i < n * n; i += QLR_THREADS) z[i] = A[i];
-    unsigned long long hmask[2] = {0ull, 0ull};
-    __syncthreads();
-    for (int i = n - 1; i >= 1; --i) {
-        const int l = i - 1;
-        double h = 0.0;
-        if (l > 0) {
-            double sc = 0.0;
-            for (int k = c8; k <= l; k += 8) { const double v = QZ(i, k); sc = __builtin_fma(v, v, sc); }
-            h = jac_oct_sum(sc);
-        }
-        if (l == 0 || h == 0.0) {                                 // uniform
-            if (t == 0) e[i] = QZ(i, l);
-            __syncthreads();
-            continue;
-        }
-        const double f0 = QZ(i, l);
-        const double g0 = f0 >= 0.0 ? -det_sqrt(h) : det_sqrt(h);
-        h = h - f0 * g0;
-        __syncthreads();                                          // every thread has read Z(i, l)
-        if (t == 0) { e[i] = g0; QZ(i, l) = f0 - g0; }
-        __syncthreads();
-        for (int j = oct; j <= l; j += QLR_THREADS / 8) {
-            double sc = 0.0;
-            for (int k = c8; k <= l; k += 8) sc = __builtin_fma(k <= j ? QZ(j, k) : QZ(k, j), QZ(i, k), sc);
-            const double g = jac_oct_sum(sc);
-            // the two quotients of row j by two lanes of its oct: one division sequence instead of two on the critical path
-            const double quo = (c8 == 0 ? g : QZ(i, j)) / h;
-            if (c8 == 0) pq[j] = quo;
-            else if (c8 == 1) QZ(j, i) = quo;
-        }
-        __syncthreads();
-        double fc = 0.0;
-        for (int k = c8; k <= l; k += 8) fc = __builtin_fma(pq[k], QZ(i, k), fc);
-        const double f = jac_oct_sum(fc);
-        const double hh = f / (h + h);
-        __syncthreads();                                          // every thread has its f
-        for (int j = t; j <= l; j += QLR_THREADS) pq[j] = pq[j] - hh * QZ(i, j);
-        __syncthreads();
-        for (int j = ty; j <= l; j += QLR_TY) {
-            const double uj = QZ(i, j), qj = pq[j];
-            for (int k = tx; k <= j; k += 16) QZ(j, k) = QZ(j, k) - (uj * pq[k] + qj * QZ(i, k));
-        }
-        hmask[i >> 6] |= 1ull << (i & 63);
-        __syncthreads();
-    }
-    if (t == 0) e[0] = 0.0;
-    for (int i = 0; i < n; ++i) {
-        const int l = i - 1;
-        if ((hmask[i >> 6] >> (i & 63)) & 1ull) {                  // uniform
-            // the products g_j of the leading block's columns with row i; row i is dead afterwards (zeroed below) and keeps them
-            double gj[4] = {0.0, 0.0, 0.0, 0.0};
-            int nj = 0;
-            for (int j = oct; j <= l; j += QLR_THREADS / 8, ++nj) {
-                double sc = 0.0;
-                for (int k = c8; k <= l; k += 8) sc = __builtin_fma(QZ(i, k), QZ(k, j), sc);
-                gj[nj & 3] = jac_oct_sum(sc);
-            }
-            __syncthreads();                                      // every product has read row i
-            nj = 0;
-            for (int j = oct; j <= l; j += QLR_THREADS / 8, ++nj)
-                if (c8 == 0) QZ(i, j) = gj[nj & 3];
-            __syncthreads();
-            for (int k = ty; k <= l; k += QLR_TY) {
-                const double zki = QZ(k, i);
-                for (int j = tx; j <= l; j += 16) QZ(k, j) = QZ(k, j) - QZ(i, j) * zki;
-            }
-        }
-        __syncthreads();
-        if (t == 0) { pq[i] = QZ(i, i); QZ(i, i) = 1.0; }
-        for (int j = t; j <= l; j += QLR_THREADS) { QZ(j, i) = 0.0; QZ(i, j) = 0.0; }
-        __syncthreads();
-    }
-#undef QZ
-    double *zo = q.z + (size_t)blockIdx.x * n * n;
-    for (int i = t; i < n * n; i += QLR_THREADS) zo[i] = z[i];
-    qls_d2 *deo = q.de + (size_t)blockIdx.x * n;
-    for (int i = t; i < n; i += QLR_THREADS) deo[i] = qls_d2{pq[i], i + 1 < n ? e[i + 1] : 0.0};
-}
-
-// the QL iterations on {d, e} pairs in LDS (one wave; every lane runs the scalar recurrence).  ROWS: the lane also turns rows t and
-// t + 64 of zt (the eigenvector matrix TRANSPOSED in LDS: column c at zt[c n ...], so that the lanes' rows sit side by side);
-// else the rotations and the iterations' (l, m) are recorded.  Returns the iterations (negative: an eigenvalue did not converge).
-template <bool ROWS>
-__device__ __forceinline__ int ql_iterate(qls_d2 *de, int n, int t, double *zt, qls_d2 *rot, int32_t *hdr, int cap, int capit, int *overflow)
-{
-    const int k0 = t, k1 = t + 64;
-    const bool r0 = ROWS && k0 < n, r1 = ROWS && k1 < n;
-    int iters = 0, nrot = 0;
-    bool over = false, failed = false;
-    double f = 0.0, tst1 = 0.0;
-    for (int l = 0; l < n && !failed; ++l) {
-        const qls_d2 del = de[l];
-        const double t0 = __builtin_fabs(del.x) + __builtin_fabs(del.y);
-        if (tst1 < t0) tst1 = t0;
-        int m = l;
-        while (m < n - 1 && tst1 + __builtin_fabs(de[m].y) != tst1) ++m;
-        double dlf = del.x;
-        if (m > l) {
-            int it = 0;
-            double el;
-            do {
-                if (++it > QL_MAXIT) { failed = true; break; }
-                if (!ROWS) {
-                    if (iters >= capit || nrot + (m - l) > cap) over = true;
-                    if (!over && t == 0) { hdr[2 * iters] = l; hdr[2 * iters + 1] = m; }
-                }
-                ++iters;
-                const qls_d2 pl = de[l], pl1 = de[l + 1];
-                const double g = pl.x, e_l = pl.y;
-                const double p0 = (pl1.x - g) / (2.0 * e_l);
-                const double rr0 = det_sqrt(p0 * p0 + 1.0);
-                const double pr = p0 + (p0 >= 0.0 ? rr0 : -rr0);
-                const double dl = e_l / pr, dl1 = e_l * pr;
-                const double h = g - dl;
-                const double el1 = pl1.y;
-                double p = de[m].x;
-                asm volatile("" ::: "memory");
-                if (t == 0) { de[l].x = dl; de[l + 1].x = dl1; }
-                for (int i = l + 2 + t; i < n; i += 64) de[i].x = de[i].x - h;
-                asm volatile("" ::: "memory");
-                f = f + h;
-                if (m == l + 1) p = dl1; else if (m >= l + 2) p = p - h;
-                double c = 1.0, c2 = 1.0, c3 = 1.0, s = 0.0, s2 = 0.0;
-                qls_d2 nx = de[m - 1];
-                double zb0 = r0 ? zt[m * n + k0] : 0.0, zb1 = r1 ? zt[m * n + k1] : 0.0;
-                for (int i = m - 1; i >= l; --i) {
-                    c3 = c2; c2 = c; s2 = s;
-                    const double di = nx.x, ei = nx.y;
-                    if (i > l) nx = de[i - 1];
-                    double za0 = 0.0, za1 = 0.0;
-                    if (ROWS) { za0 = r0 ? zt[i * n + k0] : 0.0; za1 = r1 ? zt[i * n + k1] : 0.0; }
-                    const double gg = c * ei, hh = c * p;
-                    double r, ri;
-                    ql_root_and_reciprocal(p * p + ei * ei, r, ri);
-                    const double e1 = s * r;
-                    s = ei * ri;
-                    c = p * ri;
-                    p = c * di - s * gg;
-                    const double d1 = hh + s * (c * gg + s * di);
-                    if (t == 0) de[i + 1] = qls_d2{d1, e1};
-                    if (ROWS) {
-                        if (r0) zt[(i + 1) * n + k0] = s * za0 + c * zb0;
-                        if (r1) zt[(i + 1) * n + k1] = s * za1 + c * zb1;
-                        zb0 = c * za0 - s * zb0;
-                        zb1 = c * za1 - s * zb1;
-                    } else if (!over && t == 0) {
-                        rot[nrot + (m - 1 - i)] = qls_d2{c, s};
-                    }
-                }
-                if (ROWS) {
-                    if (r0) zt[l * n + k0] = zb0;
-                    if (r1) zt[l * n + k1] = zb1;
-                }
-                nrot += m - l;
-                p = -s * s2 * c3 * el1 * e_l / dl1;
-                el = s * p;
-                dlf = c * p;
-                asm volatile("" ::: "memory");
-                if (t == 0) de[l] = qls_d2{dlf, el};
-                asm volatile("" ::: "memory");
-            } while (tst1 + __builtin_fabs(el) != tst1);
-        }
-        asm volatile("" ::: "memory");
-        if (t == 0) de[l] = qls_d2{dlf + f, 0.0};
-        asm volatile("" ::: "memory");
-    }
-    if (overflow) *overflow = over ? 1 : 0;
-    return failed ? -iters - 1 : iters;
-}
-
-__global__ __launch_bounds__(64) void eig_ql_chain_kernel(int n, QlScratch q)
-{
-    extern __shared__ __attribute__((aligned(16))) double qsm[];
-    qls_d2 *de = reinterpret_cast<qls_d2 *>(qsm);
-    const int t = (int)threadIdx.x;
-    const size_t b = blockIdx.x;
-    for (int i = t; i < n; i += 64) de[i] = q.de[b * n + i];
-    asm volatile("" ::: "memory");
-    int over = 0;
-    const int iters = ql_iterate<false>(de, n, t, nullptr, q.rot + b * (size_t)q.cap, q.hdr + b * 2 * (size_t)q.capit, q.cap, q.capit, &over);
-    asm volatile("" ::: "memory");
-    for (int i = t; i < n; i += 64) q.ev[b * n + i] = de[i].x;
-    if (t == 0) { q.cnt[2 * b] = iters < 0 ? 0 : iters; q.cnt[2 * b + 1] = (over || iters < 0) ? 1 : 0; }
-}
-
-__global__ __launch_bounds__(QL_THREADS) void eig_ql_apply_kernel(double *Ut, double *S, int n, int ut_stride, int s_stride, QlScratch q, int redo_only)
-{
-    if (redo_only && q.cnt[2 * blockIdx.x + 1] == 0) return;      // eig_ql_apply_reg_kernel has done this matrix
-
-    extern __shared__ __attribute__((aligned(16))) double qsm[];
-    double *zt = qsm;                                              // zt[c n + k] = Z(k, c)
-    qls_d2 *de = reinterpret_cast<qls_d2 *>(qsm + (((size_t)n * n + 1) & ~(size_t)1));
-    const int t = (int)threadIdx.x;
-    const size_t b = blockIdx.x;
-    const double *zi = q.z + b * n * n;
-    for (int i = t; i < n * n; i += QL_THREADS) { const int r = i / n, c = i % n; zt[c * n + r] = zi[i]; }
-    const bool redo = q.cnt[2 * b + 1] != 0;                       // the record did not hold this matrix's rotations
-    if (redo) {
-        for (int i = t; i < n; i += QL_THREADS) de[i] = q.de[b * n + i];
-        __syncthreads();
-        if (t < 64) ql_iterate<true>(de, n, t, zt, nullptr, nullptr, 0, 0, nullptr);
-    } else {
-        // A thread per row.  The rotations of ONE iteration (at most n - 1 of them) are staged in LDS -- the pairs' 2 n doubles,
-        // free until the eigenvalues go there -- by all threads at once, the next iteration's requested before this one's are
-        // applied (a read of the record per rotation sat on every row's chain with its whole memory round trip: 300 cycles per
-        // rotation).  Of the two columns a rotation turns, the lower one is the next rotation's upper one and stays in a register.
-        const int nit = q.cnt[2 * b];
-        const int32_t *hdr = q.hdr + b * 2 * (size_t)q.capit;
-        const qls_d2 *rot = q.rot + b * (size_t)q.cap;
-        int r = 0;
-        int l = nit > 0 ? hdr[0] : 0, m = nit > 0 ? hdr[1] : 0;
-        int ln = nit > 1 ? hdr[2] : 0, mn = nit > 1 ? hdr[3] : 0;  // the (l, m) of the iteration after: known two iterations ahead
-        qls_d2 mine = (nit > 0 && t < m - l) ? rot[t] : qls_d2{0.0, 0.0};
-        for (int itn = 0; itn < nit; ++itn) {
-            const int cntr = m - l;
-            __syncthreads();                                        // the previous iteration's rotations have been applied
-            if (t < cntr) de[t] = mine;
-            __syncthreads();
-            r += cntr;
-            const int lnn = itn + 2 < nit ? hdr[2 * itn + 4] : 0, mnn = itn + 2 < nit ? hdr[2 * itn + 5] : 0;
-            if (itn + 1 < nit && t < mn - ln) mine = rot[r + t];
-            if (t < n) {
-                double zb = zt[m * n + t];
-                const double *zp = zt + (size_t)(m - 1) * n + t;    // column i of this thread's row, i descending
-                int j = 0;
-                for (; j + 4 <= cntr; j += 4, zp -= 4 * n) {       // four rotations a trip: their reads go out together
-                    const qls_d2 c0 = de[j], c1 = de[j + 1], c2 = de[j + 2], c3 = de[j + 3];
-                    const double a0 = zp[0], a1 = zp[-n], a2 = zp[-2 * n], a3 = zp[-3 * n];
-                    const_cast<double *>(zp)[n] = c0.y * a0 + c0.x * zb;
-                    zb = c0.x * a0 - c0.y * zb;
-                    const_cast<double *>(zp)[0] = c1.y * a1 + c1.x * zb;
-                    zb = c1.x * a1 - c1.y * zb;
-                    const_cast<double *>(zp)[-n] = c2.y * a2 + c2.x * zb;
-                    zb = c2.x * a2 - c2.y * zb;
-                    const_cast<double *>(zp)[-2 * n] = c3.y * a3 + c3.x * zb;
-                    zb = c3.x * a3 - c3.y * zb;
-                }
-                for (; j < cntr; ++j, zp -= n) {
-                    const qls_d2 cs = de[j];
-                    const double za = zp[0];
-                    const_cast<double *>(zp)[n] = cs.y * za + cs.x * zb;
-                    zb = cs.x * za - cs.y * zb;
-                }
-                zt[l * n + t] = zb;
-            }
-            l = ln; m = mn;
-            ln = lnn; mn = mnn;
-        }
-        __syncthreads();
-        for (int i = t; i < n; i += QL_THREADS) de[i] = qls_d2{q.ev[b * n + i], 0.0};
-    }
-    __syncthreads();
-    double *Uo = Ut + b * ut_stride, *So = S + b * s_stride;
-    for (int k = t; k < n; k += QL_THREADS) {
-        const double mine = __builtin_fabs(de[k].x);
-        int rank = 0;
-        for (int j = 0; j < n; ++j) { const double o = __builtin_fabs(de[j].x); rank += (o > mine) || (o == mine && j < k); }
-        const double *col = zt + (size_t)k * n;                    // Z(i, k), i = 0 .. n - 1
-        int im = 0;
-        for (int i = 1; i < n; ++i) if (__builtin_fabs(col[i]) > __builtin_fabs(col[im])) im = i;
-        const double sg = col[im] < 0.0 ? -1.0 : 1.0;
-        for (int i = 0; i < n; ++i) Uo[(size_t)rank * n + i] = sg * col[i];
-        So[rank] = mine;
-    }
-}
-
-// The apply step with the eigenvector matrix in REGISTERS (n <= 100): thread t holds row t of Z, z[0 .. n - 1], and a rotation of
-// columns (i, i + 1) is six instructions on two registers of every thread -- the record's (c, s) and the iterations' (l, m) are the
-// same for all rows: uniform branches, (c, s) an LDS broadcast staged by each wave for itself; no barrier until the end, four matrices (eight waves)
-// per CU instead of the two that fit with Z in LDS.  Register indices are compile-time: an iteration's sweep i = m - 1 ... l is the
-// unrolled sweep 98 ... 0 entered block by block (QLA_BLK = 8 steps, 2.29 ms against 2.41 with 4; a block outside [l, m) is one uniform branch, a block inside it
-// runs without tests).  eig_ql_apply_kernel: 4.15 ms per epoch at 4096 x 100 x 100 (a wave per SIMD, an LDS round trip on every
-// row's chain per four rotations).  Matrices whose record overflowed are left to that kernel (redo_only).
-#ifndef PTMI_QLA_BLK
-#define PTMI_QLA_BLK 8
-#endif
-constexpr int QLA_N = 100, QLA_BLK = PTMI_QLA_BLK;
-template <int LO, int HI, bool CHECK>
-__device__ __forceinline__ void qla_steps(double (&z)[QLA_N], const qls_d2 *cs_of_step, int l, int m)
-{
-#pragma unroll
-    for (int i = HI; i >= LO; --i) {
-        if (!CHECK || (i >= l && i < m)) {
-            const qls_d2 cs = cs_of_step[i];                        // {c, s}: an LDS broadcast at a compile-time offset
-            const double za = z[i], zb = z[i + 1];
-            z[i + 1] = cs.y * za + cs.x * zb;
-            z[i] = cs.x * za - cs.y * zb;
-        }
-    }
-}
-template <int BLKI>
-__device__ __forceinline__ void qla_sweep(double (&z)[QLA_N], const qls_d2 *cs_of_step, int l, int m)
-{
-    constexpr int LO = QLA_BLK * BLKI, HI = LO + QLA_BLK - 1 < QLA_N - 2 ? LO + QLA_BLK - 1 : QLA_N - 2;
-    if (HI >= l && LO < m) {
-        if (LO >= l && HI < m) qla_steps<LO, HI, false>(z, cs_of_step, l, m);
-        else qla_steps<LO, HI, true>(z, cs_of_step, l, m);
-    }
-    if constexpr (BLKI > 0) qla_sweep<BLKI - 1>(z, cs_of_step, l, m);
-}
-__global__ __launch_bounds__(128, 2) void eig_ql_apply_reg_kernel(double *Ut, double *S, int n, int ut_stride, int s_stride,
-                                                                  const double *__restrict__ zin, const double *__restrict__ evin,
-                                                                  const qls_d2 *__restrict__ rot_all, const int32_t *__restrict__ hdr_all,
-                                                                  const int32_t *__restrict__ cnt, int cap, int capit)
-{
-    __shared__ double wmax[2][QLA_N], wsv[2][QLA_N], sgs[QLA_N];
-    __shared__ int rk[QLA_N];
-    // an iteration's rotations, staged by each wave for itself (no barrier): slot i = the rotation of step i; the next iteration's
-    // are requested before this one's sweep and stored behind it (a scalar load per block of the sweep waited 600 cycles each)
-    __shared__ __attribute__((aligned(16))) qls_d2 stg[2][2][QLA_N];
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const size_t b = blockIdx.x;
-    if (cnt[2 * b + 1] != 0) return;                                // the record did not hold this matrix's rotations
-    const bool rowok = t < n;
-    double z[QLA_N];
-    {
-        const double *zi = zin + b * n * n + (size_t)(rowok ? t : 0) * n;
-#pragma unroll
-        for (int c = 0; c < QLA_N; ++c) z[c] = c < n ? zi[c] : 0.0;
-    }
-    const int nit = cnt[2 * b];
-    const int32_t *hdr = hdr_all + b * 2 * (size_t)capit;
-    const qls_d2 *rot = rot_all + b * (size_t)cap;
-    int l = nit > 0 ? hdr[0] : 0, m = nit > 0 ? hdr[1] : 0;
-    int ln = nit > 1 ? hdr[2] : 0, mn = nit > 1 ? hdr[3] : 0;      // the (l, m) of the iteration after: known two iterations ahead
-    int r = 0;
-    {
-        const int cn = m - l;
-        if (lane < cn) stg[wave][0][m - 1 - lane] = rot[lane];
-        if (lane + 64 < cn) stg[wave][0][m - 1 - lane - 64] = rot[lane + 64];
-    }
-    for (int itn = 0; itn < nit; ++itn) {
-        r += m - l;
-        const int lnn = itn + 2 < nit ? hdr[2 * itn + 4] : 0, mnn = itn + 2 < nit ? hdr[2 * itn + 5] : 0;
-        const int cn = itn + 1 < nit ? mn - ln : 0;
-        qls_d2 nx0 = qls_d2{0.0, 0.0}, nx1 = qls_d2{0.0, 0.0};
-        if (lane < cn) nx0 = rot[r + lane];
-        if (lane + 64 < cn) nx1 = rot[r + lane + 64];
-        __builtin_amdgcn_wave_barrier();
-        qla_sweep<(QLA_N - 2) / QLA_BLK>(z, stg[wave][itn & 1], l, m);
-        __builtin_amdgcn_wave_barrier();
-        if (lane < cn) stg[wave][(itn + 1) & 1][mn - 1 - lane] = nx0;
-        if (lane + 64 < cn) stg[wave][(itn + 1) & 1][mn - 1 - lane - 64] = nx1;
-        l = ln; m = mn;
-        ln = lnn; mn = mnn;
-    }
-    // the sign of every eigenvector: its first component of largest magnitude becomes positive (row ascending, strict >)
-#pragma unroll
-    for (int k = 0; k < QLA_N; ++k) {
-        if (k < n) {
-            const double a = rowok ? __builtin_fabs(z[k]) : -1.0;
-            double mx = a;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) { const double ot = __shfl_xor(mx, o, 64); mx = ot > mx ? ot : mx; }
-            const unsigned long long eq = __ballot(a == mx);
-            const int first = __builtin_ctzll(eq);
-            const double sv = __shfl(z[k], first, 64);
-            if (lane == 0) { wmax[wave][k] = mx; wsv[wave][k] = sv; }
-        }
-    }
-    __syncthreads();
-    if (rowok) {
-        const int k = t;
-        const double sv = wmax[1][k] > wmax[0][k] ? wsv[1][k] : wsv[0][k];
-        sgs[k] = sv < 0.0 ? -1.0 : 1.0;
-        const double *ev = evin + b * n;
-        const double mine = __builtin_fabs(ev[k]);
-        int rank = 0;
-        for (int j = 0; j < n; ++j) { const double o = __builtin_fabs(ev[j]); rank += (o > mine) || (o == mine && j < k); }
-        rk[k] = rank;
-        S[b * s_stride + rank] = mine;
-    }
-    __syncthreads();
-    double *Uo = Ut + b * ut_stride;
-#pragma unroll
-    for (int k = 0; k < QLA_N; ++k) {
-        if (k < n && rowok) Uo[(size_t)rk[k] * n + t] = sgs[k] * z[k];
-    }
-}
-
 // ------------------------------------------------ launch order of the gradient-jump kernel
 // Counting sort of the chains by the NUTS step size of their rank (half-octave classes, smallest first = longest
 // trees first; a rank that has no step size yet is in class 0: its first call searches for one), then dealt across the
@@ -2593,7 +1401,7 @@ int ptmi_create(const ptmi_config *cfg, const ptmi_buffers *buf, ptmi_handle *ou
     h->cfg.gj_tab = nullptr;
     h->cfg.ladder = h->cfg.temps_mh = h->cfg.logl_par = h->cfg.logp_par = h->cfg.group_mask = nullptr;  // host copies are not kept
     h->cfg.group_size = nullptr;
-    hipError_t e = hipMalloc((void **)&h->d_pre, sizeof(SwapPre) * (size_t)c.nwalkers * c.ntemps_global);
+    hipError_t e = hipMalloc((void **)&h->d_pre, PTMI_SWAP_PRE_BYTES * (size_t)c.nwalkers * c.ntemps_global);
     if (e == hipSuccess && !c.cov_per_walker && c.temp0 == 0) {
         const int SL = pool_slab(c.nwalkers, c.ndim), nslab = (c.nwalkers + SL - 1) / SL;
         e = hipMalloc((void **)&h->d_pool_part, sizeof(double) * (size_t)nslab * c.ndim * (c.ndim + 1));
@@ -2662,8 +1470,6 @@ int ptmi_create(const ptmi_config *cfg, const ptmi_buffers *buf, ptmi_handle *ou
     return PTMI_OK;
 }
 
-static void dc_plan_free(ptmi_engine *h);
-
 int ptmi_destroy(ptmi_handle h)
 {
     if (!h) return PTMI_OK;
@@ -2673,7 +1479,7 @@ int ptmi_destroy(ptmi_handle h)
     (void)hipFree(h->d_gsize); (void)hipFree(h->d_gmask); (void)hipFree(h->d_gcn); (void)hipFree(h->d_gdiv); (void)hipFree(h->d_pool_part); (void)hipFree(h->d_pool_T);
     (void)hipFree(h->d_ql_scr); (void)hipFree(h->d_qlg_scr); (void)hipFree(h->d_sy_scr); (void)hipFree(h->d_utpad);
     free(h->gsize_host);
-    dc_plan_free(h);
+    ptmi_dc_plan_free(h);
     if (h->h_sy_info) (void)hipHostFree(h->h_sy_info);
     (void)hipFree(h->d_rle_ent); (void)hipFree(h->d_rle_cnt);
     (void)hipFree(h->d_am_ev); (void)hipFree(h->d_am_count); (void)hipFree(h->d_am_base); (void)hipFree(h->d_am_inc);
@@ -3074,376 +1880,6 @@ int ptmi_proposals(ptmi_handle h, double **q)
     return PTMI_OK;
 }
 
-int ptmi_swap_write_am(ptmi_handle h, int64_t iter)
-{
-    if (!h) return fail(PTMI_EINVAL, "NULL handle");
-    if (h->cfg.temp0 != 0 || !h->buf.AM) return PTMI_OK;
-    hipLaunchKernelGGL(am_write_kernel, dim3(h->cfg.nwalkers), dim3(64), 0, h->stream, (const double *)h->buf.X,
-                       (const double *)h->buf.lnL, (const double *)h->buf.lp, (const int32_t *)h->buf.slot_of, h->buf.AM,
-                       h->buf.AMaux, h->cfg.nwalkers, h->cfg.ntemps, h->cfg.ndim, h->cfg.cov_update, (long long)iter, am_row_epl(h->G, h->EPL),
-                       (AmFlag *)h->buf.AMflag);
-    HIPCHK(hipGetLastError());
-    return PTMI_OK;
-}
-
-// odd/even mode: swap epoch e = iter / tskip tries the pairs (k, k+1) with k = e (mod 2)
-static int swap_parity(const ptmi_config &c, int64_t iter)
-{
-    return (int)((c.tskip > 0 ? iter / c.tskip : iter) & 1);
-}
-
-static int launch_swap_sweep(ptmi_engine *h, int W, int n, const SwapPre *pre, int32_t *slot_of, int32_t *temp_of,
-                             int32_t *map, u64 *nswap, int local0, int nlocal, int parity, int32_t *inv, int hop_nt = 0, bool *hop_done = nullptr,
-                             const SwapAmRow *amr = nullptr, bool *am_done = nullptr)
-{
-    if (hop_done) *hop_done = false;
-    if (am_done) *am_done = false;
-    SwapAmRow none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 0, 0, nullptr};
-    int wpb = 64;                                                      // 2 tables of wpb x (n + 1) ints must fit the CU's LDS
-    while (wpb > 8 && sizeof(int32_t) * (2 * (size_t)wpb * (size_t)(n + 1) + n) > 160 * 1024) wpb /= 2;
-    const size_t lds = sizeof(int32_t) * (2 * (size_t)wpb * (size_t)(n + 1) + n);      // forward table, flags, block of a position
-    if (lds <= 160 * 1024) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)swap_sweep_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return fail(PTMI_EHIP, "hipFuncSetAttribute(%zu B of LDS): %s", lds, hipGetErrorString(e));
-        }
-        if (hop_nt > 0) {                                              // the multi-hop scan rides on the write-out
-            HIPCHK(hipMemsetAsync(h->d_hop, 0, sizeof(int32_t), h->stream));
-            if (hop_done) *hop_done = true;
-        }
-        const bool with_am = amr != nullptr && slot_of != nullptr;
-        hipLaunchKernelGGL(swap_sweep_kernel<true>, dim3((unsigned)((W + wpb - 1) / wpb)), dim3(256), lds, h->stream, W, n, h->d_ladder, pre,
-                           slot_of, temp_of, map, nswap, local0, nlocal, parity, inv, wpb, hop_nt, h->d_hop, with_am ? *amr : none);
-        if (am_done) *am_done = with_am;
-    } else {
-        hipLaunchKernelGGL(swap_sweep_kernel<false>, dim3((unsigned)((W + 63) / 64)), dim3(64), 0, h->stream, W, n, h->d_ladder, pre,
-                           slot_of, temp_of, map, nswap, local0, nlocal, parity, inv, 64, 0, (int32_t *)nullptr, none);
-    }
-    return PTMI_OK;
-}
-
-// The sweep with its records made in the block (swap_fused_kernel) when its tables and the ring fit the LDS; *used says whether it
-// was launched (else the caller runs swap_prepare_kernel + swap_sweep_kernel).  PTMI_SWAP_FUSED=0: the two-kernel form (a
-// test hook, same results).
-static int launch_swap_fused(ptmi_engine *h, int W, int n, const SwapSrc &src, int32_t *slot_of, int32_t *temp_of, int32_t *map, u64 *nswap,
-                             int local0, int nlocal, int parity, int32_t *inv, int hop_nt, bool *hop_done, const SwapAmRow *amr, bool *am_done,
-                             bool *used)
-{
-    *used = false;
-    if (hop_done) *hop_done = false;
-    if (am_done) *am_done = false;
-    if (!ptmi_env("PTMI_SWAP_FUSED", 1)) return PTMI_OK;
-    // walkers per block: 16 puts the 4096 walkers of config 2 on every CU (64 per block ran on 64 CUs: 31 -> 24 us per swap epoch
-    // at 64 ranks; 8 starve the producers: 38); long ladders are cut further by the LDS their tables need
-    int wpb = 64, lg = 6;
-    const int want = n <= 128 ? 16 : 32;                           // 256 ranks: 94 us with 32 or 64, 104 with 16
-    while (wpb > 8 && wpb > want) { wpb /= 2; --lg; }
-    while (wpb > 8 && swf_lds_bytes(wpb, n) > 160 * 1024) { wpb /= 2; --lg; }
-    const size_t lds = swf_lds_bytes(wpb, n);
-    if (lds > 160 * 1024) return PTMI_OK;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)swap_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(PTMI_EHIP, "hipFuncSetAttribute(%zu B of LDS): %s", lds, hipGetErrorString(e));
-    }
-    if (hop_nt > 0) {                                              // the multi-hop scan rides on the write-out
-        HIPCHK(hipMemsetAsync(h->d_hop, 0, sizeof(int32_t), h->stream));
-        if (hop_done) *hop_done = true;
-    }
-    const SwapAmRow none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 0, 0, nullptr};
-    const bool with_am = amr != nullptr && slot_of != nullptr;
-    hipLaunchKernelGGL(swap_fused_kernel, dim3((unsigned)((W + wpb - 1) / wpb)), dim3(SWF_BLK), lds, h->stream, W, n, src, slot_of, temp_of, map,
-                       nswap, local0, nlocal, parity, inv, wpb, lg, hop_nt, h->d_hop, with_am ? *amr : none);
-    if (am_done) *am_done = with_am;
-    *used = true;
-    return PTMI_OK;
-}
-
-int ptmi_swap(ptmi_handle h, int64_t iter)
-{
-    if (!h) return fail(PTMI_EINVAL, "NULL handle");
-    const ptmi_config &c = h->cfg;
-    if (c.ntemps != c.ntemps_global) return fail(PTMI_EINVAL, "ptmi_swap needs the whole ladder on this GPU; use the three-piece form");
-    if (!h->buf.nswap) return fail(PTMI_EINVAL, "nswap buffer missing");
-    if (c.ntemps < 2) return PTMI_OK;
-    const int W = c.nwalkers;
-    if (c.swap_mode == PTMI_SWAP_ODDEVEN) {
-        const int parity = swap_parity(c, iter);
-        const long long np = (long long)W * ((c.ntemps - parity) / 2);
-        if (np > 0)
-            hipLaunchKernelGGL(swap_oddeven_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream, W, c.ntemps,
-                               h->d_ladder, (const double *)h->buf.lnL, h->buf.slot_of, h->buf.temp_of, (u64 *)h->buf.nswap,
-                               (long long)iter, c.seed, c.walker0, parity);
-        HIPCHK(hipGetLastError());
-        return ptmi_swap_write_am(h, iter);
-    }
-    const SwapSrc src = {h->d_ladder, (const double *)nullptr, (const double *)h->buf.lnL, (const int32_t *)h->buf.slot_of, (long long)iter, c.seed,
-                         c.walker0, 0, h->rp_swap_u};
-    // the sweep's write-out also stores the swap iteration's AM row (one kernel and one launch gap less per swap epoch)
-    const SwapAmRow amr = {(const double *)h->buf.X, (const double *)h->buf.lnL, (const double *)h->buf.lp, h->buf.AM, h->buf.AMaux,
-                           c.ndim, c.cov_update, am_row_epl(h->G, h->EPL), (long long)iter, (AmFlag *)h->buf.AMflag};
-    bool am_done = false, used = false;
-    if (int rc = launch_swap_fused(h, W, c.ntemps, src, h->buf.slot_of, h->buf.temp_of, (int32_t *)nullptr, (u64 *)h->buf.nswap, 0, c.ntemps, -1,
-                                   (int32_t *)nullptr, 0, nullptr, (c.temp0 == 0 && h->buf.AM) ? &amr : nullptr, &am_done, &used)) return rc;
-    if (used) {
-        HIPCHK(hipGetLastError());
-        return am_done ? PTMI_OK : ptmi_swap_write_am(h, iter);
-    }
-    hipLaunchKernelGGL(swap_prepare_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)c.ntemps), dim3(256), 0, h->stream, W, c.ntemps, src,
-                       (SwapPre *)h->d_pre);
-    if (int rc = launch_swap_sweep(h, W, c.ntemps, (const SwapPre *)h->d_pre, h->buf.slot_of, h->buf.temp_of,
-                                   (int32_t *)nullptr, (u64 *)h->buf.nswap, 0, c.ntemps, -1, (int32_t *)nullptr, 0, nullptr,
-                                   (c.temp0 == 0 && h->buf.AM) ? &amr : nullptr, &am_done)) return rc;
-    HIPCHK(hipGetLastError());
-    return am_done ? PTMI_OK : ptmi_swap_write_am(h, iter);
-}
-
-int ptmi_swap_gather_lnl(ptmi_handle h, double *out)
-{
-    if (!h || !out) return fail(PTMI_EINVAL, "NULL argument");
-    const long long n = (long long)h->cfg.nwalkers * h->cfg.ntemps;
-    hipLaunchKernelGGL(gather_lnl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->buf.lnL,
-                       h->buf.slot_of, out, n, h->cfg.ntemps);
-    HIPCHK(hipGetLastError());
-    return PTMI_OK;
-}
-
-// exchange scratch: inv[W][ntg] (written by the sweep), newslot[W][T], arr_slot[nranks][W], lv_slot[2][W], lv_rank[2][W], err[1]
-static size_t xint_count(const ptmi_config &c)
-{
-    const size_t W = (size_t)c.nwalkers, nr = (size_t)((c.ntemps_global + c.ntemps - 1) / c.ntemps);
-    return W * c.ntemps_global + W * c.ntemps + nr * W + 4 * W + 1;
-}
-static int ensure_xint(ptmi_engine *h)
-{
-    if (h->d_xint) return PTMI_OK;
-    HIPCHK(hipMalloc((void **)&h->d_xint, sizeof(int32_t) * xint_count(h->cfg)));
-    HIPCHK(hipMemsetAsync(h->d_xint, 0, sizeof(int32_t) * xint_count(h->cfg), h->stream));
-    HIPCHK(hipMalloc((void **)&h->d_hop, sizeof(int32_t)));
-    HIPCHK(hipMemsetAsync(h->d_hop, 0, sizeof(int32_t), h->stream));
-    HIPCHK(hipHostMalloc((void **)&h->h_hop, sizeof(int32_t), hipHostMallocDefault));
-    *h->h_hop = 0;
-    HIPCHK(hipEventCreateWithFlags(&h->hop_ev, hipEventDisableTiming));
-    return PTMI_OK;
-}
-
-static int sweep_global(ptmi_handle h, int64_t iter, const double *lnL, int32_t *map, int block_nt)
-{
-    if (!h || !lnL || !map) return fail(PTMI_EINVAL, "NULL argument");
-    if (!h->buf.nswap) return fail(PTMI_EINVAL, "nswap buffer missing");
-    const ptmi_config &c = h->cfg;
-    const int W = c.nwalkers;
-    if (int rc = ensure_xint(h)) return rc;
-    const SwapSrc src = {h->d_ladder, lnL, (const double *)nullptr, (const int32_t *)nullptr, (long long)iter, c.seed, c.walker0, block_nt, h->rp_swap_u};
-    const int parity = c.swap_mode == PTMI_SWAP_ODDEVEN ? swap_parity(c, iter) : -1;
-    bool used = false;
-    if (int rc = launch_swap_fused(h, W, c.ntemps_global, src, (int32_t *)nullptr, (int32_t *)nullptr, map, (u64 *)h->buf.nswap, c.temp0, c.ntemps,
-                                   parity, h->d_xint /* inv[W][ntemps_global] */, block_nt, &h->hop_from_sweep, nullptr, nullptr, &used)) return rc;
-    if (used) {
-        HIPCHK(hipGetLastError());
-        return PTMI_OK;
-    }
-    hipLaunchKernelGGL(swap_prepare_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)c.ntemps_global), dim3(256), 0, h->stream, W, c.ntemps_global,
-                       src, (SwapPre *)h->d_pre);
-    if (int rc = launch_swap_sweep(h, W, c.ntemps_global, (const SwapPre *)h->d_pre, (int32_t *)nullptr,
-                                   (int32_t *)nullptr, map, (u64 *)h->buf.nswap, c.temp0, c.ntemps,
-                                   c.swap_mode == PTMI_SWAP_ODDEVEN ? swap_parity(c, iter) : -1, h->d_xint /* inv[W][ntemps_global] */,
-                                   block_nt, &h->hop_from_sweep)) return rc;
-    HIPCHK(hipGetLastError());
-    return PTMI_OK;
-}
-int ptmi_swap_sweep(ptmi_handle h, int64_t iter, const double *lnL_pos_global, int32_t *map)
-{
-    return sweep_global(h, iter, lnL_pos_global, map, 0);
-}
-int ptmi_swap_sweep_blocks(ptmi_handle h, int64_t iter, const double *lnL_blocks, int32_t *map)
-{
-    if (h && h->cfg.ntemps_global % h->cfg.ntemps) return fail(PTMI_EINVAL, "the ladder is not a whole number of blocks");
-    return sweep_global(h, iter, lnL_blocks, map, h ? h->cfg.ntemps : 0);
-}
-
-// ---- device-side exchange of the rows that cross a block edge --------------------------------------------------
-// One wave per walker, one lane per local position.  From the global map and its inverse (both written by the sweep)
-// it (1) lists this block's leaving rows (local source, remote destination) and arriving rows (local destination,
-// remote source), both in ascending local position -- the k-th arrival takes the slot the k-th departure frees, the
-// rule of sharded.py's plan_exchange -- and (2) rewrites slot_of / temp_of.  A hot -> cold sweep moves at most one
-// row of a walker down out of a block (the carried state) and at most one up (displaced by one level), hence the
-// fixed [2][W] / [nranks][W] tables.  The work is O(local ranks), whatever the length of the whole ladder.
-__global__ __launch_bounds__(256) void exchange_plan_kernel(int W, int nt, int ntg, int temp0, int nranks, const int32_t *map,
-                                                            int32_t *slot_of, int32_t *temp_of, const int32_t *inv, int32_t *newslot,
-                                                            int32_t *arr_slot, int32_t *lv_slot, int32_t *lv_rank, int32_t *err)
-{
-    const int lane = (int)(threadIdx.x & 63);
-    const int w = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    if (w >= W) return;
-    const int me = temp0 / nt;
-    const int32_t *m = map + (size_t)w * ntg + temp0, *iv = inv + (size_t)w * ntg + temp0;
-    int32_t *so = slot_of + (size_t)w * nt, *to = temp_of + (size_t)w * nt, *ns = newslot + (size_t)w * nt;
-    const u64 lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));            // lanes below this one
-    for (int q = lane; q < nranks; q += 64) arr_slot[(size_t)q * W + w] = -1;
-    // departures, ascending local position
-    int nlv = 0, freed0 = -1, freed1 = -1, lq0 = -1, lq1 = -1;
-    for (int base = 0; base < nt; base += 64) {
-        const int p = base + lane;
-        const bool valid = p < nt;
-        const int q = valid ? iv[p] / nt : me;
-        const int slot = valid ? so[p] : -1;
-        const bool leaving = valid && q != me;
-        u64 mask = __ballot(leaving);
-        while (mask) {
-            const int l = __builtin_ctzll(mask);
-            const int fs = __shfl(slot, l, 64), fq = __shfl(q, l, 64);
-            if (nlv == 0) { freed0 = fs; lq0 = fq; }
-            else if (nlv == 1) { freed1 = fs; lq1 = fq; }
-            ++nlv;
-            mask &= mask - 1;
-        }
-    }
-    // arrivals, ascending local position; rows that stay keep their slot
-    int narr = 0, aq0 = -1;
-    bool bad = nlv > 2 || (nlv == 2 && lq0 == lq1);                       // two destinations on one GPU would collide in send[q][w]
-    for (int base = 0; base < nt; base += 64) {
-        const int j = base + lane;
-        const bool valid = j < nt;
-        const int src = valid ? m[j] : temp0;
-        const int q = src / nt;
-        const bool arriving = valid && q != me;
-        const u64 mask = __ballot(arriving);
-        const int rank = narr + __builtin_popcountll(mask & lt);
-        if (valid) {
-            int slot;
-            if (!arriving) slot = so[src - temp0];
-            else {
-                slot = rank == 0 ? freed0 : (rank == 1 ? freed1 : -1);
-                if (slot >= 0) arr_slot[(size_t)q * W + w] = slot;
-                else { bad = true; slot = 0; }
-            }
-            ns[j] = slot;
-        }
-        if (mask) {                                                       // two arrivals from one GPU would collide in recv[q][w]
-            const int l0 = __builtin_ctzll(mask);
-            const int q0 = __shfl(q, l0, 64);
-            if (narr == 0) aq0 = q0;
-            else if (q0 == aq0) bad = true;
-            const u64 rest = mask & (mask - 1);
-            if (rest) {
-                const int q1 = __shfl(q, __builtin_ctzll(rest), 64);
-                if (q1 == aq0) bad = true;
-            }
-        }
-        narr += __builtin_popcountll(mask);
-    }
-    if (narr != nlv) bad = true;
-    if (lane == 0) {                                                      // -1 = no such departure
-        lv_slot[w] = freed0; lv_rank[w] = lq0;
-        lv_slot[W + w] = freed1; lv_rank[W + w] = lq1;
-    }
-    if (__any(bad) && lane == 0) atomicAdd(err, 1);
-    for (int base = 0; base < nt; base += 64) {
-        const int j = base + lane;
-        if (j < nt) { const int sl = ns[j]; so[j] = sl; to[sl] = j; }
-    }
-}
-__global__ void exchange_pack_kernel(int W, int nt, int d, const double *X, const double *lnL, const double *lp,
-                                     const int32_t *lv_slot, const int32_t *lv_rank, double *send)
-{
-    const int w = (int)blockIdx.x, k = (int)blockIdx.y;
-    const int slot = lv_slot[(size_t)k * W + w];
-    if (slot < 0) return;
-    const size_t r = (size_t)w * nt + slot;
-    double *dst = send + ((size_t)lv_rank[(size_t)k * W + w] * W + w) * (d + 2);
-    for (int i = (int)threadIdx.x; i < d; i += (int)blockDim.x) dst[i] = X[r * d + i];
-    if (threadIdx.x == 0) { dst[d] = lnL[r]; dst[d + 1] = lp[r]; }
-}
-// a block per walker looks through the source GPUs (at most two of them sent a row): a block per (walker, GPU) was 32 768
-// blocks at eight GPUs, nearly all of which found nothing
-__global__ void exchange_apply_kernel(int W, int nt, int d, double *X, double *lnL, double *lp, const int32_t *arr_slot,
-                                      const double *recv, int nranks)
-{
-    const int w = (int)blockIdx.x;
-    for (int q = 0; q < nranks; ++q) {
-        const int slot = arr_slot[(size_t)q * W + w];
-        if (slot < 0) continue;
-        const size_t r = (size_t)w * nt + slot;
-        const double *src = recv + ((size_t)q * W + w) * (d + 2);
-        for (int i = (int)threadIdx.x; i < d; i += (int)blockDim.x) X[r * d + i] = src[i];
-        if (threadIdx.x == 0) { lnL[r] = src[d]; lp[r] = src[d + 1]; }
-    }
-}
-
-
-// A row travels further than to a neighbouring block when the carried state of the sweep wins every pair of a whole
-// block.  Every GPU scans the whole map (identical everywhere), so all of them take the same decision on the transport.
-__global__ void exchange_multihop_kernel(int W, int ntg, int nt, const int32_t *map, int32_t *flag)
-{
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)W * ntg) return;
-    const int j = (int)(idx % ntg);
-    const int hop = map[idx] / nt - j / nt;
-    if (hop > 1 || hop < -1) atomicOr(flag, 1);
-}
-
-int ptmi_exchange_pack(ptmi_handle h, const int32_t *map, double *send)
-{
-    if (!h || !map || !send) return fail(PTMI_EINVAL, "NULL argument");
-    const ptmi_config &c = h->cfg;
-    if (c.ntemps_global % c.ntemps) return fail(PTMI_EINVAL, "the ladder is not a whole number of blocks");
-    const int W = c.nwalkers, nr = c.ntemps_global / c.ntemps;
-    if (int rc = ensure_xint(h)) return rc;
-    int32_t *inv = h->d_xint, *newslot = inv + (size_t)W * c.ntemps_global, *arr = newslot + (size_t)W * c.ntemps;
-    int32_t *lvs = arr + (size_t)nr * W, *lvr = lvs + 2 * (size_t)W, *err = lvr + 2 * (size_t)W;
-    hipLaunchKernelGGL(exchange_plan_kernel, dim3((W + 3) / 4), dim3(256), 0, h->stream, W, c.ntemps, c.ntemps_global, c.temp0, nr,
-                       map, h->buf.slot_of, h->buf.temp_of, (const int32_t *)inv, newslot, arr, lvs, lvr, err);
-    hipLaunchKernelGGL(exchange_pack_kernel, dim3(W, 2), dim3(64), 0, h->stream, W, c.ntemps, c.ndim, (const double *)h->buf.X,
-                       (const double *)h->buf.lnL, (const double *)h->buf.lp, (const int32_t *)lvs, (const int32_t *)lvr, send);
-    if (!h->hop_from_sweep) {                                          // the sweep's write-out did not look (tables beyond the LDS)
-        HIPCHK(hipMemsetAsync(h->d_hop, 0, sizeof(int32_t), h->stream));
-        const long long tot = (long long)W * c.ntemps_global;
-        hipLaunchKernelGGL(exchange_multihop_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, W, c.ntemps_global, c.ntemps,
-                           map, h->d_hop);
-    }
-    h->hop_from_sweep = false;
-    HIPCHK(hipGetLastError());
-    // the flag sets out for the host now, with an event of its own: ptmi_exchange_multihop waits for these four bytes, not for
-    // whatever the caller has queued behind the pack step in the meantime (the neighbour exchange)
-    HIPCHK(hipMemcpyAsync(h->h_hop, h->d_hop, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipEventRecord(h->hop_ev, h->stream));
-    h->hop_pending = true;
-    return PTMI_OK;
-}
-int ptmi_exchange_multihop(ptmi_handle h, int32_t *flag)
-{
-    if (!h || !flag) return fail(PTMI_EINVAL, "NULL argument");
-    *flag = 0;
-    if (!h->d_hop) return PTMI_OK;
-    if (h->hop_pending) {
-        HIPCHK(hipEventSynchronize(h->hop_ev));
-        h->hop_pending = false;
-    }
-    *flag = *h->h_hop;
-    return PTMI_OK;
-}
-int ptmi_exchange_apply(ptmi_handle h, const double *recv)
-{
-    if (!h || !recv) return fail(PTMI_EINVAL, "NULL argument");
-    if (!h->d_xint) return fail(PTMI_EINVAL, "ptmi_exchange_apply without a preceding ptmi_exchange_pack");
-    const ptmi_config &c = h->cfg;
-    const int W = c.nwalkers, nr = c.ntemps_global / c.ntemps;
-    const int32_t *arr = h->d_xint + (size_t)W * c.ntemps_global + (size_t)W * c.ntemps;
-    hipLaunchKernelGGL(exchange_apply_kernel, dim3(W), dim3(64), 0, h->stream, W, c.ntemps, c.ndim, h->buf.X, h->buf.lnL,
-                       h->buf.lp, arr, recv, nr);
-    HIPCHK(hipGetLastError());
-    return PTMI_OK;
-}
-int ptmi_exchange_status(ptmi_handle h, int32_t *violations)
-{
-    if (!h || !violations) return fail(PTMI_EINVAL, "NULL argument");
-    *violations = 0;
-    if (!h->d_xint) return PTMI_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(violations, h->d_xint + xint_count(h->cfg) - 1, sizeof(int32_t), hipMemcpyDeviceToHost));
-    return PTMI_OK;
-}
-
 int ptmi_update_cov(ptmi_handle h, int64_t iter) { return ptmi_update_cov_on(h, iter, nullptr, nullptr, nullptr); }
 
 int ptmi_set_am_buffers(ptmi_handle h, double *AM, double *AMaux, uint64_t *AMflag)
@@ -3536,540 +1972,6 @@ int ptmi_update_cov_on(ptmi_handle hh, int64_t iter, void *stream, const double 
                            nprev + nb - 1.0);
     }
     HIPCHK(hipGetLastError());
-    return PTMI_OK;
-}
-
-int ptmi_eig_jacobi(ptmi_handle h)
-{
-    if (!h) return fail(PTMI_EINVAL, "NULL handle");
-    const ptmi_config &c = h->cfg;
-    if (!h->buf.cov || !h->buf.Ut || !h->buf.S) return fail(PTMI_EINVAL, "cov / Ut / S buffers missing");
-    if (c.ngroups > 1) return fail(PTMI_EUNSUPPORTED, "the device eigensolver factorizes the full covariance (no parameter groups)");
-    const int d = c.ndim;
-    const size_t lds = sizeof(double) * 2 * (size_t)d * d;
-    if (lds > 160 * 1024 || d > 101) return fail(PTMI_EUNSUPPORTED, "the device eigensolver keeps two %d x %d tables in LDS: ndim <= 101", d, d);
-    if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)eig_jacobi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int nmat = c.cov_per_walker ? c.nwalkers : 1;
-    hipLaunchKernelGGL(eig_jacobi_kernel, dim3(nmat), dim3(JAC_THREADS), lds, h->stream, (const double *)h->buf.cov, h->buf.Ut, h->buf.S,
-                       d, d * d, d);
-    HIPCHK(hipGetLastError());
-    return PTMI_OK;
-}
-
-// nmat symmetric matrices of order n, packed [nmat][n][n] -> eigenvectors as rows [nmat][n][n], eigenvalues [nmat][n] (see ptmi_eig_ql)
-static int eig_ql_run(ptmi_engine *h, int n, int nmat, const double *cov, double *Ut, double *S)
-{
-    const ptmi_config &c = h->cfg;
-    const int d = n, dmax = c.ndim;
-    const size_t lds = sizeof(double) * ((((size_t)d * d + 1) & ~(size_t)1) + 2 * (size_t)d);
-    if (lds > 160 * 1024 || d > 128) return fail(PTMI_EUNSUPPORTED, "the QL eigensolver keeps the %d x %d matrix in LDS: ndim <= 128", d, d);
-    const bool split = ptmi_env("PTMI_QL_SPLIT", nmat >= 64) != 0;    // 1 / 0 forces the three-kernel / the one-kernel form (a test hook)
-    if (split) {
-        // many matrices: reduce -> the scalar chains of all of them at once -> apply (see eig_ql_chain_kernel)
-        const int cap = 3 * d * d, capit = 8 * d;
-        if (!h->d_ql_scr) {                                             // sized for the full order (a parameter group's matrices are smaller)
-            const int capm = 3 * dmax * dmax, capitm = 8 * dmax;
-            const size_t bytes = sizeof(double) * (size_t)nmat * ((size_t)dmax * dmax + 2 * (size_t)dmax + (size_t)dmax + 2 * (size_t)capm) +
-                                 sizeof(int32_t) * (size_t)nmat * (2 * (size_t)capitm + 2) + 256;
-            HIPCHK(hipMalloc((void **)&h->d_ql_scr, bytes));
-        }
-        QlScratch q;
-        char *pb = (char *)h->d_ql_scr;
-        auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-        q.z = (double *)pb; pb += up16(sizeof(double) * (size_t)nmat * d * d);
-        q.de = (qls_d2 *)pb; pb += sizeof(double) * 2 * (size_t)nmat * d;
-        q.rot = (qls_d2 *)pb; pb += sizeof(double) * 2 * (size_t)nmat * cap;
-        q.ev = (double *)pb; pb += up16(sizeof(double) * (size_t)nmat * d);
-        q.hdr = (int32_t *)pb; pb += sizeof(int32_t) * 2 * (size_t)nmat * capit;
-        q.cnt = (int32_t *)pb;
-        q.cap = cap; q.capit = capit;
-        if (lds > 64 * 1024) {
-            HIPCHK(hipFuncSetAttribute((const void *)eig_ql_reduce_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(hipFuncSetAttribute((const void *)eig_ql_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        hipLaunchKernelGGL(eig_ql_reduce_kernel, dim3(nmat), dim3(QLR_THREADS), lds, h->stream, cov, d, q);
-        hipLaunchKernelGGL(eig_ql_chain_kernel, dim3(nmat), dim3(64), sizeof(double) * 2 * (size_t)d, h->stream, d, q);
-        const bool regs = d <= QLA_N;
-        if (regs)
-            hipLaunchKernelGGL(eig_ql_apply_reg_kernel, dim3(nmat), dim3(128), 0, h->stream, Ut, S, d, d * d, d, (const double *)q.z,
-                               (const double *)q.ev, (const qls_d2 *)q.rot, (const int32_t *)q.hdr, (const int32_t *)q.cnt, cap, capit);
-        hipLaunchKernelGGL(eig_ql_apply_kernel, dim3(nmat), dim3(QL_THREADS), lds, h->stream, Ut, S, d, d * d, d, q, regs ? 1 : 0);
-        HIPCHK(hipGetLastError());
-        return PTMI_OK;
-    }
-    if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)eig_ql_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(eig_ql_kernel, dim3(nmat), dim3(QL_THREADS), lds, h->stream, cov, Ut, S, d, d * d, d, (int32_t *)nullptr);
-    HIPCHK(hipGetLastError());
-    return PTMI_OK;
-}
-
-// Parameter groups (PT:129-145, 797-803: one SVD per group's block of the covariance): the group's rows and columns, in ascending
-// parameter order, packed into an m x m matrix per walker ...
-__global__ __launch_bounds__(256) void group_gather_kernel(const double *cov, const double *gmask, int d, int m, double *sub)
-{
-    __shared__ int idx[128];
-    const double *mk = gmask;                                            // [d] membership of this group
-    if (threadIdx.x == 0) {
-        int k = 0;
-        for (int i = 0; i < d && k < 128; ++i) if (mk[i] != 0.0) idx[k++] = i;
-    }
-    __syncthreads();
-    const double *cw = cov + (size_t)blockIdx.x * d * d;
-    double *sw = sub + (size_t)blockIdx.x * m * m;
-    for (int t = (int)threadIdx.x; t < m * m; t += 256) sw[t] = cw[(size_t)idx[t / m] * d + idx[t % m]];
-}
-// ... and its eigenvectors embedded in the full space, one per row of the group's table (zero outside the group, zero rows beyond
-// the group's size), the eigenvalues padded with zeros: the layout propose() reads (Ut[Wc][Ng][d][d], S[Wc][Ng][d])
-__global__ __launch_bounds__(256) void group_embed_kernel(const double *usub, const double *ssub, const double *gmask, int d, int m, int ng, int gi,
-                                                          double *Ut, double *S)
-{
-    __shared__ int pos[128];                                             // position of parameter i inside the group, or -1
-    if (threadIdx.x == 0) {
-        int k = 0;
-        for (int i = 0; i < d; ++i) pos[i] = gmask[i] != 0.0 ? k++ : -1;
-    }
-    __syncthreads();
-    const double *uw = usub + (size_t)blockIdx.x * m * m, *sw = ssub + (size_t)blockIdx.x * m;
-    double *Uo = Ut + ((size_t)blockIdx.x * ng + gi) * d * d, *So = S + ((size_t)blockIdx.x * ng + gi) * d;
-    for (int t = (int)threadIdx.x; t < d * d; t += 256) {
-        const int k = t / d, i = t % d;
-        Uo[t] = (k < m && pos[i] >= 0) ? uw[(size_t)k * m + pos[i]] : 0.0;
-    }
-    for (int k = (int)threadIdx.x; k < d; k += 256) So[k] = k < m ? sw[k] : 0.0;
-}
-
-int ptmi_eig_ql(ptmi_handle h)
-{
-    if (!h) return fail(PTMI_EINVAL, "NULL handle");
-    const ptmi_config &c = h->cfg;
-    if (!h->buf.cov || !h->buf.Ut || !h->buf.S) return fail(PTMI_EINVAL, "cov / Ut / S buffers missing");
-    const int d = c.ndim, nmat = c.cov_per_walker ? c.nwalkers : 1;
-    if (c.ngroups <= 1) return eig_ql_run(h, d, nmat, (const double *)h->buf.cov, h->buf.Ut, h->buf.S);
-    if (d > 128) return fail(PTMI_EUNSUPPORTED, "the QL eigensolver keeps a matrix in LDS: ndim <= 128");
-    // one factorization per parameter group, as the reference's loop over self.groups (PT:797-803)
-    if (!h->d_qlg_scr) HIPCHK(hipMalloc((void **)&h->d_qlg_scr, sizeof(double) * (size_t)nmat * (2 * (size_t)d * d + d)));
-    double *sub = (double *)h->d_qlg_scr, *usub = sub + (size_t)nmat * d * d, *ssub = usub + (size_t)nmat * d * d;
-    for (int gi = 0; gi < c.ngroups; ++gi) {
-        const int m = h->gsize_host[gi];
-        const double *mk = h->d_gmask + (size_t)gi * d;
-        hipLaunchKernelGGL(group_gather_kernel, dim3(nmat), dim3(256), 0, h->stream, (const double *)h->buf.cov, mk, d, m, sub);
-        if (int rc = eig_ql_run(h, m, nmat, (const double *)sub, usub, ssub)) return rc;
-        hipLaunchKernelGGL(group_embed_kernel, dim3(nmat), dim3(256), 0, h->stream, (const double *)usub, (const double *)ssub, mk, d, m, c.ngroups, gi,
-                           h->buf.Ut, h->buf.S);
-    }
-    HIPCHK(hipGetLastError());
-    return PTMI_OK;
-}
-
-// ptmi_eig_ql on the caller's stream, from / into the caller's buffers: the engine's eig_lag with per-walker covariances -- the
-// factorization of thousands of small matrices (chains of dependent rotations: little of the GPU each) runs BESIDE the step launches of
-// the next covariance period instead of between two of them.  One call at a time (the scratch is the handle's).
-int ptmi_eig_ql_from(ptmi_handle h, void *stream, const double *cov_in, double *Ut_out, double *S_out)
-{
-    if (!h) return fail(PTMI_EINVAL, "NULL handle");
-    const ptmi_config &c = h->cfg;
-    const double *cov = cov_in ? cov_in : (const double *)h->buf.cov;
-    double *Uo = Ut_out ? Ut_out : h->buf.Ut, *So = S_out ? S_out : h->buf.S;
-    if (!cov || !Uo || !So) return fail(PTMI_EINVAL, "cov / Ut / S buffers missing");
-    if (c.ngroups > 1) return fail(PTMI_EUNSUPPORTED, "ptmi_eig_ql_from: one parameter group (use ptmi_eig_ql)");
-    ptmi_engine view = *h;                                               // eig_ql_run reads the stream, the configuration and the scratch pointer
-    if (stream) view.stream = (hipStream_t)stream;
-    const int rc = eig_ql_run(&view, c.ndim, c.cov_per_walker ? c.nwalkers : 1, cov, Uo, So);
-    h->d_ql_scr = view.d_ql_scr;                                         // (made by the first call)
-    return rc;
-}
-
-// ---------------------------------------------------------------- one large matrix: tridiagonalization in one kernel
-// eig_mode "sytrd" (ptmi_eig_sytrd; ndim <= 1024, one pooled covariance).  The ROCm library's symmetric eigensolver spends two thirds
-// of its time reducing the matrix to tridiagonal form in some 7000 launches of one-block kernels (1000 x 1000: 25 of 35 ms of kernel
-// time, 3 us each).  Here that step is ONE kernel: the matrix lives in the LDS of its blocks (block b owns the full columns
-// b, b + NB, ...: 64 KB of 160 at 1000 x 1000 over 128 blocks), a Householder step is
-//   the owner of column k forms v (its own LDS)                                         -> v to all      [grid barrier]
-//   every block: p_j = tau (column j . v) for ITS columns (A symmetric: column j is row j)  -> p to all      [grid barrier]
-//   every block: w = p - (tau/2 p.v) v, its columns -= v w_j + w v_j
-// -- no reduction across blocks, two barriers per column (a few microseconds each on an atomic counter).  Output in LAPACK's
-// dsytrd format (uplo = lower: d, e, tau, the reflectors below the subdiagonal), from which the divide-and-conquer solver for the
-// tridiagonal matrix and its back-transformation through the reflectors (dc_solve) take it.
-struct SytrdArgs {
-    double *A;             // [n][n] column-major = row-major (symmetric in); out: the reflectors
-    double *D, *E, *tau;   // [n], [n - 1], [n - 1]
-    double *vbuf;          // [2][n + 2]: column m as its owner holds it before the update (by parity of m)
-    double *pbuf;          // [2][n]: the products p_j (by parity of m)
-    unsigned *bar;
-    int n;
-};
-#ifndef PTMI_SY_THREADS
-#define PTMI_SY_THREADS 256
-#endif
-constexpr int SY_THREADS = PTMI_SY_THREADS, SY_NW = SY_THREADS / 64, SY_CMAX = 16, SY_PT = 1024 / SY_THREADS;       // SY_PT: elements of a vector per thread (n <= 1024)
-// exchanged data goes through agent-scope relaxed atomics (write-through stores, loads past the caches of the other XCDs): no
-// cache write-back / invalidation beside the barrier's own counter
-__device__ __forceinline__ void sy_grid_sync(unsigned *bar, unsigned &target, unsigned nb)
-{
-    // every thread's exchanged stores must be ACKNOWLEDGED before the counter moves.  __syncthreads alone does not wait for them (a
-    // workgroup-scope release needs no vmcnt wait on this part: the CU's L1 is the block's own), and the counter's increment is
-    // relaxed: beside an idle GPU the stores happened to land first; beside step launches that saturate the L2 / MALL path (the wide
-    // kernels of round 5) another block could pass the barrier and read a vector's old contents -- whole runs differed from
-    // repeat to repeat (tools/repeat_check.py).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-#ifdef PTMI_SY_NOBAR
-    return;
-#endif
-    if (threadIdx.x == 0) {
-        target += nb;
-        // RELAXED: a release / acquire at agent scope writes back / invalidates the XCD's whole L2 at every barrier -- under the step
-        // kernel running beside this one (its table rows live there): launches of 3.2 ms instead of 2.5.  The exchanged vectors
-        // need neither: they are written and read with agent-scope atomics themselves, and __syncthreads has waited for the stores.
-        __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifndef PTMI_SY_SLEEP
-#define PTMI_SY_SLEEP 8
-#endif
-        while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) __builtin_amdgcn_s_sleep(PTMI_SY_SLEEP);
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ double sy_load(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void sy_store(double *p, double x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// elements lo .. n - 1 of an exchanged vector into LDS: every load of a thread in flight at once
-__device__ __forceinline__ void sy_fetch(const double *src, double *dst, int lo, int n)
-{
-    double tmp[SY_PT];
-#pragma unroll
-    for (int u = 0; u < SY_PT; ++u) { const int i = lo + (int)threadIdx.x + u * SY_THREADS; tmp[u] = i < n ? sy_load(src + i) : 0.0; }
-#pragma unroll
-    for (int u = 0; u < SY_PT; ++u) { const int i = lo + (int)threadIdx.x + u * SY_THREADS; if (i < n) dst[i] = tmp[u]; }
-}
-__device__ __forceinline__ double sy_block_sum(double x, double *red)      // red: [SY_NW] doubles of LDS
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < SY_THREADS / 64; ++w) s += red[w];
-    return s;
-}
-// 256 threads and at most 64 registers: a wave per SIMD that fits beside FOUR waves of the config-4 step kernel (112 registers each);
-// with 512 threads of 72 registers the step kernel lost a wave per SIMD on every CU that holds a block of this one (launches 3.1 ms
-// against 2.5)
-__global__ __launch_bounds__(SY_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void sytrd_lds_kernel(SytrdArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) double sy[];
-    const int n = a.n, nb = (int)gridDim.x, b = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int ncol = b < n ? (n - 1 - b) / nb + 1 : 0;               // owned columns b, b + nb, ...
-    double *col = sy;                                                // [ncol][n]
-    double *v = sy + (size_t)SY_CMAX * n, *w = v + n, *xr = w + n, *red = xr + n;    // [n] each, [1 + SY_CMAX][SY_NW]
-    unsigned target = 0;
-    for (int c = 0; c < ncol; ++c)
-        for (int i = t; i < n; i += SY_THREADS) col[(size_t)c * n + i] = a.A[(size_t)(b + c * nb) * n + i];
-    for (int i = t; i < n; i += SY_THREADS) { v[i] = 0.0; w[i] = 0.0; }
-    double tau = 0.0;                                                // of the reflector in v (m - 1)
-    __syncthreads();
-    // Iteration m: the update by reflector m - 1 (in v, known to every block) and the generation of reflector m, with ONE grid
-    // barrier: beside its p_j every block would need column m after the update to form the next reflector -- the column's owner
-    // sends it as it is BEFORE the update, and every block applies the update to its copy and forms v_m for itself (the same
-    // operations on the same values in every block).
-    for (int m = 0; m + 1 < n; ++m) {
-        const int par = m & 1;
-        double *pb = a.pbuf + (size_t)par * n, *rb = a.vbuf + (size_t)par * (n + 2);
-        const int c0 = m <= b ? 0 : (m - b + nb - 1) / nb;             // this block's columns j >= m: those from c0 on
-        if (m >= 1 && tau != 0.0) {
-            // a wave per column (columns wave, wave + SY_NW, ...: SY_CMAX / SY_NW accumulators per lane, reduced inside the wave,
-            // no barrier): with every thread on every column the 16 accumulators' 96 shuffle steps, an LDS exchange between the
-            // waves and a barrier made this the longest part of a step (9 of 12.5 us)
-            constexpr int CW = SY_CMAX / SY_NW;
-            const int wv = t >> 6, ln = t & 63;
-            double acc[CW];
-#pragma unroll
-            for (int q = 0; q < CW; ++q) acc[q] = 0.0;
-            for (int i = m + ln; i < n; i += 64) {
-                const double vi = v[i];
-#pragma unroll
-                for (int q = 0; q < CW; ++q) {
-                    const int c = wv + q * SY_NW;
-                    if (c >= c0 && c < ncol) acc[q] = __builtin_fma(col[(size_t)c * n + i], vi, acc[q]);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < CW; ++q) {
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
-                const int c = wv + q * SY_NW;
-                if (ln == 0 && c >= c0 && c < ncol) sy_store(pb + b + c * nb, tau * acc[q]);
-            }
-        }
-        if (b == m % nb) {
-            const double *x = col + (size_t)(m / nb) * n;
-            for (int i = m + 1 + t; i < n; i += SY_THREADS) sy_store(rb + i, x[i]);
-        }
-        sy_grid_sync(a.bar, target, (unsigned)nb);
-        if (m >= 1 && tau != 0.0) {
-            // both vectors' loads in flight at once (a round trip to memory each)
-            double tx[SY_PT], tp[SY_PT];
-#pragma unroll
-            for (int u = 0; u < SY_PT; ++u) {
-                const int i = m + t + u * SY_THREADS;
-                tx[u] = (i > m && i < n) ? sy_load(rb + i) : 0.0;
-                tp[u] = i < n ? sy_load(pb + i) : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < SY_PT; ++u) {
-                const int i = m + t + u * SY_THREADS;
-                if (i > m && i < n) xr[i] = tx[u];
-                if (i < n) w[i] = tp[u];
-            }
-            __syncthreads();
-            double pv = 0.0;
-            for (int i = m + t; i < n; i += SY_THREADS) pv = __builtin_fma(w[i], v[i], pv);
-            const double ptv = sy_block_sum(pv, red);
-            const double al = -0.5 * tau * ptv;
-            for (int i = m + t; i < n; i += SY_THREADS) w[i] = __builtin_fma(al, v[i], w[i]);
-            __syncthreads();
-            for (int c = c0; c < ncol; ++c) {
-                const int j = b + c * nb;
-                const double vj = v[j], wj = w[j];
-                double *cj = col + (size_t)c * n;
-                for (int i = m + t; i < n; i += SY_THREADS) cj[i] -= v[i] * wj + w[i] * vj;
-            }
-            const double vm = v[m], wm = w[m];
-            for (int i = m + 1 + t; i < n; i += SY_THREADS) xr[i] -= v[i] * wm + w[i] * vm;       // column m as its owner now has it
-        } else {
-            sy_fetch(rb, xr, m + 1, n);
-        }
-        __syncthreads();
-        // reflector m from xr[m + 1 .. n - 1] (dlarfg)
-        double ss = 0.0;
-        for (int i = m + 2 + t; i < n; i += SY_THREADS) ss = __builtin_fma(xr[i], xr[i], ss);
-        const double xn2 = sy_block_sum(ss, red);
-        const double alpha = xr[m + 1];
-        double beta = alpha, scal = 0.0;
-        tau = 0.0;
-        if (xn2 != 0.0) {
-            const double nrm = det_sqrt(alpha * alpha + xn2);
-            beta = alpha >= 0.0 ? -nrm : nrm;
-            tau = (beta - alpha) / beta;
-            scal = 1.0 / (alpha - beta);
-        }
-        __syncthreads();                                              // every thread has read alpha
-        for (int i = m + 2 + t; i < n; i += SY_THREADS) v[i] = xr[i] * scal;
-        if (t == 0) v[m + 1] = 1.0;
-        if (b == m % nb) {
-            for (int i = m + 2 + t; i < n; i += SY_THREADS) a.A[(size_t)m * n + i] = xr[i] * scal;      // LAPACK's storage of reflector m
-            if (t == 0) {
-                a.D[m] = col[(size_t)(m / nb) * n + m];
-                a.E[m] = beta;
-                a.tau[m] = tau;
-            }
-        }
-        __syncthreads();
-    }
-    if ((n - 1) % nb == b && t == 0) a.D[n - 1] = col[(size_t)((n - 1) / nb) * n + (n - 1)];
-}
-// eigenvalues ascending (the library's order) -> by decreasing size in absolute value, the eigenvectors (rows of C) along
-__global__ __launch_bounds__(256) void eig_sort_rows_kernel(const double *D, const double *Cm, int n, double *Ut, double *S)
-{
-    __shared__ int rank_s;
-    const int k = (int)blockIdx.x;
-    if (threadIdx.x == 0) {
-        const double mine = __builtin_fabs(D[k]);
-        int rank = 0;
-        for (int j = 0; j < n; ++j) { const double o = __builtin_fabs(D[j]); rank += (o > mine) || (o == mine && j > k); }
-        rank_s = rank;
-        S[rank] = mine;
-    }
-    __syncthreads();
-    const int rank = rank_s;
-    for (int i = (int)threadIdx.x; i < n; i += 256) Ut[(size_t)rank * n + i] = Cm[(size_t)k * n + i];
-}
-#include "ptmi_dc.inc.h"
-
-// host side of the divide-and-conquer solver: the tree of a matrix order (all leaves at one depth, so that every level merges every
-// block and the two vector buffers alternate), built once per engine
-struct DcPlan {
-    int n = 0, nlevels = 0, nleaves = 0, nnodes = 0;
-    std::vector<int> lvl_off, lvl_cnt, lvl_nmax;       // per level (bottom-up): first node, nodes, largest node
-    dc::Node *d_nodes = nullptr;                       // all merges, level by level
-    dc::Leaf *d_leaves = nullptr;
-    char *scr = nullptr;                               // two vector buffers, U, the per-row arrays
-};
-static int dc_plan_get(ptmi_engine *h, int n, DcPlan **out)
-{
-    if (h->dc_plan) { *out = (DcPlan *)h->dc_plan; return PTMI_OK; }
-    DcPlan *P = new (std::nothrow) DcPlan();
-    if (!P) return fail(PTMI_EHIP, "out of memory");
-    int depth = 0;
-    while (((n + (1 << depth) - 1) >> depth) > dc::LEAF) ++depth;
-    std::vector<std::vector<dc::Node>> by_depth(depth);
-    std::vector<dc::Leaf> leaves;
-    struct Rec { static void go(int off, int nn, int dep, int depth, std::vector<std::vector<dc::Node>> &bd, std::vector<dc::Leaf> &lv) {
-        if (dep == depth) { lv.push_back({off, nn}); return; }
-        const int n1 = nn / 2;
-        bd[dep].push_back({off, nn, n1});
-        go(off, n1, dep + 1, depth, bd, lv);
-        go(off + n1, nn - n1, dep + 1, depth, bd, lv);
-    } };
-    Rec::go(0, n, 0, depth, by_depth, leaves);
-    std::vector<dc::Node> all;
-    for (int dep = depth - 1; dep >= 0; --dep) {       // bottom-up
-        P->lvl_off.push_back((int)all.size());
-        P->lvl_cnt.push_back((int)by_depth[dep].size());
-        int mx = 0;
-        for (const dc::Node &nd : by_depth[dep]) { all.push_back(nd); mx = nd.n > mx ? nd.n : mx; }
-        P->lvl_nmax.push_back(mx);
-    }
-    P->n = n; P->nlevels = depth; P->nleaves = (int)leaves.size(); P->nnodes = (int)all.size();
-    const size_t nn = (size_t)n * n;
-    const size_t bytes = sizeof(double) * (3 * nn + 12 * (size_t)n + 2 * all.size() + 64) + sizeof(int) * (6 * (size_t)n + 2 * all.size() + 64);
-    hipError_t e = hipMalloc((void **)&P->scr, bytes);
-    if (e == hipSuccess && !all.empty()) e = hipMalloc((void **)&P->d_nodes, sizeof(dc::Node) * all.size());
-    if (e == hipSuccess) e = hipMalloc((void **)&P->d_leaves, sizeof(dc::Leaf) * leaves.size());
-    if (e == hipSuccess && !all.empty()) e = hipMemcpy(P->d_nodes, all.data(), sizeof(dc::Node) * all.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(P->d_leaves, leaves.data(), sizeof(dc::Leaf) * leaves.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(P->scr); (void)hipFree(P->d_nodes); (void)hipFree(P->d_leaves);
-        delete P;
-        return fail(PTMI_EHIP, "divide-and-conquer scratch: %s", hipGetErrorString(e));
-    }
-    h->dc_plan = P;
-    *out = P;
-    return PTMI_OK;
-}
-static void dc_plan_free(ptmi_engine *h)
-{
-    DcPlan *P = (DcPlan *)h->dc_plan;
-    if (!P) return;
-    (void)hipFree(P->scr); (void)hipFree(P->d_nodes); (void)hipFree(P->d_leaves);
-    delete P;
-    h->dc_plan = nullptr;
-}
-// eigenvalues (ascending, *Dres) and eigenvectors (vector-major, *Zres) of the tridiagonal matrix (D, E), back-transformed through the
-// reflectors (A, tau) of the reduction; everything queued on st
-static int dc_solve(ptmi_engine *h, hipStream_t st, int n, const double *D, const double *E, const double *A, const double *tau,
-                    const double **Dres, const double **Zres, int *info /* device: zeroed by the caller; a leaf that did not converge sets it */)
-{
-    DcPlan *P = nullptr;
-    if (int rc = dc_plan_get(h, n, &P)) return rc;
-    const size_t nn = (size_t)n * n;
-    double *p = (double *)P->scr;
-    double *Qa = p; p += nn;
-    double *Qb = p; p += nn;
-    dc::Args a;
-    memset(&a, 0, sizeof(a));
-    a.n = n;
-    a.U = p; p += nn;
-    a.d = p; p += n;
-    a.e = p; p += n;
-    double *Da = p; p += n;
-    double *Db = p; p += n;
-    a.dk = p; p += n; a.zk = p; p += n; a.Ddefl = p; p += n; a.mu = p; p += n; a.lam = p; p += n; a.zh = p; p += n;
-    a.rho = p; p += P->nnodes + 8;
-    int *q = (int *)p;
-    a.keepv = q; q += n; a.deflv = q; q += n; a.org = q; q += n; a.rankk = q; q += n; a.rankd = q; q += n;
-    a.cnt = q;
-    HIPCHK(hipMemcpyAsync(a.d, D, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(a.e, E, sizeof(double) * (n - 1), hipMemcpyDeviceToDevice, st));
-    if (P->nnodes) hipLaunchKernelGGL(dc::split_kernel, dim3((P->nnodes + 63) / 64), dim3(64), 0, st, (const dc::Node *)P->d_nodes, P->nnodes, a.d, (const double *)a.e);
-    HIPCHK(hipMemsetAsync(Qa, 0, sizeof(double) * nn, st));
-    hipLaunchKernelGGL(dc::leaf_kernel, dim3(P->nleaves), dim3(64), 0, st, (const dc::Leaf *)P->d_leaves, n, (const double *)a.d, (const double *)a.e, Da, Qa, info);
-    double *Qin = Qa, *Qout = Qb, *Din = Da, *Dout = Db;
-    for (int lv = 0; lv < P->nlevels; ++lv) {
-        const int cnt = P->lvl_cnt[lv], nmax = P->lvl_nmax[lv];
-        a.nodes = P->d_nodes + P->lvl_off[lv];
-        a.Qin = Qin; a.Qout = Qout; a.Din = Din; a.Dout = Dout;
-        HIPCHK(hipMemsetAsync(Qout, 0, sizeof(double) * nn, st));
-        hipLaunchKernelGGL(dc::prep_kernel, dim3(cnt), dim3(dc::PREP_THREADS), 0, st, a);
-        hipLaunchKernelGGL(dc::secular_kernel, dim3((nmax + 3) / 4, cnt), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(dc::zhat_kernel, dim3((nmax + 3) / 4, cnt), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(dc::vectors_kernel, dim3((nmax + 3) / 4, cnt), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(dc::rank_kernel, dim3(cnt), dim3(1024), 0, st, a);
-        hipLaunchKernelGGL(dc::gemm_kernel, dim3((nmax + 63) / 64, (nmax + 63) / 64, cnt), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(dc::copy_deflated_kernel, dim3(nmax, cnt), dim3(256), 0, st, a);
-        double *tq = Qin; Qin = Qout; Qout = tq;
-        double *td = Din; Din = Dout; Dout = td;
-    }
-    hipLaunchKernelGGL(dc::backtransform_kernel, dim3((n + 4 * dc::VPW - 1) / (4 * dc::VPW)), dim3(256), 0, st, A, tau, n, Qin);
-    HIPCHK(hipGetLastError());
-    *Dres = Din;
-    *Zres = Qin;
-    return PTMI_OK;
-}
-
-int ptmi_eig_sytrd(ptmi_handle h, void *stream, double *Ut_out, double *S_out) { return ptmi_eig_sytrd_from(h, stream, nullptr, Ut_out, S_out); }
-
-int ptmi_eig_sytrd_from(ptmi_handle h, void *stream, const double *cov_in, double *Ut_out, double *S_out)
-{
-    if (!h) return fail(PTMI_EINVAL, "NULL handle");
-    const ptmi_config &c = h->cfg;
-    if (!cov_in) cov_in = h->buf.cov;
-    if (!cov_in) return fail(PTMI_EINVAL, "cov buffer missing");
-    if (c.cov_per_walker || c.ngroups > 1) return fail(PTMI_EUNSUPPORTED, "ptmi_eig_sytrd factorizes ONE pooled covariance (no parameter groups)");
-    const int n = c.ndim;
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    double *Uo = Ut_out ? Ut_out : h->buf.Ut, *So = S_out ? S_out : h->buf.S;
-    if (!Uo || !So) return fail(PTMI_EINVAL, "Ut / S buffers missing");
-    int dev = 0, ncu = 0;
-    HIPCHK(hipGetDevice(&dev));
-    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    int nb = ncu / 4 > 0 ? ncu / 4 : 1;                             // 64 blocks: the barrier's cost grows with them (21.1 ms at 64, 23.1 at 128, 27.8 at 256)
-    while ((n + nb - 1) / nb > SY_CMAX && nb < ncu) nb *= 2;
-    if (nb > ncu) nb = ncu;
-    if (nb > n) nb = n;
-    if (n < 3 || (n + nb - 1) / nb > SY_CMAX) return fail(PTMI_EUNSUPPORTED, "ptmi_eig_sytrd: 3 <= ndim <= %d on this device", SY_CMAX * nb);
-    int cpb = (n + nb - 1) / nb;                                    // columns per block
-    const size_t lds = sizeof(double) * ((size_t)(SY_CMAX + 3) * n + (size_t)(1 + SY_CMAX) * SY_NW);
-    if (lds > 160 * 1024 || n > 1024) return fail(PTMI_EUNSUPPORTED, "ptmi_eig_sytrd: ndim = %d does not fit the LDS", n);
-    (void)cpb;
-    const size_t nn = (size_t)n * n;
-    if (!h->d_sy_scr) HIPCHK(hipMalloc(&h->d_sy_scr, sizeof(double) * (nn + 8 * (size_t)n + 64) + 256));
-    double *A = (double *)h->d_sy_scr, *D = A + nn, *E = D + n, *tau = E + n, *vbuf = tau + n, *pbuf = vbuf + 2 * (n + 2);
-    unsigned *bar = (unsigned *)(pbuf + 2 * n + 2);
-    int *info = (int *)(bar + 4);
-    HIPCHK(hipMemcpyAsync(A, cov_in, sizeof(double) * nn, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemsetAsync(bar, 0, 32, st));
-    HIPCHK(hipFuncSetAttribute((const void *)sytrd_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SytrdArgs sa = {A, D, E, tau, vbuf, pbuf, bar, n};
-    // The kernel's grid barrier needs all nb blocks resident at once.  One block per CU always fits an otherwise free CU (checked
-    // here against the occupancy the runtime computes); beside persistent step kernels the blocks take the CUs' remaining LDS as it
-    // is (the step kernel leaves 78 KB, a block needs up to 160: such a block starts when its CU's step block ends, and every step
-    // block ends).  What could deadlock is a SECOND factorization of another engine on the same device holding part of the CUs with
-    // blocks that spin: factorizations of one device are therefore serialized by an event chain across engines and streams.
-    int occ = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)sytrd_lds_kernel, SY_THREADS, lds));
-    if (occ < 1 || (long long)occ * ncu < nb)
-        return fail(PTMI_EUNSUPPORTED, "ptmi_eig_sytrd: %d blocks of %zu B of LDS cannot be resident at once on %d CUs", nb, lds, ncu);
-    {
-        static std::mutex mu;
-        static hipEvent_t last[64] = {};
-        std::lock_guard<std::mutex> lk(mu);
-        const int di = dev & 63;
-        if (last[di]) HIPCHK(hipStreamWaitEvent(st, last[di], 0));
-        else HIPCHK(hipEventCreateWithFlags(&last[di], hipEventDisableTiming));
-        hipLaunchKernelGGL(sytrd_lds_kernel, dim3(nb), dim3(SY_THREADS), lds, st, sa);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(last[di], st));
-    }
-    // the tridiagonal matrix's eigenvectors by the engine's own divide-and-conquer kernels, back-transformed through the reflectors
-    const double *Dres = nullptr, *Zres = nullptr;
-    if (int rc = dc_solve(h, st, n, D, E, A, tau, &Dres, &Zres, info)) return rc;
-    hipLaunchKernelGGL(eig_sort_rows_kernel, dim3(n), dim3(256), 0, st, Dres, Zres, n, Uo, So);
-    HIPCHK(hipGetLastError());
-    // the convergence word (a leaf's QL iteration: dc::leaf_kernel) follows the result to the host on the same stream
-    // (ptmi_eig_sytrd_info reads the last one that arrived)
-    if (!h->h_sy_info) {
-        HIPCHK(hipHostMalloc((void **)&h->h_sy_info, 2 * sizeof(int32_t)));
-        h->h_sy_info[0] = 0; h->h_sy_info[1] = 0;
-    }
-    HIPCHK(hipMemcpyAsync(h->h_sy_info, info, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    return PTMI_OK;
-}
-
-int ptmi_eig_sytrd_info(ptmi_handle h, int32_t *info)
-{
-    if (!h || !info) return fail(PTMI_EINVAL, "NULL argument");
-    *info = h->h_sy_info ? h->h_sy_info[0] : 0;
     return PTMI_OK;
 }
 

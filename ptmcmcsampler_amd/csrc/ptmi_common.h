@@ -183,7 +183,7 @@ struct ptmi_engine {
     hipEvent_t side_go, side_done;
     double *d_utpad;             // zero-padded copy of the pooled eigenvector table for the 16- / 64-lane shapes (KArgs::UtPad)
     void *d_sy_scr;              // ptmi_eig_sytrd: the working matrix, d / e / tau, the eigenvectors, the exchange vectors and the barrier word
-    void *dc_plan;               // ... the divide-and-conquer solver's tree and scratch (DcPlan, ptmi_abi.hip)
+    void *dc_plan;               // ... the divide-and-conquer solver's tree and scratch (DcPlan, ptmi_eig.hip)
     int32_t *h_sy_info;          // pinned: the divide-and-conquer solver's convergence word of the last factorization that has finished
     void *d_qlg_scr;             // ptmi_eig_ql with parameter groups: a group's packed matrices, their eigenvectors and eigenvalues
     int32_t *gsize_host;         // [Ng] parameters per group (host copy of d_gsize)
@@ -209,6 +209,10 @@ struct ptmi_engine {
 enum { PTMI_GJ_NONE = 0, PTMI_GJ_PENDING = 1 /* proposals made, ptmi_gj_begin not yet called */, PTMI_GJ_ROUNDS = 2, PTMI_GJ_DONE = 3 };
 // the split path's refusals for gradient jumps (0: served; else the code, with the message set)
 int ptmi_gj_split_check(const ptmi_engine *h);
+// eigensolvers (ptmi_eig.hip): frees h->dc_plan, for ptmi_destroy
+void ptmi_dc_plan_free(ptmi_engine *h);
+// swap (ptmi_swap.hip): bytes of a record of d_pre (SwapPre), for ptmi_create
+constexpr size_t PTMI_SWAP_PRE_BYTES = 48;
 
 
 // split path on contiguous rows (ptmi_split.hip): does the handle's configuration run there; mode 0 propose(iter0), 1 accept(iter0),

@@ -15,6 +15,7 @@ import os
 import numpy as np
 
 from . import _lib
+from ._build import _usable_cores
 from .ladder import temperature_ladder
 
 
@@ -42,23 +43,6 @@ def _blas_threads(n):
 
 def _blas_single_thread():
     return _blas_threads(1)
-
-
-def _usable_cores():
-    """Visible CPUs, capped by the affinity mask and the cgroup CPU quota."""
-    import os
-    n = os.cpu_count() or 1
-    try:
-        n = min(n, len(os.sched_getaffinity(0)))
-    except AttributeError:
-        pass
-    try:
-        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
-        if quota != "max":
-            n = min(n, max(1, int(int(quota) / int(period))))
-    except (OSError, ValueError):
-        pass
-    return n
 
 
 def factorize(cov, per_walker):
