@@ -70,6 +70,13 @@ def _compile(job):
     return obj
 
 
+def shape_defs(g, e, fam, part):
+    """The defines and scheduler options one unit of ptmi_shape.hip is compiled with (see build())."""
+    track = ["-mllvm", "-amdgpu-use-amdgpu-trackers"] if fam < 2 else []
+    ilp = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"] if fam < 2 and part == 0 else []
+    return ["-DPTMI_G=%d" % g, "-DPTMI_E=%d" % e, "-DPTMI_L=%d" % fam, "-DPTMI_PART=%d" % part] + track + ilp
+
+
 def build(force=False, verbose=False, jobs=None):
     if not force and not stale():
         return OUT
@@ -91,11 +98,8 @@ def build(force=False, verbose=False, jobs=None):
             # config-2 kernel 0.797 -> 0.782 ms per 100 steps, dense 5.81 -> 5.72); the kernels of cycles with AM / DE entries
             # (part 1) measured 1-2 % slower with it and keep the default strategy.  max-memory-clause, metric bias 0, relaxed
             # occupancy and no post-RA scheduling measured within 0.5 % of the default or worse.
-            track = ["-mllvm", "-amdgpu-use-amdgpu-trackers"] if fam < 2 else []
-            ilp = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"] if fam < 2 else []
-            defs = ["-DPTMI_G=%d" % g, "-DPTMI_E=%d" % e, "-DPTMI_L=%d" % fam]
-            work.append((os.path.join(CSRC, "ptmi_shape.hip"), os.path.join(OBJ, "shape_%d_%d_%d.o" % (g, e, fam)), defs + ["-DPTMI_PART=0"] + track + ilp))
-            work.append((os.path.join(CSRC, "ptmi_shape.hip"), os.path.join(OBJ, "shape_full_%d_%d_%d.o" % (g, e, fam)), defs + ["-DPTMI_PART=1"] + track))
+            work.append((os.path.join(CSRC, "ptmi_shape.hip"), os.path.join(OBJ, "shape_%d_%d_%d.o" % (g, e, fam)), shape_defs(g, e, fam, 0)))
+            work.append((os.path.join(CSRC, "ptmi_shape.hip"), os.path.join(OBJ, "shape_full_%d_%d_%d.o" % (g, e, fam)), shape_defs(g, e, fam, 1)))
     jobs = jobs or min(len(work), _usable_cores())
     if verbose:
         print("compiling %d translation units with %d workers" % (len(work), jobs))
