@@ -435,6 +435,46 @@ int ptmi_gj_begin(ptmi_handle h, int64_t iter, void *work, double *rows /* dev [
 int ptmi_gj_step(ptmi_handle h, void *work, const double *lnl /* dev [n] */, const double *dlnl /* dev [n][ndim] */,
                  const double *lp /* dev [n] or NULL */, const double *dlp /* dev [n][ndim] or NULL */, double *rows, int64_t *n);
 
+/* Custom jump proposals in the cycle as BATCHED device callbacks on the split path (csrc/ptmi_cj.hip): addProposalToCycle(func, weight)
+ * of the reference (PT:988-1014, PT = PTMCMCSampler/PTMCMCSampler.py) and its dispatch q, qxy = func(x, iter, beta) (PT:1058-1059), for
+ * every chain whose pick of the iteration is one of the handle's w_host entries at once.  The proposal launch hands such a chain's state
+ * back as its proposal row with qaux[.][1] = PTMI_J_NTYPES + pick; per proposal launch (ptmi_propose(iter), or the propose half of
+ * ptmi_accept_propose(iter - 1)):
+ *
+ *     ptmi_cj_begin(h, iter, work, rows, beta, offs);
+ *     for every function f with offs[f] < offs[f + 1]:
+ *         callback f on rows[offs[f] .. offs[f + 1]) with beta[...]: the proposals written over the rows, qxy[offs[f] .. offs[f + 1])
+ *         (or ptmi_cj_box_draw(h, work, f, lo, hi, rows + offs[f] * ndim): qxy = 0)
+ *     ptmi_cj_end(h, work, rows, qxy);
+ *     likelihood callback on the proposals (ptmi_proposals), then ptmi_accept / ptmi_accept_propose
+ *
+ * ptmi_cj_attach (once, before the first ptmi_propose) declares that the w_host entries are served this way: fun_of_pick (HOST [w_host])
+ * maps each pick index to a function 0 .. nfun - 1 (the weight copies of one function share an index; nfun <= 32, else
+ * PTMI_EUNSUPPORTED), cjstat (DEVICE [W][T][w_host][2], by RANK like jstat, zeroed by the caller) takes proposed / accepted per pick index
+ * (PT:602,622) from ptmi_accept / ptmi_accept_propose.  With AM entries in the cycle it makes the scratch for their increments that
+ * ptmi_create leaves out for w_host > 0: ptmi_split_am_piece > 0 afterwards, the row kernels serve the handle.  A handle with w_host > 0
+ * that is never attached behaves as before (the caller rewrites the proposals itself).
+ * ptmi_cj_begin lists the chains with qaux[.][1] >= PTMI_J_NTYPES sorted by (function, chain slot w * T + s) -- a stable compaction, no
+ * atomics: the same order on every run -- copies each one's row of the CURRENT proposal buffer (ptmi_proposals; for these picks the row
+ * is the chain's state, wherever sloc says the state lives) into rows [n][ndim], writes beta[k] = 1 / T of the chain as the kernels use
+ * it, and returns the spans: function f owns rows offs[f] .. offs[f + 1] - 1 (offs: HOST [nfun + 1]).  One stream synchronisation: the
+ * offsets' read-back, the only one the stage adds per iteration.  ptmi_cj_end scatters the rows back into the listed chains' rows of the
+ * proposal buffer and qxy [n] (NULL: zeros) into qaux[.][0].  Row copies are contiguous 16-byte pieces (8-byte for odd ndim).
+ * ptmi_cj_box_draw is the reference's UniformJump (tests/test_simple.py:44-62: every parameter redrawn uniformly in [lo, hi], qxy = 0)
+ * for function fun's span, from the library's own generator: parameter i of a listed chain = lo[i] + (hi[i] - lo[i]) * u, u =
+ * (word >> 11) 2^-53 of word i & 1 of Philox at (seed, iter, the chain's stream id (walker0 + w) * ntemps_global + temp0 + rank,
+ * 0x4000000 + (i >> 1)); lo / hi: DEVICE [ndim]; rows: that function's span.
+ * work: caller-owned device memory of ptmi_cj_work_bytes bytes, 16-byte aligned (the list, the listing's block counts, the offsets);
+ * rows: device [W*T][ndim]; beta: device [W*T].  ptmi_accept / ptmi_accept_propose refuse (PTMI_EINVAL) while the stage of the current
+ * proposals of an attached handle has not ended; so do these calls out of sequence.  Not in ptmi_device_iter mode
+ * (PTMI_EUNSUPPORTED); parameter groups are fine (the stage never looks at them).  ptmi_create still refuses w_host > 0 together with
+ * w_nuts + w_hmc > 0.  On the handle's stream. */
+int ptmi_cj_attach(ptmi_handle h, uint64_t *cjstat /* dev [W][T][w_host][2] */, const int32_t *fun_of_pick /* host [w_host] */, int32_t nfun);
+int ptmi_cj_work_bytes(ptmi_handle h, size_t *bytes);
+int ptmi_cj_begin(ptmi_handle h, int64_t iter, void *work, double *rows /* dev [W*T][ndim] */, double *beta /* dev [W*T] */, int64_t *offs /* host [nfun+1] */);
+int ptmi_cj_end(ptmi_handle h, void *work, const double *rows /* dev [n][ndim] */, const double *qxy /* dev [n] or NULL: zeros */);
+int ptmi_cj_box_draw(ptmi_handle h, void *work, int32_t fun, const double *lo, const double *hi /* dev [ndim] */, double *rows /* dev: that function's span */);
+
 /* Self-test hooks used by the parity tests: evaluate the device's deterministic math on
  * n inputs (op: 0 log, 1 exp, 2 cos2pi, 3 sqrt, 4 reciprocal-free divide a/b with b=in2). */
 int ptmi_selftest_math(int device, int op, const double *in, const double *in2, double *out, int64_t n);

@@ -1096,7 +1096,7 @@ static KArgs make_args(ptmi_engine *h)
     a.Ut = b.Ut; a.S = b.S; a.DE = b.DE; a.AM = c.temp0 == 0 ? b.AM : nullptr; a.AMaux = c.temp0 == 0 ? b.AMaux : nullptr;
     a.AMflag = c.temp0 == 0 ? (AmFlag *)b.AMflag : nullptr;
     a.rp_draws = h->rp_draws;
-    a.nacc = (u64 *)b.nacc; a.jstat = (u64 *)b.jstat;
+    a.nacc = (u64 *)b.nacc; a.jstat = (u64 *)b.jstat; a.cjstat = h->cjstat;
     a.temps_mh = h->d_temps; a.beta = h->d_beta; a.logl_par = h->d_loglpar; a.logp_par = h->d_logppar;
     a.gsize = h->d_gsize; a.gmask = h->d_gmask; a.gcn = h->d_gcn; a.gdiv = h->d_gdiv; a.ngroups = c.ngroups > 1 ? c.ngroups : 1;
     a.Q = b.Q; a.qaux = b.qaux; a.Q2 = nullptr; a.sloc = nullptr; a.q_cur = 0; a.q_tgt = 0;
@@ -1194,6 +1194,51 @@ static int launch_am_gemm(ptmi_engine *h, long long max_events)
     if (h->G == 16) return ntile <= 16 ? launch_am_gemm_t<16, 4>(h, max_events) : launch_am_gemm_t<16, 8>(h, max_events);
     if (h->G == 64) return launch_am_gemm_t<64, 8>(h, max_events);
     return fail(PTMI_EINVAL, "AM increments ahead of the launch: unknown shape");
+}
+
+// Scratch for the AM increments of one piece of iterations (am_gemm_kernel), and the split path's cursors into it.  An allocation that
+// does not fit is no error: the handle then computes its AM products in the step kernels (split_am_piece = am_piece = 0).
+hipError_t ptmi_am_scratch_alloc(ptmi_engine *h, bool am_main)
+{
+    const ptmi_config &c = h->cfg;
+    const ptmi_buffers *buf = &h->buf;
+    hipError_t e = hipSuccess;
+    const long long nch = (long long)c.nwalkers * c.ntemps;
+    // scratch for the increments of one piece (6 GB; 2 GB for the split path alone)
+    const double budget = (am_main ? ptmi_env("PTMI_AM_BUDGET_MB", 6144.0) : ptmi_env("PTMI_SPLIT_AM_BUDGET_MB", 2048.0)) * 1048576.0;
+    long long piece = (long long)(budget / ((double)c.ndim * 8.0 * (double)nch));
+    piece = piece < 1 ? 1 : (piece > 64 ? 64 : piece);
+    if ((c.ngroups > 1 || c.cov_per_walker) && nch * piece > 0x7FFFFFFFLL) piece = 0x7FFFFFFFLL / nch;      // (the group lists index the events with 32 bits; nch itself is below 2^32 / ntemps)
+    if (piece < 1) piece = 1;
+    h->am_piece = am_main ? (int)piece : 0;
+    h->split_am_piece = (int)piece;
+    h->am_cap = nch * piece;
+    if (buf->Q != nullptr) e = hipMalloc((void **)&h->d_am_next, sizeof(long long) * (size_t)(nch + 1));
+    if (e == hipSuccess)
+    e = hipMalloc((void **)&h->d_am_ev, sizeof(AmEvent) * (size_t)h->am_cap);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_count, sizeof(int32_t) * (size_t)(nch + (nch + 1023) / 1024));      // counts | the scan's block sums
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_base, sizeof(long long) * (size_t)(nch + 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_inc, sizeof(double) * (size_t)h->am_cap * c.ndim);
+    if (e == hipSuccess && (c.ngroups > 1 || c.cov_per_walker)) {    // the events listed key by key: totals | cursors | the scan's block sums; list starts (+ the end)
+        const size_t nkeys = (size_t)(c.ngroups > 1 ? c.ngroups : 1) * (c.cov_per_walker ? (size_t)c.nwalkers : 1);
+        if (h->am_cap > 0x7FFFFFFFLL) e = hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_grp, sizeof(int32_t) * (2 * nkeys + (nkeys + 1023) / 1024 + 1));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_kbase, sizeof(long long) * (nkeys + 1));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_perm, sizeof(int32_t) * (size_t)h->am_cap);
+    }
+    if (e == hipErrorOutOfMemory) {
+        // no room for the scratch: the step kernels compute their own AM products (slower, the same results) instead of failing the
+        // handle -- configurations that fitted before this path existed still do
+        (void)hipGetLastError();
+        (void)hipFree(h->d_am_ev); (void)hipFree(h->d_am_count); (void)hipFree(h->d_am_base); (void)hipFree(h->d_am_inc);
+        (void)hipFree(h->d_am_grp); (void)hipFree(h->d_am_perm); (void)hipFree(h->d_am_kbase);
+        h->d_am_ev = nullptr; h->d_am_count = nullptr; h->d_am_base = nullptr; h->d_am_inc = nullptr;
+        h->d_am_grp = nullptr; h->d_am_perm = nullptr; h->d_am_kbase = nullptr;
+        (void)hipFree(h->d_am_next); h->d_am_next = nullptr;
+        h->am_piece = 0; h->am_cap = 0; h->split_am_piece = 0;
+        e = hipSuccess;
+    }
+    return e;
 }
 
 extern "C" {
@@ -1426,43 +1471,7 @@ int ptmi_create(const ptmi_config *cfg, const ptmi_buffers *buf, ptmi_handle *ou
     // kernels do not take this way (4 lanes per chain, one group: their own matrix-core product) the scratch serves the split path alone.
     const bool am_main = c.w_am > 0 && (c.ngroups > 1 || s.G > 4) && c.ndim <= 1024 && c.w_host == 0;
     const bool am_split = !am_main && buf->Q != nullptr && c.w_am > 0 && c.ndim <= 1024 && c.w_host == 0;
-    if (e == hipSuccess && (am_main || am_split)) {
-        const long long nch = (long long)c.nwalkers * c.ntemps;
-        // scratch for the increments of one piece (6 GB; 2 GB for the split path alone)
-        const double budget = (am_main ? ptmi_env("PTMI_AM_BUDGET_MB", 6144.0) : ptmi_env("PTMI_SPLIT_AM_BUDGET_MB", 2048.0)) * 1048576.0;
-        long long piece = (long long)(budget / ((double)c.ndim * 8.0 * (double)nch));
-        piece = piece < 1 ? 1 : (piece > 64 ? 64 : piece);
-        if ((c.ngroups > 1 || c.cov_per_walker) && nch * piece > 0x7FFFFFFFLL) piece = 0x7FFFFFFFLL / nch;      // (the group lists index the events with 32 bits; nch itself is below 2^32 / ntemps)
-        if (piece < 1) piece = 1;
-        h->am_piece = am_main ? (int)piece : 0;
-        h->split_am_piece = (int)piece;
-        h->am_cap = nch * piece;
-        if (buf->Q != nullptr) e = hipMalloc((void **)&h->d_am_next, sizeof(long long) * (size_t)(nch + 1));
-        if (e == hipSuccess)
-        e = hipMalloc((void **)&h->d_am_ev, sizeof(AmEvent) * (size_t)h->am_cap);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_count, sizeof(int32_t) * (size_t)(nch + (nch + 1023) / 1024));      // counts | the scan's block sums
-        if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_base, sizeof(long long) * (size_t)(nch + 1));
-        if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_inc, sizeof(double) * (size_t)h->am_cap * c.ndim);
-        if (e == hipSuccess && (c.ngroups > 1 || c.cov_per_walker)) {    // the events listed key by key: totals | cursors | the scan's block sums; list starts (+ the end)
-            const size_t nkeys = (size_t)(c.ngroups > 1 ? c.ngroups : 1) * (c.cov_per_walker ? (size_t)c.nwalkers : 1);
-            if (h->am_cap > 0x7FFFFFFFLL) e = hipErrorInvalidValue;
-            if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_grp, sizeof(int32_t) * (2 * nkeys + (nkeys + 1023) / 1024 + 1));
-            if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_kbase, sizeof(long long) * (nkeys + 1));
-            if (e == hipSuccess) e = hipMalloc((void **)&h->d_am_perm, sizeof(int32_t) * (size_t)h->am_cap);
-        }
-        if (e == hipErrorOutOfMemory) {
-            // no room for the scratch: the step kernels compute their own AM products (slower, the same results) instead of failing the
-            // handle -- configurations that fitted before this path existed still do
-            (void)hipGetLastError();
-            (void)hipFree(h->d_am_ev); (void)hipFree(h->d_am_count); (void)hipFree(h->d_am_base); (void)hipFree(h->d_am_inc);
-            (void)hipFree(h->d_am_grp); (void)hipFree(h->d_am_perm); (void)hipFree(h->d_am_kbase);
-            h->d_am_ev = nullptr; h->d_am_count = nullptr; h->d_am_base = nullptr; h->d_am_inc = nullptr;
-            h->d_am_grp = nullptr; h->d_am_perm = nullptr; h->d_am_kbase = nullptr;
-            (void)hipFree(h->d_am_next); h->d_am_next = nullptr;
-            h->am_piece = 0; h->am_cap = 0; h->split_am_piece = 0;
-            e = hipSuccess;
-        }
-    }
+    if (e == hipSuccess && (am_main || am_split)) e = ptmi_am_scratch_alloc(h, am_main);
     if (e == hipSuccess) e = hipEventCreate(&h->ev0);
     if (e == hipSuccess) e = hipEventCreate(&h->ev1);
     if (e != hipSuccess) { ptmi_destroy(h); return fail(PTMI_EHIP, "create: %s", hipGetErrorString(e)); }
@@ -1485,6 +1494,8 @@ int ptmi_destroy(ptmi_handle h)
     (void)hipFree(h->d_am_ev); (void)hipFree(h->d_am_count); (void)hipFree(h->d_am_base); (void)hipFree(h->d_am_inc);
     (void)hipFree(h->d_am_grp); (void)hipFree(h->d_am_perm); (void)hipFree(h->d_am_kbase); (void)hipFree(h->d_am_next); (void)hipFree(h->d_iter);
     if (h->h_gj_n) (void)hipHostFree(h->h_gj_n);
+    (void)hipFree(h->d_cj_fun);
+    if (h->h_cj_offs) (void)hipHostFree(h->h_cj_offs);
     (void)hipFree(h->d_gj_tab); (void)hipFree(h->d_gj_scr); (void)hipFree(h->d_gj_scal); (void)hipFree(h->d_gj_order); (void)hipFree(h->d_gj_bucket);
     if (h->side) { (void)hipStreamDestroy(h->side); (void)hipEventDestroy(h->side_go); (void)hipEventDestroy(h->side_done); }
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1669,6 +1680,9 @@ static void gj_proposed(ptmi_engine *h, long long iter)
 {
     h->gj_phase = h->cfg.w_nuts + h->cfg.w_hmc > 0 ? PTMI_GJ_PENDING : PTMI_GJ_NONE;
     h->gj_iter = iter;
+    // ... and with batched custom jumps attached (ptmi_cj.hip) their stage
+    h->cj_phase = h->cj_nfun > 0 ? PTMI_GJ_PENDING : PTMI_GJ_NONE;
+    h->cj_iter = iter;
 }
 // ... and an accept test may only read them once that stage is over
 static int gj_stage_over(const ptmi_engine *h, const char *who, int64_t iter)
@@ -1676,6 +1690,9 @@ static int gj_stage_over(const ptmi_engine *h, const char *who, int64_t iter)
     if (h->gj_phase == PTMI_GJ_PENDING || h->gj_phase == PTMI_GJ_ROUNDS)
         return fail(PTMI_EINVAL, "%s(%lld): the HMC / NUTS proposals of iteration %lld are not made yet -- ptmi_gj_begin and ptmi_gj_step until n = 0 first",
                     who, (long long)iter, h->gj_iter);
+    if (h->cj_phase == PTMI_GJ_PENDING || h->cj_phase == PTMI_GJ_ROUNDS)
+        return fail(PTMI_EINVAL, "%s(%lld): the custom jumps' proposals of iteration %lld are not made yet -- ptmi_cj_begin, the callbacks, ptmi_cj_end first",
+                    who, (long long)iter, h->cj_iter);
     return PTMI_OK;
 }
 
@@ -1744,6 +1761,7 @@ int ptmi_accept(ptmi_handle h, int64_t iter, const double *newlnL, const double 
     }
     HIPCHK(hipGetLastError());
     h->gj_phase = PTMI_GJ_NONE;
+    h->cj_phase = PTMI_GJ_NONE;
     return PTMI_OK;
 }
 
@@ -1779,6 +1797,7 @@ int ptmi_accept_propose(ptmi_handle h, int64_t iter, const double *newlnL, const
     if (int rc = set_step_args(h, &b)) return rc;
     if (int rc = run_shape(h, PTMI_OP_PROPOSE, b, grid, true)) return rc;
     HIPCHK(hipGetLastError());
+    gj_proposed(h, iter + 1);
     return PTMI_OK;
 }
 

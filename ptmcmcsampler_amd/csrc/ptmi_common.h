@@ -127,6 +127,7 @@ struct KArgs {
     const int32_t *gj_order;     // chain handled by each chain slot of the launch (chains of similar NUTS step size share a wave), -1: none
     int gj_nslots;               // chain slots of the launch when gj_order is set (>= the chains: the longest trees' chains have a wave to themselves)
     const u64 *rp_draws;         // TEST HOOK (ptmi_test_replay): propose_kernel takes P0, Q0, Q1 and the SCAM normal's bits of every chain from here
+    u64 *cjstat;                 // split path, batched custom jumps (ptmi_cj_attach): [W][T][w_host][2] proposed, accepted per pick index by RANK, or nullptr
 };
 
 // gradient jumps (ptmi_gj.inc.h): per-rank state, Philox slots, layout of a chain's tree scratch
@@ -134,6 +135,8 @@ enum { GJ_EPS = 0, GJ_MU = 1, GJ_HBAR = 2, GJ_EPSBAR = 3, GJ_NITER = 4, GJ_HITER
 constexpr int GJ_BUCKETS = 128;         // step-size classes of the launch order (ptmi_abi.hip gj_order_*)
 constexpr u32 SLOT_GJ = 0x2000000u;    // + 4096 * (momenta draw of the call) + direction
 constexpr u32 SLOT_GJS = 0x3000000u;   // + scalar draw of the call
+constexpr u32 SLOT_CJ = 0x4000000u;    // ptmi_cj_box_draw (ptmi_cj.hip): + (parameter >> 1), word parameter & 1
+constexpr int PTMI_CJ_MAXFUN = 32;     // functions a handle's batched custom jumps may name (ptmi_cj_attach)
 // vector slots of a chain's scratch: the two ends and the sample of the outer loop, then 4 per tree level
 enum { GJV_TM = 0, GJV_RM = 1, GJV_GM = 2, GJV_TP = 3, GJV_RP = 4, GJV_GP = 5, GJV_SAMPLE = 6, GJV_TOP = 7 };
 enum { GJL_FAR_T = 0, GJL_FAR_R = 1, GJL_CAND_T = 2, GJL_CAND_G = 3, GJL_VECS = 4 };
@@ -205,10 +208,23 @@ struct ptmi_engine {
     long long gj_iter, gj_n;
     void *gj_work;
     long long *h_gj_n;
+    // split path with batched custom jumps (ptmi_cj.hip): the counters and the pick -> function map of ptmi_cj_attach (cj_nfun == 0: not
+    // attached), where the stage of the current proposals is (PTMI_GJ_* as above; ROUNDS = between ptmi_cj_begin and ptmi_cj_end), their
+    // iteration, the caller's work area, the spans' offsets of the open stage and the pinned words they are read into
+    u64 *cjstat;
+    int32_t *d_cj_fun;
+    int cj_nfun, cj_phase;
+    long long cj_iter;
+    void *cj_work;
+    long long cj_offs[PTMI_CJ_MAXFUN + 1];
+    long long *h_cj_offs;
 };
 enum { PTMI_GJ_NONE = 0, PTMI_GJ_PENDING = 1 /* proposals made, ptmi_gj_begin not yet called */, PTMI_GJ_ROUNDS = 2, PTMI_GJ_DONE = 3 };
 // the split path's refusals for gradient jumps (0: served; else the code, with the message set)
 int ptmi_gj_split_check(const ptmi_engine *h);
+// the split path's scratch for AM increments made ahead of a launch (ptmi_abi.hip; ptmi_create for cycles without host-served entries,
+// ptmi_cj_attach for cycles whose host-served entries are batched device callbacks); main: the fused kernels read it too
+hipError_t ptmi_am_scratch_alloc(ptmi_engine *h, bool am_main);
 // eigensolvers (ptmi_eig.hip): frees h->dc_plan, for ptmi_destroy
 void ptmi_dc_plan_free(ptmi_engine *h);
 // swap (ptmi_swap.hip): bytes of a record of d_pre (SwapPre), for ptmi_create

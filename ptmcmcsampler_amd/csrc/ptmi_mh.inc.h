@@ -2038,6 +2038,8 @@ __global__ __launch_bounds__(256) void accept_kernel(const KArgs a)
     if (gl == 0) {
         const size_t r = (size_t)w * nt + t;
         if (jt >= 0 && jt < PTMI_J_NTYPES) a.jstat[(r * PTMI_J_NTYPES + jt) * 2 + 0] += 1;
+        const bool cj = a.cjstat != nullptr && jt >= PTMI_J_NTYPES && jt < PTMI_J_NTYPES + a.w_host;      // a batched custom jump (ptmi_cj_attach)
+        if (cj) a.cjstat[(r * a.w_host + (size_t)(jt - PTMI_J_NTYPES)) * 2 + 0] += 1;
         if (am && a.AMflag) a.AMflag[(size_t)w * a.cov_update + (size_t)a.am_row0] = AMROW_KEY | (acc ? AMROW_NEW : 0ull);   // the split path stores every row
         if (am && a.AMaux) {
             double *ax = a.AMaux + ((size_t)w * a.cov_update + (size_t)a.am_row0) * 2;
@@ -2049,6 +2051,7 @@ __global__ __launch_bounds__(256) void accept_kernel(const KArgs a)
             a.lp[ch] = nlp;
             a.nacc[r] += 1;
             if (jt >= 0 && jt < PTMI_J_NTYPES) a.jstat[(r * PTMI_J_NTYPES + jt) * 2 + 1] += 1;
+            if (cj) a.cjstat[(r * a.w_host + (size_t)(jt - PTMI_J_NTYPES)) * 2 + 1] += 1;
         }
         a.qaux[ch * 4 + 2] = acc ? 1.0 : 0.0;   // decision, for the host's per-name jump statistics
     }

@@ -31,7 +31,8 @@
 // AM picks (PT:879-933, 2 d^2 flop each) get their increments from the matrix cores AHEAD of the launch (am_gemm_kernel of ptmi_abi.hip:
 // ptmi_split_am_prepare lists the picks of a piece of iterations and multiplies; an increment depends on the chain's stream, the
 // iteration and the scale branch, not on its state) and the row kernel adds the chain's next one as it adds a SCAM direction.
-// Not here: host-served cycle entries together with AM entries, and handles without room for the increments -- the shape kernels'
+// Not here: host-served cycle entries together with AM entries (unless they are batched device callbacks: ptmi_cj_attach makes the
+// increments' scratch then), and handles without room for the increments -- the shape kernels'
 // propose_kernel / accept_kernel keep serving those; ptmi_split_rows_ok says whether a handle's configuration runs here.
 #include "ptmi_mh.inc.h"
 
@@ -126,6 +127,8 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const KArgs a)
             const bool am = cold && !swap_last;
             const size_t r = (size_t)w * nt + t;
             if (jt >= 0 && jt < PTMI_J_NTYPES) a.jstat[(r * PTMI_J_NTYPES + jt) * 2 + 0] += 1;
+            const bool cj = a.cjstat != nullptr && jt >= PTMI_J_NTYPES && jt < PTMI_J_NTYPES + a.w_host;      // a batched custom jump (ptmi_cj_attach)
+            if (cj) a.cjstat[(r * a.w_host + (size_t)(jt - PTMI_J_NTYPES)) * 2 + 0] += 1;
             if (am && a.AMflag) a.AMflag[(size_t)w * a.cov_update + (size_t)am_row0] = AMROW_KEY | (acc ? AMROW_NEW : 0ull);   // the split path stores every row
             if (am && a.AMaux) {
                 double *ax = a.AMaux + ((size_t)w * a.cov_update + (size_t)am_row0) * 2;
@@ -137,6 +140,7 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const KArgs a)
                 a.lp[ch] = nlp;
                 a.nacc[r] += 1;
                 if (jt >= 0 && jt < PTMI_J_NTYPES) a.jstat[(r * PTMI_J_NTYPES + jt) * 2 + 1] += 1;
+                if (cj) a.cjstat[(r * a.w_host + (size_t)(jt - PTMI_J_NTYPES)) * 2 + 1] += 1;
             }
             if (!PROP) a.qaux[ch * 4 + 2] = acc ? 1.0 : 0.0;     // the decision, for the host's per-name jump statistics
             if (acc) loc = 1 + a.q_cur;                          // the accepted proposal IS the new state, where it sits

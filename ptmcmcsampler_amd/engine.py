@@ -73,6 +73,35 @@ def interval_par(a, b, d):
     return np.ascontiguousarray(np.concatenate([a, w, np.log(w)]))
 
 
+class _BoxDrawJump(object):
+    """``PTEngine.box_draw_jump``: a batched jump whose body is ``ptmi_cj_box_draw`` (include/ptmi.h)."""
+    __name__ = "boxDrawJump"
+
+    def __init__(self, lo, hi):
+        self.lo_host, self.hi_host, self.engine = np.asarray(lo, np.float64), np.asarray(hi, np.float64), None
+
+    def bind(self, engine):
+        """The engine whose stage this jump draws in (``PTEngine(jumps=...)`` binds the ones it is given): the bounds go to its GPU."""
+        torch = _torch()
+        self.lo = torch.as_tensor(np.array(np.broadcast_to(self.lo_host, (engine.d,))), device=engine.device)
+        self.hi = torch.as_tensor(np.array(np.broadcast_to(self.hi_host, (engine.d,))), device=engine.device)
+        self.engine = engine
+        return self
+
+    def __call__(self, X, iter, beta):
+        eng = self.engine
+        if eng is None:
+            raise _lib.PtmiError("boxDrawJump runs inside PTEngine.jump_stage: give it to PTEngine(jumps=...) or PTSampler.addProposalToCycle(..., batched=True)")
+        _lib.check(eng.lib.ptmi_cj_box_draw(eng.h, eng._cj_work.data_ptr(), eng._cj_cur, self.lo.data_ptr(), self.hi.data_ptr(), X.data_ptr()))
+        return X, None
+
+
+def box_draw_jump(lo, hi):
+    """An unbound ``boxDrawJump`` (``PTEngine.box_draw_jump``) for ``PTEngine(jumps=[(box_draw_jump(lo, hi), weight), ...])``: the
+    engine binds it when it is built."""
+    return _BoxDrawJump(lo, hi)
+
+
 class PTEngine(object):
     """Chains of ``nwalkers`` x ``ntemps`` on one GPU.
 
@@ -135,6 +164,12 @@ class PTEngine(object):
     ``run_callback`` supports; not with ``w_host`` or a sharded ladder (``ntemps_global`` / ``temp0``).  ``am_mode="auto"`` is ``"rows"``
     here (the split path stores every rank-0 row), so with a POOLED covariance the bits are those of the fused path with
     ``am_mode="rows"``; its default ``"rle"`` sums the same pooled statistics in another order.
+    ``jumps=[(func, weight), ...]`` (with ``w_host`` = the sum of the weights, or 0 for that; ``split=True`` or ``rows_logl=True``): the
+    cycle's custom entries (the reference's ``addProposalToCycle``, PTMCMCSampler.py:988-1014, 1058-1059) as BATCHED device callbacks --
+    ``func(X[n, d], iter, beta[n]) -> (Q[n, d], qxy[n] | 0 | None)`` on torch tensors of this GPU, once per iteration for all chains
+    whose pick is that function (``jump_stage``; include/ptmi.h ``ptmi_cj_*``).  ``box_draw_jump(lo, hi)`` is the reference's
+    ``UniformJump`` as a library kernel.  ``get("cjstat")`` [W][nt][w_host][2]: proposed / accepted per pick index by rank.  Not with
+    gradient jumps, not in graph mode.
     ``stats_async`` (pooled covariance with ``eig_lag >= 1``): the statistics of a covariance period that is over need nothing the next
     launches touch once those write ANOTHER ring -- so the engine keeps two rings (``t["AM"]`` is always the one in use), switches at
     every covariance epoch, and runs the period's statistics (``ptmi_update_cov_on``) and the factorization behind them on a side
@@ -149,14 +184,35 @@ class PTEngine(object):
                  ntemps_global=None, temp0=0, walker0=0, device=0, split=False, use_de_buffer=None,
                  w_host=0, keep_lnl=False, groups=None, swap_mode="sweep",
                  grad_weights=(0, 0), hmc=(0.1, 2, 300), nuts_delta=0.6, nuts_maxdepth=24, pick_mode="chain",
-                 eig_mode="lapack", am_mode="auto", eig_lag=0, stats_async=False, split_nuts=False, rows_logl=False):
+                 eig_mode="lapack", am_mode="auto", eig_lag=0, stats_async=False, split_nuts=False, rows_logl=False, jumps=None):
         torch = _torch()
+        # jumps: the w_host cycle entries as batched device callbacks (see the class docstring); fun_of_pick in cycle order, the
+        # weight copies of one function sharing its index
+        self._jumps, self._fun_of_pick = [], []
+        if jumps is not None:
+            for func, weight in jumps:
+                if not callable(func) or int(weight) < 1:
+                    raise ValueError("jumps=[(func, weight), ...] takes callables with weights >= 1")
+                known = [k for k, f in enumerate(self._jumps) if f is func]
+                if not known:
+                    self._jumps.append(func)
+                self._fun_of_pick += [known[0] if known else len(self._jumps) - 1] * int(weight)
+            if int(w_host) == 0:
+                w_host = len(self._fun_of_pick)
+            if len(self._fun_of_pick) != int(w_host) or not self._jumps:
+                raise ValueError("jumps= names %d cycle entries for w_host=%d" % (len(self._fun_of_pick), int(w_host)))
+            if len(self._jumps) > _lib.CJ_MAXFUN:
+                raise ValueError("jumps= takes at most %d different functions (got %d)" % (_lib.CJ_MAXFUN, len(self._jumps)))
+            if sum(int(w) for w in grad_weights) > 0:
+                raise ValueError("custom jumps (jumps=) cannot be mixed with gradient jumps (grad_weights) in one cycle")
+            if not (split or rows_logl):
+                raise ValueError("jumps= are served on the callback path: split=True (or rows_logl=True)")
         # rows_logl: the built-in likelihood as a row kernel on the split path (see the class docstring); refused before anything is built
         self.rows_logl = bool(rows_logl)
         if self.rows_logl:
             if logl[0] not in ("iso", "dense"):
                 raise ValueError("rows_logl=True serves logl=('iso',) and ('dense', mu, P) (ptmi_rows_logl), not %r" % (logl[0],))
-            if int(w_host) > 0:
+            if int(w_host) > 0 and not self._jumps:
                 raise ValueError("rows_logl=True cannot be combined with w_host > 0: host-served jumps need the caller's own callbacks")
             if (ntemps_global is not None and int(ntemps_global) != int(ntemps)) or int(temp0) != 0:
                 raise ValueError("rows_logl=True cannot be combined with ntemps_global / temp0 (a sharded ladder): run_callback swaps the whole ladder on one GPU")
@@ -304,6 +360,15 @@ class PTEngine(object):
         buf = _lib.Buffers(**{k: (C.c_void_p(v.data_ptr()) if v is not None else None) for k, v in self.t.items()})
         self.h = C.c_void_p()
         _lib.check(self.lib.ptmi_create(C.byref(cfg), C.byref(buf), C.byref(self.h)))
+        if self._jumps:
+            # proposed / accepted per pick index, by rank like jstat (get("cjstat"); device checkpoints carry it)
+            self.t["cjstat"] = z((W, nt, int(w_host), 2), i64)
+            fop = np.ascontiguousarray(self._fun_of_pick, dtype=np.int32)
+            _lib.check(self.lib.ptmi_cj_attach(self.h, C.c_void_p(self.t["cjstat"].data_ptr()), fop.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               len(self._jumps)))
+            for f in self._jumps:
+                if isinstance(f, _BoxDrawJump):
+                    f.bind(self)
         self.de_on = False
         self.de_head = 0
         self.iter = 0
@@ -369,7 +434,7 @@ class PTEngine(object):
             return np.ascontiguousarray(a[..., pos])
         if name == "AM" and self.am_pos is not None:
             return np.ascontiguousarray(a[..., self.am_pos])              # parameter order whatever the device format
-        return a.view(np.uint64) if name in ("nacc", "jstat", "nswap", "AMflag") else a
+        return a.view(np.uint64) if name in ("nacc", "jstat", "nswap", "AMflag", "cjstat") else a
 
     def put(self, name, value):
         torch = _torch()
@@ -761,6 +826,8 @@ class PTEngine(object):
         for k, v in self.t.items():
             if v is not None and "t_" + k in st:
                 v.copy_(torch.from_numpy(np.ascontiguousarray(st["t_" + k])).to(v.dtype))
+            elif v is not None and k == "cjstat":
+                v.zero_()                                             # a checkpoint from before the counters existed
         if self.stats_async:                                          # the ring of the period before (readers of older rows: get("AM"))
             for k, v in self._alt.items():
                 if v is not None and "alt_" + k in st:
@@ -961,6 +1028,68 @@ class PTEngine(object):
             rounds += 1
         return rounds
 
+    def jump_stage(self, it):
+        """The custom picks of the proposals of iteration ``it`` (just made by ptmi_propose / ptmi_accept_propose) through the batched
+        jumps of ``jumps=``: ``ptmi_cj_begin`` lists the chains by (function, chain slot) and copies their states out; every function
+        with a non-empty span is called once, ``func(X[n, d], it, beta[n]) -> (Q[n, d], qxy[n] | 0 | None)`` on device tensors (``X``
+        may be changed in place and returned); ``ptmi_cj_end`` puts the rows back as those chains' proposals with their ``qxy``.
+        One host read-back (the spans' offsets); nothing else leaves the device.  Returns the number of listed chains.  A no-op
+        without ``jumps=``."""
+        if not self._jumps:
+            return 0
+        torch = _torch()
+        nf, n_all = len(self._jumps), self.W * self.nt
+        if getattr(self, "_cj_work", None) is None:
+            nb = C.c_size_t(0)
+            _lib.check(self.lib.ptmi_cj_work_bytes(self.h, C.byref(nb)))
+            self._cj_work = torch.empty(nb.value, dtype=torch.uint8, device=self.device)
+            self._cj_rows = torch.empty((n_all, self.d), dtype=torch.float64, device=self.device)
+            self._cj_beta = torch.empty(n_all, dtype=torch.float64, device=self.device)
+            self._cj_qxy = torch.empty(n_all, dtype=torch.float64, device=self.device)
+            self._cj_offs = (C.c_int64 * (nf + 1))()
+        lib, h, work, rows = self.lib, self.h, self._cj_work.data_ptr(), self._cj_rows
+        _lib.check(lib.ptmi_cj_begin(h, it, work, rows.data_ptr(), self._cj_beta.data_ptr(), self._cj_offs))
+        offs = list(self._cj_offs)
+        have_qxy = []
+        for f, func in enumerate(self._jumps):
+            lo, hi = offs[f], offs[f + 1]
+            n = hi - lo
+            if n <= 0:
+                continue                                              # a span of zero rows is not called
+            X = rows[lo:hi]
+            self._cj_cur = f                                          # (box_draw_jump: which span the library draws into)
+            r = func(X, it, self._cj_beta[lo:hi])
+            what = getattr(func, "__name__", "jump %d" % f)
+            if not isinstance(r, (tuple, list)) or len(r) != 2:
+                raise ValueError("%s must return (Q[n, ndim], qxy[n] or 0 or None)" % what)
+            Q, qxy = r
+            if not (torch.is_tensor(Q) and Q.dtype == torch.float64 and Q.device == self.device and Q.is_contiguous()):
+                Q = torch.as_tensor(Q, dtype=torch.float64, device=self.device).contiguous()
+            if tuple(Q.shape) != (n, self.d):
+                raise ValueError("%s returned proposals %s for %d rows of %d parameters" % (what, tuple(Q.shape), n, self.d))
+            if Q.data_ptr() != X.data_ptr():
+                X.copy_(Q)
+            if qxy is None or (not torch.is_tensor(qxy) and np.ndim(qxy) == 0 and qxy == 0):
+                continue
+            if not (torch.is_tensor(qxy) and qxy.dtype == torch.float64 and qxy.device == self.device):
+                qxy = torch.as_tensor(qxy, dtype=torch.float64, device=self.device)
+            if qxy.numel() != n:
+                raise ValueError("%s returned qxy %s for %d rows" % (what, tuple(qxy.shape), n))
+            self._cj_qxy[lo:hi].copy_(qxy.reshape(n))
+            have_qxy.append(f)
+        if have_qxy and len(have_qxy) < nf:
+            for f in range(nf):
+                if f not in have_qxy and offs[f + 1] > offs[f]:
+                    self._cj_qxy[offs[f]:offs[f + 1]].zero_()
+        _lib.check(lib.ptmi_cj_end(h, work, rows.data_ptr(), self._cj_qxy.data_ptr() if have_qxy else None))
+        return offs[nf]
+
+    def box_draw_jump(self, lo, hi):
+        """The reference's ``UniformJump`` (tests/test_simple.py:44-62: every parameter redrawn uniformly in ``[lo, hi]``, qxy = 0)
+        as a batched jump for ``jumps=``: its body is ``ptmi_cj_box_draw``, the library's own counter-based generator -- reproducible
+        and independent of torch's.  Bound to this engine (the module's ``box_draw_jump`` makes an unbound one for ``PTEngine(jumps=...)``)."""
+        return _BoxDrawJump(lo, hi).bind(self)
+
     def split_step(self, it, logl, logp, logl_grad=None, logp_grad=None):
         """One iteration of every chain with batched callbacks: ptmi_propose -> (HMC / NUTS in the cycle: the gradient stage,
         ``gradient_stage``) -> callbacks on the device tensor of proposals -> ptmi_accept.  All on the engine's stream; no host copy of
@@ -969,6 +1098,7 @@ class PTEngine(object):
             raise _lib.PtmiError("the callback path needs the engine built with split=True")
         _lib.check(self.lib.ptmi_propose(self.h, it))
         self.gradient_stage(it, logl_grad, logp_grad)
+        self.jump_stage(it)
         ll, lp = self.eval_callback(self.t["Q"], logl, logp)
         _lib.check(self.lib.ptmi_accept(self.h, it, ll.data_ptr(), lp.data_ptr()))
 
@@ -1063,12 +1193,14 @@ class PTEngine(object):
             _lib.check(lib.ptmi_split_am_prepare(h, it, min(piece, end - it + 1)))
         _lib.check(lib.ptmi_propose(h, it))
         self.gradient_stage(it, logl_grad, logp_grad)
+        self.jump_stage(it)
         for j in range(it, end):
             ll, lp = self.eval_callback(self.proposals(), logl, logp)
             if piece and (j + 1 - it) % piece == 0:                   # the proposal of j + 1 opens the next piece
                 _lib.check(lib.ptmi_split_am_prepare(h, j + 1, min(piece, end - j)))
             _lib.check(lib.ptmi_accept_propose(h, j, ll.data_ptr(), lp.data_ptr()))       # (between here and ptmi_accept X is not the state: sloc)
             self.gradient_stage(j + 1, logl_grad, logp_grad)
+            self.jump_stage(j + 1)
         ll, lp = self.eval_callback(self.proposals(), logl, logp)
         _lib.check(lib.ptmi_accept(h, end, ll.data_ptr(), lp.data_ptr()))
 
@@ -1083,8 +1215,8 @@ class PTEngine(object):
         configurations the row kernels do not serve; HMC or NUTS in the cycle: their rounds are counted on the host): the caller then runs
         ``callback_segment``.  Same results, bit for bit."""
         torch = _torch()
-        if self.t["Q2"] is None or self.weights[1] > 0 or sum(self.grad_weights) > 0:
-            return False
+        if self.t["Q2"] is None or self.weights[1] > 0 or sum(self.grad_weights) > 0 or self._jumps:
+            return False                                              # (custom jumps: their spans are read on the host)
         if getattr(self, "_graphs", None) is None:
             self._graphs = {}
         L = end - it + 1

@@ -19,7 +19,9 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
 * ``batched=True``: ``logl`` / ``logp`` are called once per iteration with the device tensor of all proposals,
   ``f(X[n, ndim]) -> [n]`` (torch in, torch out; loglargs / loglkwargs still apply) -- the same boundary as the reference's
   ``_function_wrapper`` (PTMCMCSampler.py:1072-1086), one call per batch instead of one per chain, nothing copied to the
-  host; custom Python jumps cannot be mixed in.  With ``logl_grad`` / ``logp_grad`` as batched callbacks too --
+  host; per-chain Python jumps cannot be mixed in, custom jumps in the batched signature can
+  (``addProposalToCycle(func, weight, batched=True)``: ``func(X[n, ndim], iter, beta[n]) -> (Q[n, ndim], qxy[n] | 0 | None)``;
+  ``boxDrawJump(lo, hi)`` is the reference's uniform prior draw as a library kernel).  With ``logl_grad`` / ``logp_grad`` as batched callbacks too --
   ``f(X[n, ndim]) -> (value[n], gradient[n, ndim])`` -- HMC (``HMCweight``) runs on the device with the callbacks' gradients
   (``PTEngine.gradient_stage``); NUTS (``NUTSweight``) too with ``batched_nuts=True`` -- opt-in: an iteration takes as many
   callback rounds as its deepest tree has leaves (without it pass ``NUTSweight=0``);
@@ -181,6 +183,7 @@ class PTSampler(object):
         self.M2 = np.zeros((ndim, ndim))
         self.mu = np.zeros(ndim)
         self.propCycle, self.jumpDict, self.aux = [], {}, []
+        self._batched_jumps = []                             # cycle entries added with addProposalToCycle(..., batched=True)
         self.engine = None
         self._ctx = (0, 0)
 
@@ -199,19 +202,35 @@ class PTSampler(object):
         return bool(rows_logl)
 
     # ------------------------------------------------------------------ proposal cycle API
-    def addProposalToCycle(self, func, weight):
-        """PTMCMCSampler.py:988-1014: ``weight`` copies of ``func`` join the cycle; weight 0 is ignored."""
+    def addProposalToCycle(self, func, weight, batched=False):
+        """PTMCMCSampler.py:988-1014: ``weight`` copies of ``func`` join the cycle; weight 0 is ignored.  ``batched=True``: ``func`` is
+        called once per iteration for ALL chains whose pick it is, on device tensors -- ``func(X[n, ndim], iter, beta[n]) ->
+        (Q[n, ndim], qxy[n] | 0 | None)`` -- between the proposal launch and the likelihood (``PTEngine.jump_stage``); for samplers
+        with ``batched=True`` or a device likelihood with ``rows_logl=True``, which take no per-chain Python jumps."""
         if weight == 0:
             return
+        if batched and not any(f is func for f in self._batched_jumps):
+            self._batched_jumps.append(func)
         for _ in range(weight):
             self.propCycle.append(func)
         if func.__name__ not in self.jumpDict:
             self.jumpDict[func.__name__] = [0, 0]
             open(self.outDir + "/" + func.__name__ + "_jump.txt", "w").close()
 
-    def addAuxilaryJump(self, func):
-        """PTMCMCSampler.py:1017-1028."""
+    def addAuxilaryJump(self, func, batched=False):
+        """PTMCMCSampler.py:1017-1028 (per chain, on the host)."""
+        if batched:
+            raise NotImplementedError("auxiliary jumps are not served as batched device callbacks: func(x, q, iter, beta) needs the state x of "
+                                      "EVERY chain, and between the proposal launch and the accept test a chain's state lives in X or in "
+                                      "one of the two proposal buffers (sloc); add them per chain on a sampler without batched=True")
         self.aux.append(func)
+
+    @staticmethod
+    def boxDrawJump(lo, hi):
+        """The reference's ``UniformJump`` (tests/test_simple.py:44-62: every parameter redrawn uniformly in ``[lo, hi]``, qxy = 0) as a
+        library kernel on the library's own generator: ``s.addProposalToCycle(s.boxDrawJump(lo, hi), 5, batched=True)``."""
+        from .engine import box_draw_jump
+        return box_draw_jump(lo, hi)
 
     def randomizeProposalCycle(self):
         """PTMCMCSampler.py:1031-1045 (the shuffled copy is dead state there too)."""
@@ -364,12 +383,32 @@ class PTSampler(object):
                     os.remove(stale)
         # ---- engine
         self.host_jumps = [f for f in self.propCycle if self._builtin(f) < 0]
-        self.split = self.logl is not None or bool(self.host_jumps) or bool(self.aux)
+        # custom cycle entries as batched device callbacks (addProposalToCycle(..., batched=True)): through the engine's jump stage on
+        # the samplers whose proposals never leave the device -- batched=True, or a device likelihood run as row kernels (rows_logl)
+        is_bj = lambda f: any(f is g for g in self._batched_jumps)      # noqa: E731
+        stage_ok = self.batched or (self.logl is None and self.rows_logl)
+        if any(is_bj(f) for f in self.host_jumps) and not stage_ok:
+            raise ValueError("a batched jump (addProposalToCycle(..., batched=True)) runs on the device callback path: PTSampler(..., "
+                             "batched=True), or a device likelihood with rows_logl=True; this sampler calls its jumps per chain")
+        self._stage_jumps = bool(self.host_jumps) and stage_ok and all(is_bj(f) for f in self.host_jumps) and not self.aux
+        if self._stage_jumps and sum(self._grad_weights) > 0:
+            raise NotImplementedError("batched custom jumps cannot be mixed with gradient jumps (HMC / NUTS) in one cycle: pass "
+                                      "NUTSweight=0, HMCweight=0 or leave logl_grad / logp_grad out")
+        on_host = [] if self._stage_jumps else self.host_jumps
+        self.split = self.logl is not None or bool(on_host) or bool(self.aux)
         if self.split and self.logl is None:
             raise NotImplementedError("host-side jumps need Python logl/logp callbacks")
-        if self.batched and (self.logl is None or self.host_jumps or self.aux):
+        if self.batched and (self.logl is None or on_host or self.aux):
             raise NotImplementedError("batched=True takes callable logl/logp and no per-chain Python jumps "
-                                      "(they would need every proposal on the host)")
+                                      "(they would need every proposal on the host): add them with addProposalToCycle(func, weight, "
+                                      "batched=True) in the batched signature")
+        stage_list = []                                               # [(func, weight)] in cycle order
+        if self._stage_jumps:
+            for f in self.host_jumps:
+                if stage_list and stage_list[-1][0] is f:
+                    stage_list[-1][1] += 1
+                else:
+                    stage_list.append([f, 1])
         self.engine = PTEngine(
             self.ndim, self.nchain, self.nwalkers, np.asarray(self.cov, dtype=np.float64), ladder=self.ladder,
             logl=self.logl_spec or ("iso",), logp=self.logp_spec or ("flat",),
@@ -377,6 +416,7 @@ class PTSampler(object):
             seed=self.seed, cov_mode=self.cov_mode, hot_chain=hotChain, device=self.device_index, split=self.split,
             swap_mode=self.swap_mode, pick_mode=self.pick_mode, eig_mode=self.eig_mode, grad_weights=self._grad_weights, hmc=(HMCstepsize, 2, HMCsteps), nuts_maxdepth=self.nuts_maxdepth,
             split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
+            jumps=[(f, n) for f, n in stage_list] if stage_list else None,
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     # ------------------------------------------------------------------ sample (:374-528)
@@ -523,7 +563,8 @@ class PTSampler(object):
         return np.asarray([self.seed & 0x7FFFFFFFFFFFFFFF, self.ndim, self.nchain, self.nwalkers, self.thin, self.covUpdate, self.burn,
                            eng.de_ld, eng.de_epl, self.keep_walkers, eng.am_epl,
                            digest(np.asarray(eng.ladder, dtype=np.float64), np.asarray(eng.temps_mh, dtype=np.float64)), self.Tskip,
-                           digest((self.SCAMweight, self.AMweight, self.DEweight) + tuple(self._grad_weights) + (len(self.host_jumps),)),
+                           digest((self.SCAMweight, self.AMweight, self.DEweight) + tuple(self._grad_weights) + (len(self.host_jumps),)
+                                  + ((tuple(f.__name__ for f in self.host_jumps),) if getattr(self, "_stage_jumps", False) else ())),
                            digest((self.cov_mode, self.swap_mode, self.pick_mode, self.eig_mode, self.nuts_maxdepth, bool(self.split), bool(self.batched),
                                    bool(eng.am_rle)), *groups),
                            digest(*(spec(self.logl_spec) + spec(self.logp_spec)))], dtype=np.int64)
@@ -716,6 +757,14 @@ class PTSampler(object):
         for k, name in ((_lib.J_NUTS, "NUTSJUMP"), (_lib.J_HMC, "HMCJump")):
             if self._grad_weights[k - _lib.J_NUTS] > 0:
                 self.jumpDict[name] = [int(js[k, 0]), int(js[k, 1])]
+        if getattr(self, "_stage_jumps", False):                     # batched custom jumps: per pick index on the device, summed per name
+            cj = eng.get("cjstat")[0, 0]
+            tot = {}
+            for k, f in enumerate(self.host_jumps):
+                t = tot.setdefault(f.__name__, [0, 0])
+                t[0] += int(cj[k, 0])
+                t[1] += int(cj[k, 1])
+            self.jumpDict.update(tot)
 
     def _harvest(self, iters):
         """updateChains (:331-335) for the kept walkers, read back from the AM ring."""
