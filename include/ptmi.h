@@ -96,7 +96,9 @@ typedef struct ptmi_config {
     int32_t swap_mode;       /* PTMI_SWAP_SWEEP (the reference's hot -> cold sweep, :666-686) or PTMI_SWAP_ODDEVEN */
     /* Gradient jumps on the built-in likelihoods (the reference adds them when logl_grad / logp_grad are given,
      * :225-258; nutsjump.py): cycle += [NUTS]*w_nuts + [HMC]*w_hmc.  ndim <= 512; the engine then shares a chain among
-     * ptmi_lanes_for_grad(ndim) lanes (at most 8 register slots per lane), which fixes the summation orders. */
+     * ptmi_lanes_for_grad(ndim) lanes (at most 8 register slots per lane), which fixes the summation orders.  With parameter
+     * groups (ngroups > 1; not the interval family) SCAM / AM / DE move one group's parameters with that group's tables, a NUTS or
+     * HMC pick draws no group and moves every parameter with the whitening tables of the full initial covariance (gj_tab). */
     int32_t w_nuts, w_hmc;
     int32_t gj_nburn;        /* nburn of the jump objects (= burn, :227,238,251) */
     int32_t hmc_min, hmc_max;/* HMC takes randint(hmc_min, hmc_max) leapfrogs (:240-241: 2, HMCsteps) */
@@ -428,8 +430,10 @@ int ptmi_rows_logp(ptmi_handle h, const double *rows /* dev [n][ndim] */, int64_
  * -- 88 vectors with the HMC ones at nuts_maxdepth = 24: 1.85 GB at 64 x 1024 chains of 40 parameters.  rows: device [W*T][ndim] (a
  * round lists at most every chain).  Each call reads n back to the host: one stream synchronisation per round, the only one the stage
  * adds.  ptmi_accept / ptmi_accept_propose refuse (PTMI_EINVAL) while the stage of the current proposals has not ended; so do these
- * calls out of sequence.  The shape kernels' split path (PTMI_SPLIT_ROWS=0, or a handle ptmi_split_rows_ok does not take),
- * ptmi_device_iter mode and parameter groups are refused (PTMI_EUNSUPPORTED).  On the handle's stream. */
+ * calls out of sequence.  The shape kernels' split path (PTMI_SPLIT_ROWS=0, or a handle ptmi_split_rows_ok does not take) and
+ * ptmi_device_iter mode are refused (PTMI_EUNSUPPORTED); parameter groups are fine (the proposal launch draws the group of a SCAM /
+ * AM / DE pick and hands a gradient pick back unchanged; the stage never looks at groups: a gradient jump moves every parameter with the
+ * whitening tables of the full initial covariance).  On the handle's stream. */
 int ptmi_gj_work_bytes(ptmi_handle h, size_t *bytes);
 int ptmi_gj_begin(ptmi_handle h, int64_t iter, void *work, double *rows /* dev [W*T][ndim] */, int64_t *n);
 int ptmi_gj_step(ptmi_handle h, void *work, const double *lnl /* dev [n] */, const double *dlnl /* dev [n][ndim] */,

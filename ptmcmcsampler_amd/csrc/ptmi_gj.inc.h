@@ -1470,11 +1470,17 @@ constexpr int GJ_BLOCK = 64;
 // PAIR (4-lane shapes, diagonal whitening, iso / curved families): two gradient jumps at a time, a half-wave each (GradJumpPair)
 // W16 (the 16-lane shape at ndim <= 64): a gradient jump takes the whole wave there too
 // (GradJumpWide<16, LOGL, 16>: one element per lane instead of seven slots of every vector in each of the chain's 16 lanes)
-template <int G, int EPL, int LOGL, bool PAIR = false, int W16 = 0 /* 1: diagonal whitening tables, 2: full ones (two instantiations: the product's code costs the diagonal kernel 14 %) */>
+// GRP: parameter groups (PT:129-145).  SCAM / AM / DE move one group's parameters with that group's tables (propose() draws the group
+// and picks the table, [walker or 0][group] as in the GRP step kernels of ptmi_mh.inc.h); a NUTS / HMC pick moves every parameter with
+// the whitening tables of the full initial covariance and never looks at a group (PT:225-258; the oracle's mh_one takes g = 0 there).
+// One layout per lane width: whole-wave at 4 lanes, per-chain at 16 and 64 (which lanes host a chain does not enter its arithmetic).
+template <int G, int EPL, int LOGL, bool PAIR = false, int W16 = 0 /* 1: diagonal whitening tables, 2: full ones (two instantiations: the product's code costs the diagonal kernel 14 %) */,
+          bool GRP = false>
 __global__ __launch_bounds__(GJ_BLOCK, ((G == 4 && EPL <= 5) || W16) ? PTMI_GJ_WPE : 1) void mh_steps_gj_kernel(const KArgs a)
 {
     static_assert(!PAIR || (G == 4 && EPL <= 8 && LOGL != PTMI_LOGL_DENSE), "the pair layout serves the 4-lane shapes without table products");
     static_assert(!W16 || (G == 16 && !PAIR), "the 16-group whole-wave layout serves the 16-lane shape");
+    static_assert(!GRP || (!PAIR && !W16), "parameter groups run the default layout of their lane width");
     constexpr int CPB = GJ_BLOCK / G;
     constexpr bool WIDE = G == 4 || W16;         // a gradient jump takes the whole wave (GradJumpWide)
     constexpr int WEPL = W16 ? 16 : EPL, WNS = W16 ? 4 : EPL;          // GradJumpWide's EPL (LD / 4); slots of a lane that hold elements in its layout
@@ -1521,7 +1527,8 @@ __global__ __launch_bounds__(GJ_BLOCK, ((G == 4 && EPL <= 5) || W16) ? PTMI_GJ_W
     const u32 sid = sid0 + (u32)tg;
     DrawBatch<false> batch;
     const size_t wc = a.per_walker ? (size_t)w : 0;
-    const double *Ut = a.Ut + wc * d * d, *S = a.S + wc * d;
+    const size_t tc = GRP ? wc * (size_t)a.ngroups : wc;                // the chain's first table: propose() adds the group's offset
+    const double *Ut = a.Ut + tc * d * d, *S = a.S + tc * d;
     const double *DE = a.DE ? a.DE + wc * (size_t)a.de_size * a.de_ld : nullptr;
     const double *PtG = LOGL == PTMI_LOGL_DENSE ? a.logl_par + d + (size_t)a.d * a.d : nullptr;   // eval_logl's half table Tl
     double *xrow = a.X + (size_t)ch * d;
@@ -1559,7 +1566,7 @@ __global__ __launch_bounds__(GJ_BLOCK, ((G == 4 && EPL <= 5) || W16) ? PTMI_GJ_W
         Draws dr;
         draws_for_step<false, true>(batch, dr, a, k, sid, sid0, gl);
         const double log_u = dr.log_u;
-        const int jt = propose<G, EPL, true, false, false, true>(a, it, sid, gl, cc, dr, Ut, false, S, DE, q, false, true, nullptr, &am_next);
+        const int jt = propose<G, EPL, true, false, GRP, true>(a, it, sid, gl, cc, dr, Ut, false, S, DE, q, false, true, nullptr, &am_next);
         const bool is_gj = jt == PTMI_J_NUTS || jt == PTMI_J_HMC;
         if constexpr (PAIR) {
             // two chains at a time, a half-wave each: their rows go through LDS into the pair layout (area 32 hh + 16 (g >> 1) +

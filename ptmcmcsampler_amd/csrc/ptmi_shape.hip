@@ -42,6 +42,8 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
             // Wider shapes: lowest levels of the tree stack | box bounds.
             size_t off = 0;
             bool pair = false, w16 = false;
+            // parameter groups: one layout per lane width (whole-wave at 4 lanes, per-chain at 16 and 64): the GRP instantiation below
+            const bool grp = h->cfg.ngroups > 1;
             const size_t box = h->cfg.logp_kind == PTMI_LOGP_BOX ? (size_t)box_table_doubles(G, E) : 0;
             const int lv = (int)ptmi_env("PTMI_GJ_LDS_LEVELS", 1 << 30);    // a test hook: same results for any value
             if constexpr (G == 4) {
@@ -52,9 +54,9 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
                 a.gj_lds_levels = levels;
                 // two jumps at a time, a half-wave each (GradJumpPair): diagonal whitening, no dense products; PTMI_GJ_NOPAIR: the
                 // one-chain-per-wave layout (a test hook, same results)
-                pair = a.gj_diag && L != PTMI_LOGL_DENSE && !ptmi_env("PTMI_GJ_NOPAIR", 0);
+                pair = a.gj_diag && L != PTMI_LOGL_DENSE && !grp && !ptmi_env("PTMI_GJ_NOPAIR", 0);
                 off += (size_t)(pair ? 2 : 1) * a.gj_lds_levels * gjw_level_doubles(E) + (pair ? 72 + 2 * GJ_BLOCK : 64);       // pair: + the 16 chains' step-size states
-            } else if (G == 16 && a.d <= 64 && !ptmi_env("PTMI_GJ_NOWIDE16", 0)) {
+            } else if (G == 16 && a.d <= 64 && !grp && !ptmi_env("PTMI_GJ_NOWIDE16", 0)) {
                 // the 16-lane shape at ndim <= 64: a gradient jump takes the whole wave (GradJumpWide<16, L, 16>, one element per lane);
                 // PTMI_GJ_NOWIDE16: the per-chain layout (a test hook, same results)
                 w16 = true;
@@ -93,6 +95,18 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
                     return PTMI_OK;
                 }
             }
+            if constexpr (L != PTMI_LOGL_INTERVAL) {        // (ptmi_create refuses the interval family with groups)
+                if (grp) {
+                    auto kern = mh_steps_gj_kernel<G, E, L, false, 0, true>;
+                    if (sizeof(double) * off > 64 * 1024) {
+                        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * off));
+                        if (e != hipSuccess) return fail(PTMI_EHIP, "hipFuncSetAttribute(%zu B of LDS): %s", sizeof(double) * off, hipGetErrorString(e));
+                    }
+                    hipLaunchKernelGGL(kern, dim3((unsigned)((nch + cpb - 1) / cpb)), dim3(GJ_BLOCK), sizeof(double) * off, h->stream, a);
+                    return PTMI_OK;
+                }
+            }
+            if (grp) return fail(PTMI_EUNSUPPORTED, "gradient jumps with parameter groups are not built for this likelihood family");
             if (sizeof(double) * off > 64 * 1024) {
                 hipError_t e = hipFuncSetAttribute((const void *)mh_steps_gj_kernel<G, E, L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * off));
                 if (e != hipSuccess) return fail(PTMI_EHIP, "hipFuncSetAttribute(%zu B of LDS): %s", sizeof(double) * off, hipGetErrorString(e));

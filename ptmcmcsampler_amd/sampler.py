@@ -914,7 +914,12 @@ class PTSampler(object):
                                                          int(nacc[r]) / iter if iter > 0 else 0, pt_acc))
         self.ind_next_write = write_end
         with open(self.outDir + "/jumps.txt", "w") as fout:
-            njumps = len(self.propCycle)
+            # gradient jumps served on the device are cycle entries of the engine, not of propCycle: listed with their share as the
+            # reference lists its jump objects (:226-258 add HMC, then NUTS, ahead of SCAM / AM)
+            dev_gj = [(name, w) for name, w in zip(("NUTSJUMP", "HMCJump"), getattr(self, "_grad_weights", (0, 0))) if w > 0]
+            njumps = len(self.propCycle) + sum(w for _, w in dev_gj)
+            for name, w in reversed(dev_gj):
+                fout.write("%s %4.2g\n" % (name, w / njumps))
             seen = []
             for jump in self.propCycle:
                 if jump not in seen:
