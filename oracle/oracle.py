@@ -38,12 +38,14 @@ class Cfg(C.Structure):
         ("seed", C.c_uint64), ("logl_par", _dp), ("logp_par", _dp), ("temps_mh", _dp), ("beta", _dp),
         ("gsize", _ip), ("gmask", _dp)] + [(n, C.c_int32) for n in (
         "w_nuts", "w_hmc", "gj_nburn", "hmc_min", "hmc_max", "nuts_maxdepth", "pick_mode")] + [
-        ("hmc_eps", C.c_double), ("nuts_delta", C.c_double), ("gj_tab", _dp)]
+        ("hmc_eps", C.c_double), ("nuts_delta", C.c_double), ("gj_tab", _dp), ("w_host", C.c_int32), ("replay_ref_order", C.c_int32),
+        ("cj_box", _ip), ("cj_boxpar", _dp)]
 
 
 class State(C.Structure):
     _fields_ = [("X", _dp), ("lnL", _dp), ("lp", _dp), ("temp_of", _ip), ("slot_of", _ip), ("Ut", _dp), ("S", _dp),
-                ("DE", _dp), ("AM", _dp), ("nacc", _up), ("jstat", _up), ("gj", _dp), ("AMflag", _up)]
+                ("DE", _dp), ("AM", _dp), ("nacc", _up), ("jstat", _up), ("gj", _dp), ("AMflag", _up), ("cjstat", _up), ("cj_pick", _ip),
+                ("cj_q", _dp), ("cj_qxy", _dp)]
 
 
 class Replay(C.Structure):
@@ -86,6 +88,9 @@ def lib():
         L.orc_index.restype = C.c_uint64
         L.orc_index.argtypes = [C.c_uint64, C.c_uint64]
         L.orc_mh_steps.argtypes = [C.POINTER(Cfg), C.POINTER(State), C.c_int64, C.c_int, C.POINTER(Replay)]
+        L.orc_mh_phase.argtypes = [C.POINTER(Cfg), C.POINTER(State), C.c_int64, C.c_int, C.c_int, C.POINTER(Replay)]
+        L.orc_cj_box_draw.restype = None
+        L.orc_cj_box_draw.argtypes = [C.c_uint64, C.c_int64, C.c_uint32, C.c_int, _dp, _dp, _dp]
         L.orc_swap_sweep.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_int64, C.c_uint64, C.c_int, _ip, _up,
                                      C.POINTER(Replay)]
         L.orc_swap_oddeven.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_int64, C.c_uint64, C.c_int, C.c_int, _ip, _up]
@@ -147,6 +152,15 @@ def philox(ctr, key):
     out = (C.c_uint32 * 4)()
     lib().orc_philox((C.c_uint32 * 4)(*ctr), (C.c_uint32 * 2)(*key), out)
     return [int(v) for v in out]
+
+
+def cj_box_draw(seed, it, sid, lo, hi):
+    """The box draw of a custom pick in counter mode (include/ptmi.h ptmi_cj_box_draw): parameter i = lo[i] + (hi[i] - lo[i]) * u, u the
+    53-bit uniform of word i & 1 of Philox at (seed, iter, the chain's stream id, 0x4000000 + (i >> 1))."""
+    lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+    q = np.empty(len(lo))
+    lib().orc_cj_box_draw(seed, it, sid, len(lo), _p(lo), _p(hi), _p(q))
+    return q
 
 
 def temperature_ladder(nchain, ndim, Tmin=1, Tmax=None):
@@ -327,6 +341,14 @@ class OracleEngine(object):
 
     Walker = an independent replica of the whole reference run (own ladder copy,
     own RNG streams; own cov/U/S/DE history when ``cov_mode='per_walker'``).
+
+    ``jumps=[(func, weight), ...]``: custom jumps in the cycle, the reference's ``addProposalToCycle`` before ``sample()``
+    (PTMCMCSampler.py:988-1014, dispatched at :1058-1059), as include/ptmi.h ``ptmi_cj_*`` defines them for the device: their cycle
+    entries come FIRST in the pick space (then SCAM, AM, DE once on, NUTS, HMC), ``beta = 1 / temps_mh[rank]``, ``iter`` the sampler's
+    iteration, no group drawn, ``qxy`` added in the accept test, ``jstat`` untouched, ``cjstat [W][nt][w_host][2]`` (proposed,
+    accepted) per pick index by rank.  ``func`` is ``("box", lo, hi)`` (every parameter redrawn as ``lo + (hi - lo) u``: counter mode
+    ``cj_box_draw``, replay mode ``ndim`` recorded uniforms) or a NumPy function ``(x[n, d], iter, beta[n]) -> (q[n, d], qxy[n] | 0 |
+    None)``, called once per iteration on all chains that picked it, ordered by (walker, slot).
     """
 
     def __init__(self, ndim, ntemps, nwalkers, cov0, ladder=None, logl=("iso",), logp=("flat",),
@@ -334,7 +356,7 @@ class OracleEngine(object):
                  cov_mode="per_walker", hot_chain=False, lanes=None, Tmin=1, Tmax=None,
                  ntemps_global=None, temp0=0, walker0=0, groups=None, swap_mode="sweep",
                  grad_weights=(0, 0), hmc=(0.1, 2, 300), nuts_delta=0.6, nuts_maxdepth=24, pick_mode="chain",
-                 eig_mode="lapack", am_mode="auto", eig_lag=0):
+                 eig_mode="lapack", am_mode="auto", eig_lag=0, jumps=None):
         assert eig_lag >= 0
         # the engine's eig_lag: the factorization of a covariance epoch takes effect eig_lag segments late (pooled covariance, one
         # parameter group; whichever eigensolver: the host's LAPACK, or the restated device ones)
@@ -394,6 +416,25 @@ class OracleEngine(object):
         self.gj[..., GJ_EPSBAR] = 1.0
         self.nswap = np.zeros((W, self.ntg), dtype=np.uint64)
         self.swap_proposed = 0
+        # custom jumps: pick index -> function; a box is drawn in C, anything else is the caller's function between the step's two phases
+        self._jumps, self._fun_of_pick, boxes = [], [], []
+        for func, weight in (jumps or ()):
+            assert int(weight) >= 1
+            if isinstance(func, tuple):
+                assert func[0] == "box"
+                boxes.append(np.concatenate([np.broadcast_to(np.asarray(func[k], dtype=np.float64), (d,)) for k in (1, 2)]))
+                func = len(boxes) - 1
+            self._jumps.append(func)
+            self._fun_of_pick += [len(self._jumps) - 1] * int(weight)
+        self.w_host = len(self._fun_of_pick)
+        self._cj_call = any(callable(f) for f in self._jumps)
+        self._cj_box = np.asarray([f if isinstance(f, int) else -1 for f in (self._jumps[k] for k in self._fun_of_pick)] or [-1], dtype=np.int32)
+        self._cj_boxpar = np.ascontiguousarray(np.concatenate(boxes)) if boxes else np.zeros(1)
+        self.cjstat = np.zeros((W, nt, self.w_host, 2), dtype=np.uint64)
+        self._cj_pick = np.full((W, nt), -1, dtype=np.int32)
+        self._cj_q = np.zeros((W, nt, d))
+        self._cj_qxy = np.zeros((W, nt))
+        assert not (self.w_host and sum(grad_weights)), "as the device: custom jumps are not mixed with gradient jumps"
         self._par_l = np.zeros(1)
         self._par_p = np.zeros(1)
         if logl[0] == "dense":
@@ -410,14 +451,16 @@ class OracleEngine(object):
                        beta=_p(self.beta), gsize=_p(self.gsize, _ip), gmask=_p(self.gmask),
                        w_nuts=self.grad_weights[0], w_hmc=self.grad_weights[1], gj_nburn=burn, hmc_eps=hmc[0],
                        hmc_min=hmc[1], hmc_max=hmc[2], nuts_maxdepth=nuts_maxdepth, nuts_delta=nuts_delta,
-                       gj_tab=_p(self.gj_tab), pick_mode={"chain": 0, "walker": 1}[pick_mode])
+                       gj_tab=_p(self.gj_tab), pick_mode={"chain": 0, "walker": 1}[pick_mode], w_host=self.w_host,
+                       replay_ref_order=0, cj_box=_p(self._cj_box, _ip), cj_boxpar=_p(self._cj_boxpar))
         self.iter = 0
 
     # -- helpers
     def _state(self):
         return State(_p(self.X), _p(self.lnL), _p(self.lp), _p(self.temp_of, _ip), _p(self.slot_of, _ip), _p(self.Ut),
                      _p(self.S), _p(self.DE), _p(self.AM) if self.temp0 == 0 else None, _p(self.nacc, _up),
-                     _p(self.jstat, _up), _p(self.gj), _p(self.AMflag, _up) if (self.temp0 == 0 and self.am_rle) else None)
+                     _p(self.jstat, _up), _p(self.gj), _p(self.AMflag, _up) if (self.temp0 == 0 and self.am_rle) else None,
+                     _p(self.cjstat, _up) if self.w_host else None, _p(self._cj_pick, _ip), _p(self._cj_q), _p(self._cj_qxy))
 
     def _svd(self, w):
         # LAPACK results depend on the BLAS thread count in the last bits, so the checker uses the product's rule:
@@ -536,8 +579,34 @@ class OracleEngine(object):
         self.swap_proposed += 1
         return m
 
-    def run(self, niter, replay=None, record=False):
-        """Advance ``niter`` iterations. ``replay``: list (one per rank) of (kinds, vals, bounds)."""
+    def _mh_steps(self, it, n, rp_arr):
+        """Iterations it .. it + n - 1 of every chain; with a caller's function among the custom jumps, one iteration at a time in two
+        phases with the functions between them."""
+        L, cfg, st = lib(), C.byref(self.cfg), self._state()
+        if not self._cj_call:
+            return L.orc_mh_steps(cfg, C.byref(st), it, n, rp_arr)
+        err = 0
+        for k in range(n):
+            err |= L.orc_mh_phase(cfg, C.byref(st), it + k, k, 1, rp_arr)
+            fun = np.where(self._cj_pick >= 0, np.asarray(self._fun_of_pick, dtype=np.int32)[np.maximum(self._cj_pick, 0)], -1)
+            for f, func in enumerate(self._jumps):
+                w, s = np.nonzero(fun == f)                            # (walker, slot) ascending: the device's listing order
+                if not len(w):
+                    continue                                           # a span of zero rows is not called
+                x = self.X[w, s].copy()
+                q, qxy = func(x, it + k, self.beta[self.temp_of[w, s]].copy())
+                self._cj_q[w, s] = np.asarray(q, dtype=np.float64).reshape(len(w), self.d)
+                self._cj_qxy[w, s] = 0.0 if qxy is None else np.broadcast_to(np.asarray(qxy, dtype=np.float64), (len(w),))
+            err |= L.orc_mh_phase(cfg, C.byref(st), it + k, k, 2, rp_arr)
+        return err
+
+    def run(self, niter, replay=None, record=False, cycle_order="oracle"):
+        """Advance ``niter`` iterations. ``replay``: list (one per rank) of (kinds, vals, bounds).  ``cycle_order`` (replay only): the
+        order of the cycle the RECORDED pick indexes count in -- "oracle": [custom, SCAM, AM, DE, NUTS, HMC], the order of counter mode;
+        "reference": [custom, HMC, NUTS, SCAM, AM, then DE from burn on], how the reference's sample() builds propCycle
+        (PTMCMCSampler.py:225-264, 575-585).  A fixture stores the raw recorded indexes."""
+        assert cycle_order in ("oracle", "reference") and (replay is not None or cycle_order == "oracle")
+        self.cfg.replay_ref_order = int(cycle_order == "reference")
         rp_arr, keep = None, []
         if replay is not None:
             assert self.W == 1
@@ -555,7 +624,7 @@ class OracleEngine(object):
         while it <= last:
             self._epochs(it)
             end = it if record else self._next_event(it, last)
-            err = lib().orc_mh_steps(C.byref(self.cfg), C.byref(self._state()), it, end - it + 1, rp_arr)
+            err = self._mh_steps(it, end - it + 1, rp_arr)
             assert err == 0, "replay error %d at iter %d" % (err, it)
             if self.tskip > 0 and self.ntg > 1 and end % self.tskip == 0:
                 self.swap(end, C.byref(rp_arr[0]) if rp_arr is not None else None)

@@ -70,10 +70,12 @@ static void philox_words(uint64_t seed, uint64_t iter, uint32_t stream, uint32_t
  *   slot 2 (G): w0 hi32 = parameter group (only drawn with more than one group)
  *   SWAP+k: w0 uniform of pair (k,k+1), stream of rank 0
  *   AM+k: (w0,w1) Box-Muller pair: cos branch -> eigen-direction k, sin branch -> direction k+lanes, (k/lanes) even
+ *   CJ+k: the box draw of a custom pick (include/ptmi.h ptmi_cj_box_draw): w0 -> parameter 2k, w1 -> parameter 2k+1, 53-bit uniforms
  * 64-bit words give 53-bit uniforms, 32-bit halves give 32-bit uniforms h * 2^-32 and indices (h * n) >> 32.
  * pick_mode WALKER takes the cycle pick from slot 0 of the stream of the walker's rank 0 instead of the chain's own. */
 enum { SLOT_P = 0, SLOT_Q = 1, SLOT_G = 2, SLOT_SWAP = 0x10000, SLOT_AM = 0x1000000,
-       SLOT_GJ = 0x2000000 /* + 4096 * (momenta draw of the call) + direction */, SLOT_GJS = 0x3000000 /* + scalar draw of the call */ };
+       SLOT_GJ = 0x2000000 /* + 4096 * (momenta draw of the call) + direction */, SLOT_GJS = 0x3000000 /* + scalar draw of the call */,
+       SLOT_CJ = 0x4000000 /* + (parameter / 2) of a box draw */ };
 enum { PICK_CHAIN = 0, PICK_WALKER = 1 };
 
 static inline uint32_t hi32(uint64_t w) { return (uint32_t)(w >> 32); }
@@ -332,6 +334,15 @@ typedef struct {
     const double *gj_tab;             /* [3][d][d] whitening tables from L = cholesky(cov0) (NJ:53-54), each used as
                                        * out[i] = sum_k T[k][i] v[k]:  backward T[k][i] = L[k][i] (x = L^T q),
                                        * forward T[k][i] = Linv[k][i] (q = Linv^T x), gradient T[k][i] = L[i][k] */
+    /* custom jumps in the cycle (PT:988-1014 addProposalToCycle, dispatched at PT:1058-1059; include/ptmi.h ptmi_cj_*): w_host cycle
+     * entries IN FRONT of SCAM / AM / DE / NUTS / HMC.  Pick index p < w_host is a box draw (cj_box[p] = k >= 0: every parameter redrawn
+     * as lo + (hi - lo) u from cj_boxpar + 2 d k = lo[d] | hi[d], qxy = 0: the reference's UniformJump, tests/test_simple.py:44-62) or a
+     * function of the caller (cj_box[p] < 0: orc_mh_phase hands the chain back between the pick and the accept test). */
+    int32_t w_host;
+    int32_t replay_ref_order;         /* REPLAY only: the recorded pick indexes the REFERENCE's cycle [custom, HMC, NUTS, SCAM, AM, DE]
+                                       * (PT:225-264, 575-585) and is mapped to the order above before it is used */
+    const int32_t *cj_box;            /* [w_host] */
+    const double *cj_boxpar;          /* [boxes][2][d] */
 } orc_cfg;
 
 typedef struct {
@@ -349,6 +360,10 @@ typedef struct {
     uint64_t *AMflag;   /* [W][cov_update]  the engine's AM row flags (include/ptmi.h AMflag), or NULL: bit 0 NEW = the step was
                          * accepted, bit 1 KEY = first step of a launch, ring rows 0 and 1, the swap's row.  The oracle stores every
                          * row whatever the flags say; they only weight the pooled statistics (orc_pool_update_rle) */
+    uint64_t *cjstat;   /* [W][ntemps][w_host][2]  (proposed, accepted) per custom pick index, by RANK (NULL without custom jumps) */
+    int32_t *cj_pick;   /* [W][ntemps] by SLOT: orc_mh_phase 1 leaves the pick index of a chain that waits for its caller's function, else -1 */
+    double *cj_q;       /* [W][ntemps][d] by SLOT: the caller's proposals for the waiting chains ... */
+    double *cj_qxy;     /* [W][ntemps]    ... and their qxy (PT:1059) */
 } orc_state;
 
 typedef struct {
@@ -807,9 +822,34 @@ ORC_API int orc_gradjump(const orc_cfg *c, int kind, const double *x, int64_t it
 }
 
 /* ------------------------------------------------------------ MH steps */
+/* the recorded pick of the reference's cycle [custom, HMC, NUTS, SCAM, AM, DE] as an index of the oracle's [custom, SCAM, AM, DE, NUTS, HMC] */
+static int pick_from_reference_order(const orc_cfg *c, int raw, int w_de)
+{
+    int i = raw - c->w_host;
+    if (i < 0) return raw;
+    if (i < c->w_hmc) return c->w_host + c->w_scam + c->w_am + w_de + c->w_nuts + i;
+    i -= c->w_hmc;
+    if (i < c->w_nuts) return c->w_host + c->w_scam + c->w_am + w_de + i;
+    i -= c->w_nuts;
+    return c->w_host + i;                                           /* SCAM, AM, DE: the same order in both */
+}
+
+/* the box draw of a custom pick in counter mode: include/ptmi.h ptmi_cj_box_draw */
+ORC_API void orc_cj_box_draw(uint64_t seed, int64_t iter, uint32_t sid, int d, const double *lo, const double *hi, double *q)
+{
+    for (int i = 0; i < d; ++i) {
+        uint64_t Wd[2];
+        philox_words(seed, (uint64_t)iter, sid, SLOT_CJ + (uint32_t)(i >> 1), Wd);
+        q[i] = lo[i] + (hi[i] - lo[i]) * w2uniform(Wd[i & 1]);
+    }
+}
+
 /* One Metropolis-Hastings update of one chain: PT:601-622 with _jump PT:1048-1067,
- * SCAM PT:820-876, AM PT:879-933, DE PT:936-985. */
-static void mh_one(const orc_cfg *c, orc_state *st, int w, int s, int64_t it, orc_replay *rp, double *buf, int k /* step of the launch */)
+ * SCAM PT:820-876, AM PT:879-933, DE PT:936-985.
+ * phase 0: the whole step.  Phases 1 and 2 split it for custom jumps that are functions of the caller: phase 1 is the whole step for
+ * every chain but those whose pick is such a function -- they stop behind the pick (cj_pick) --, phase 2 finishes those from the
+ * caller's proposal (cj_q, cj_qxy).  Chains do not read each other's state inside an iteration, so the order does not matter. */
+static void mh_one(const orc_cfg *c, orc_state *st, int w, int s, int64_t it, orc_replay *rp, double *buf, int k /* step of the launch */, int phase)
 {
     const int d = c->ndim, nt = c->ntemps;
     const size_t ch = (size_t)w * nt + s;
@@ -827,21 +867,29 @@ static void mh_one(const orc_cfg *c, orc_state *st, int w, int s, int64_t it, or
 
     /* pick from the weighted cycle (PT:1058); pick_mode WALKER: the draw of the walker's rank 0 serves all its ranks */
     const int w_de = c->de_on ? c->w_de : 0;
-    const int L = c->w_scam + c->w_am + w_de + c->w_nuts + c->w_hmc;
+    const int L = c->w_host + c->w_scam + c->w_am + w_de + c->w_nuts + c->w_hmc;
     uint32_t pickw = hi32(P[0]);
+    if (phase == 2 && st->cj_pick[ch] < 0) return;
     if (!r && c->pick_mode == PICK_WALKER) {
         uint64_t P0[2];
         philox_words(c->seed, (uint64_t)it, (uint32_t)((uint64_t)(c->walker0 + w) * (uint32_t)c->ntemps_global), SLOT_P, P0);
         pickw = hi32(P0[0]);
     }
-    const int ind = r ? (int)rp_next(r, K_INT, L) : (int)h2index(pickw, (uint32_t)L);
-    const int jt = ind < c->w_scam ? J_SCAM : (ind < c->w_scam + c->w_am ? J_AM : (ind < c->w_scam + c->w_am + w_de ? J_DE :
+    int pick;
+    if (phase == 2) pick = st->cj_pick[ch];                         /* drawn in phase 1 */
+    else if (r) { pick = (int)rp_next(r, K_INT, L); if (c->replay_ref_order) pick = pick_from_reference_order(c, pick, w_de); }
+    else pick = (int)h2index(pickw, (uint32_t)L);
+    const int cjp = pick < c->w_host ? pick : -1;                   /* a custom pick: the w_host entries come first */
+    if (st->cj_pick && phase != 2) st->cj_pick[ch] = -1;
+    if (phase == 1 && cjp >= 0 && c->cj_box[cjp] < 0) { st->cj_pick[ch] = cjp; return; }
+    const int ind = pick - c->w_host;
+    const int jt = cjp >= 0 ? -1 : ind < c->w_scam ? J_SCAM : (ind < c->w_scam + c->w_am ? J_AM : (ind < c->w_scam + c->w_am + w_de ? J_DE :
                    (ind < c->w_scam + c->w_am + w_de + c->w_nuts ? J_NUTS : J_HMC)));
     double qxy = 0.0;
 
     /* group pick (PT:839,897,955); counter mode: its own Philox call, drawn only when there is a choice */
     int g = 0;
-    if (jt >= J_NUTS) g = 0;                                        /* the gradient jumps move all parameters */
+    if (jt >= J_NUTS || cjp >= 0) g = 0;                            /* the gradient jumps move all parameters; a custom jump draws no group (PT:1059) */
     else if (r) g = (int)rp_next(r, K_INT, ngr);
     else if (ngr > 1) {
         uint64_t Gw[2];
@@ -852,7 +900,16 @@ static void mh_one(const orc_cfg *c, orc_state *st, int w, int s, int64_t it, or
     const double *Ut = st->Ut + (wc * ngr + g) * (size_t)d * d, *S = st->S + (wc * ngr + g) * (size_t)d;
     const double *gm = (c->ngroups > 1) ? c->gmask + (size_t)g * d : NULL;
 
-    if (jt >= J_NUTS) {
+    if (cjp >= 0) {
+        if (phase == 2) {                                           /* q, qxy = func(x, iter, 1 / temp) (PT:1059), made by the caller */
+            memcpy(q, st->cj_q + ch * d, sizeof(double) * d);
+            qxy = st->cj_qxy[ch];
+        } else {
+            const double *lo = c->cj_boxpar + (size_t)c->cj_box[cjp] * 2 * d, *hi = lo + d;
+            if (r) for (int i = 0; i < d; ++i) q[i] = lo[i] + (hi[i] - lo[i]) * rp_next(r, K_UNI, 0);
+            else orc_cj_box_draw(c->seed, it, sid, d, lo, hi, q);
+        }
+    } else if (jt >= J_NUTS) {
         gj_ctx G = { c, beta, (double *)malloc(sizeof(double) * 5 * (size_t)d), 0 };
         gj_rng rng = { r, c->seed, (uint64_t)it, sid, 0, 0, c->lanes };
         double *gst = st->gj + ((size_t)w * nt + t) * GJ_NSTATE;
@@ -921,7 +978,9 @@ static void mh_one(const orc_cfg *c, orc_state *st, int w, int s, int64_t it, or
         for (int i = 0; i < d; ++i)
             q[i] = (!gm || gm[i] != 0.0) ? x[i] + scale * (DE[(size_t)mm * d + i] - DE[(size_t)nn * d + i]) : x[i] + 0.0;
     }
-    st->jstat[(((size_t)w * nt + t) * J_NTYPES + jt) * 2 + 0] += 1;
+    uint64_t *stat = cjp >= 0 ? st->cjstat + (((size_t)w * nt + t) * c->w_host + cjp) * 2      /* PT:602, 622: per cycle entry here */
+                              : st->jstat + (((size_t)w * nt + t) * J_NTYPES + jt) * 2;
+    stat[0] += 1;
 
     /* prior, likelihood, tempering (PT:605-612) */
     const double lp = eval_logp(c, q);
@@ -939,7 +998,7 @@ static void mh_one(const orc_cfg *c, orc_state *st, int w, int s, int64_t it, or
         memcpy(x, q, sizeof(double) * d);
         st->lnL[ch] = newlnL; st->lp[ch] = lp;
         st->nacc[(size_t)w * nt + t] += 1;
-        st->jstat[(((size_t)w * nt + t) * J_NTYPES + jt) * 2 + 1] += 1;
+        stat[1] += 1;
     }
 
     /* AM buffer (PT:327-328): the rank-0 chain, unless a swap follows this iteration
@@ -960,7 +1019,20 @@ ORC_API int orc_mh_steps(const orc_cfg *c, orc_state *st, int64_t iter0, int nst
     double *buf = (double *)malloc(sizeof(double) * 4 * (size_t)c->ndim);
     for (int k = 0; k < nsteps; ++k)
         for (int w = 0; w < c->nwalkers; ++w)
-            for (int s = 0; s < c->ntemps; ++s) mh_one(c, st, w, s, iter0 + k, rp, buf, k);
+            for (int s = 0; s < c->ntemps; ++s) mh_one(c, st, w, s, iter0 + k, rp, buf, k, 0);
+    free(buf);
+    int64_t err = 0;
+    if (rp) for (int t = 0; t < c->ntemps; ++t) err |= rp[t].err;
+    return (int)err;
+}
+
+/* ONE iteration in two calls, for custom jumps that are functions of the caller (mh_one): phase 1, the caller's functions on the chains
+ * that cj_pick lists (x = the chain's state, iter, beta = 1 / temps_mh of its rank), phase 2.  k: the step of the segment (AMflag). */
+ORC_API int orc_mh_phase(const orc_cfg *c, orc_state *st, int64_t iter, int k, int phase, orc_replay *rp)
+{
+    double *buf = (double *)malloc(sizeof(double) * 4 * (size_t)c->ndim);
+    for (int w = 0; w < c->nwalkers; ++w)
+        for (int s = 0; s < c->ntemps; ++s) mh_one(c, st, w, s, iter, rp, buf, k, phase);
     free(buf);
     int64_t err = 0;
     if (rp) for (int t = 0; t < c->ntemps; ++t) err |= rp[t].err;

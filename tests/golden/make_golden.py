@@ -12,7 +12,8 @@ recording proxy, and for multi-temperature runs give every rank (one thread
 each) an in-process fake communicator implementing the eight duck-typed
 methods the reference calls.
 
-Usage:  python tests/golden/make_golden.py
+Usage:  python tests/golden/make_golden.py [--out DIR] [ladder proposals welford debuffer ptswap trajectories cycle gradjump interval
+config1 resume]      (no names: all of them)
 """
 import copy
 import os
@@ -28,7 +29,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REF = "/root/reference"
 
 # draw kinds in the recorded stream
-K_INT, K_UNI, K_NRM, K_SHUF = 0, 1, 2, 3
+K_INT, K_UNI, K_NRM, K_SHUF, K_EXP = 0, 1, 2, 3, 4
 
 
 def import_reference():
@@ -44,9 +45,10 @@ def import_reference():
 class RecordingStream(object):
     """Proxy around a numpy Generator that logs every draw, in order."""
 
-    def __init__(self, gen):
+    def __init__(self, gen, glob_seed=0):
         self.gen = gen
         self.kinds, self.vals, self.bounds = [], [], []
+        self.glob = np.random.RandomState(glob_seed)       # what serves this rank's GLOBAL np.random calls (GlobalDraws)
 
     def _log(self, kind, vals, bound=0):
         for v in np.atleast_1d(vals):
@@ -78,12 +80,101 @@ class RecordingStream(object):
         self.gen.shuffle(arr)
         self._log(K_SHUF, 0.0, len(arr))
 
+    # the global np.random functions nutsjump.py calls, logged into the same stream in call order (GlobalDraws)
+    def g_randn(self, *shape):
+        r = self.glob.randn(*shape)
+        self._log(K_NRM, r)
+        return r
+
+    def g_randint(self, lo, hi=None):
+        r = self.glob.randint(lo, hi)
+        self._log(K_INT, r, hi if hi is not None else lo)
+        return r
+
+    def g_uniform(self, *a, **k):
+        r = self.glob.uniform(*a, **k)
+        self._log(K_UNI, r)
+        return r
+
+    def g_exponential(self, *a, **k):
+        r = self.glob.exponential(*a, **k)
+        self._log(K_EXP, r)
+        return r
+
     def arrays(self):
         return (
             np.asarray(self.kinds, dtype=np.uint8),
             np.asarray(self.vals, dtype=np.float64),
             np.asarray(self.bounds, dtype=np.int64),
         )
+
+
+class ReplayStream(object):
+    """Stand-in for a rank's stream AND its global np.random calls that hands back recorded draws, checking kind and bound: the
+    reference run a second time on the draws of the first (run_traj, floor_chain)."""
+
+    def __init__(self, kinds, vals, bounds):
+        self.k, self.v, self.b, self.pos = kinds, vals, bounds, 0
+
+    def _take(self, kind, size=None, bound=None):
+        n = 1 if size is None else int(np.prod(size))
+        out = np.empty(n)
+        for i in range(n):
+            assert self.k[self.pos] == kind and (bound is None or self.b[self.pos] == bound), (self.pos, kind, self.k[self.pos])
+            out[i] = self.v[self.pos]
+            self.pos += 1
+        return out[0] if size is None else out.reshape(size)
+
+    def integers(self, low, high=None, size=None):
+        r = self._take(K_INT, size, high if high is not None else low)
+        return int(r) if size is None else r.astype(np.int64)
+
+    def random(self, size=None):
+        return self._take(K_UNI, size)
+
+    def uniform(self):
+        return self._take(K_UNI)
+
+    def standard_normal(self, size=None):
+        return self._take(K_NRM, size)
+
+    def shuffle(self, arr):
+        self._take(K_SHUF)                                 # randomizedPropCycle is never read (PTMCMCSampler.py:1045, 1059)
+
+    def g_randn(self, *shape):
+        return self._take(K_NRM, shape if shape else None)
+
+    def g_randint(self, lo, hi=None):
+        return int(self._take(K_INT, None, hi if hi is not None else lo))
+
+    def g_uniform(self):
+        return self._take(K_UNI)
+
+    def g_exponential(self, scale=1.0, size=None):
+        return self._take(K_EXP, size)
+
+
+class GlobalDraws(object):
+    """While active, np.random.randn / randint / uniform / exponential -- the calls of nutsjump.py -- go to the stream of the rank
+    whose thread calls them (register())."""
+
+    NAMES = ("randn", "randint", "uniform", "exponential")
+
+    def __init__(self):
+        self.streams = {}
+
+    def register(self, stream):
+        self.streams[threading.get_ident()] = stream
+
+    def __enter__(self):
+        self.orig = [getattr(np.random, n) for n in self.NAMES]
+        for n in self.NAMES:
+            setattr(np.random, n, (lambda name: lambda *a, **k: getattr(self.streams[threading.get_ident()], "g_" + name)(*a, **k))(n))
+        return self
+
+    def __exit__(self, *exc):
+        for n, f in zip(self.NAMES, self.orig):
+            setattr(np.random, n, f)
 
 
 class ForcedUniform(object):
@@ -343,49 +434,99 @@ def gen_ptswap(PT, out, tmp):
     np.savez_compressed(os.path.join(out, "ptswap.npz"), **res)
 
 
-def run_traj(PT, name, out, ndim, nranks, logl, logp, p0, cov0, sample_kw, seed, extra=None, hot=False, groups=None):
-    """Full sample() run with per-rank recorded draws and per-epoch cov snapshots."""
+def run_traj(PT, name, out, ndim, nranks, logl, logp, p0, cov0, sample_kw, seed, extra=None, hot=False, groups=None, grad=None,
+             jumps=None):
+    """Full sample() run with per-rank recorded draws and per-epoch cov snapshots.
+
+    grad = (logl_grad, logp_grad, logl_grad_long, logp_grad_long): gradient jumps in the cycle.  The global np.random calls of
+    nutsjump.py are recorded into the calling rank's stream in call order (GlobalDraws); the run is then repeated on the recorded
+    draws (ReplayStream) with the gradient callbacks evaluated in np.longdouble and rounded back to double: both runs must take the
+    same decisions, and their largest chain deviation relative to max(1, |chain|) is the fixture's rounding floor ``floor_chain``.
+    jumps = [(make(sampler) -> func, weight), ...]: addProposalToCycle before sample(), as tests/test_simple.py:94-95 does."""
     tmp = tempfile.mkdtemp()
-    world = World(nranks)
-    samplers = [None] * nranks
-    epochs = []
-    errs = []
+    gd = GlobalDraws()
 
-    def rank_main(r):
-        try:
-            comm = ThreadComm(world, r) if nranks > 1 else None
-            kw = dict(outDir=tmp, verbose=False, seed=seed)
-            if groups is not None:
-                kw["groups"] = [np.asarray(g) for g in groups]
-            if comm is not None:
-                kw["comm"] = comm
-            s = PT.PTSampler(ndim, logl, logp, np.copy(cov0), **kw)
-            s.stream = RecordingStream(s.stream)
-            samplers[r] = s
-            if r == 0:
-                orig = s._updateRecursive
+    def run_once(make_stream, gl, gp):
+        world = World(nranks)
+        samplers = [None] * nranks
+        epochs = []
+        errs = []
 
-                def snap(it, mem):
-                    orig(it, mem)
-                    epochs.append((it, s.mu.copy(), s.M2.copy(), s.cov.copy(), s.U[0].copy(), s.S[0].copy()))
+        def rank_main(r):
+            try:
+                comm = ThreadComm(world, r) if nranks > 1 else None
+                kw = dict(outDir=tmp, verbose=False, seed=seed)
+                if groups is not None:
+                    kw["groups"] = [np.asarray(g) for g in groups]
+                if comm is not None:
+                    kw["comm"] = comm
+                if gl is not None:
+                    kw["logl_grad"], kw["logp_grad"] = gl, gp
+                s = PT.PTSampler(ndim, logl, logp, np.copy(cov0), **kw)
+                s.stream = make_stream(r, s.stream)
+                gd.register(s.stream)
+                samplers[r] = s
+                for make, weight in (jumps or ()):
+                    s.addProposalToCycle(make(s), weight)
+                if r == 0:
+                    orig = s._updateRecursive
 
-                s._updateRecursive = snap
-            s.sample(np.copy(p0), hotChain=hot, **sample_kw)
-        except BaseException as e:  # noqa
-            errs.append(e)
-            world.bar.abort()
-            raise
+                    def snap(it, mem):
+                        orig(it, mem)
+                        epochs.append((it, s.mu.copy(), s.M2.copy(), s.cov.copy(), s.U[0].copy(), s.S[0].copy()))
 
-    if nranks == 1:
-        rank_main(0)
-    else:
-        th = [threading.Thread(target=rank_main, args=(r,)) for r in range(nranks)]
-        [t.start() for t in th]
-        [t.join() for t in th]
-    if errs:
-        raise errs[0]
+                    s._updateRecursive = snap
+                s.sample(np.copy(p0), hotChain=hot, **sample_kw)
+            except BaseException as e:  # noqa
+                errs.append(e)
+                world.bar.abort()
+                raise
+
+        if nranks == 1:
+            rank_main(0)
+        else:
+            th = [threading.Thread(target=rank_main, args=(r,)) for r in range(nranks)]
+            [t.start() for t in th]
+            [t.join() for t in th]
+        if errs:
+            raise errs[0]
+        return samplers, epochs
+
+    import contextlib
+    import io
+    with gd, contextlib.redirect_stdout(io.StringIO()):            # (the jump objects print a warning each)
+        samplers, epochs = run_once(lambda r, gen: RecordingStream(gen, glob_seed=seed + 7919 * (r + 1)), *(grad[:2] if grad else (None, None)))
+        draws = [s.stream.arrays() for s in samplers]
+        if grad:
+            again, _ = run_once(lambda r, gen: ReplayStream(*draws[r]), *grad[2:])
 
     res = dict(extra or {})
+    checks = []
+    if grad:
+        floor = 0.0
+        for a, b in zip(samplers, again):
+            assert b.stream.pos == len(b.stream.k), "the second run left draws unused"
+            assert (a.naccepted, a.nswap_accepted, a.jumpDict) == (b.naccepted, b.nswap_accepted, b.jumpDict), \
+                "%s: the two reference runs decide differently -- the seed sits on a tie" % name
+            floor = max(floor, float(np.max(np.abs(a._chain - b._chain) / np.maximum(1.0, np.abs(a._chain)))))
+        assert floor <= 1e-9, "%s: floor_chain %.3g > 1e-9" % (name, floor)
+        res["floor_chain"] = floor
+        checks.append("same decisions in both runs; floor_chain = %.3g <= 1e-9" % floor)
+        for r, s in enumerate(samplers):
+            nuts = [f for f in s.propCycle if getattr(f, "name", "") == "NUTSJUMP"]
+            if nuts:                                       # the rank's step size after its last call, and how many there were
+                res["nuts_eps_%d" % r], res["nuts_calls_%d" % r] = float(nuts[0].epsilon), int(nuts[0].iter)
+    if grad or jumps:
+        for r, s in enumerate(samplers):
+            for nm, (prop, acc) in s.jumpDict.items():
+                assert prop > 0 and acc > 0, "%s: rank %d never %s a %s" % (name, r, "accepted" if prop else "proposed", nm)
+        checks.append("every jump type proposed and accepted at every rank")
+        if nranks > 1:
+            assert samplers[0].swapProposed > 0 and all(s.nswap_accepted > 0 for s in samplers[:-1]), "%s: a pair never swapped" % name
+            checks.append("nswap > 0 for every pair: %s" % [int(s.nswap_accepted) for s in samplers[:-1]])
+    if jumps:
+        res["custom_names"] = np.asarray([make(samplers[0]).__name__ for make, _ in jumps])
+        res["custom_weights"] = np.asarray([w for _, w in jumps])
     if groups is not None:
         res["groups_flat"] = np.concatenate([np.asarray(g) for g in groups])
         res["groups_size"] = np.asarray([len(g) for g in groups])
@@ -419,6 +560,10 @@ def run_traj(PT, name, out, ndim, nranks, logl, logp, p0, cov0, sample_kw, seed,
     res["chainfile_nlines"] = len(lines)
     np.savez_compressed(os.path.join(out, name + ".npz"), **res)
     print(name, "ranks", nranks, "epochs", len(epochs), "acc", [s.naccepted for s in samplers])
+    for c in checks:
+        print("   ", c)
+    if grad or jumps:
+        print("   ", {r: dict(s.jumpDict) for r, s in enumerate(samplers)})
 
 
 def gen_trajectories(PT, out):
@@ -461,6 +606,98 @@ def gen_trajectories(PT, out):
     run_traj(PT, "traj_pt2_scam_d100", out, d, 2, iso_logl, flat_logp, np.zeros(d), np.eye(d) * 0.01,
              dict(Niter=200, covUpdate=1000, burn=10000, thin=1, isave=100, Tskip=20,
                   SCAMweight=20, AMweight=0, DEweight=0), seed=1234)
+
+
+class DenseGrad(Dense):
+    """The dense Gaussian with its gradient as the reference's logl_grad wants it: (value, gradient)."""
+
+    def grad(self, x):
+        diff = x - self.mu
+        v = np.dot(self.icov, diff)
+        return -np.dot(diff, v) / 2.0, -v
+
+    def grad_long(self, x):                                # in np.longdouble, rounded back to double (run_traj's second run)
+        diff = x.astype(np.longdouble) - self.mu.astype(np.longdouble)
+        v = np.dot(self.icov.astype(np.longdouble), diff)
+        return float(-np.dot(diff, v) / 2), (-v).astype(np.float64)
+
+
+def flat_grad(x):
+    return 0.0, np.zeros_like(x)
+
+
+def uniform_jump(lo, hi):
+    """tests/test_simple.py:44-62 (UniformJump) restated on the sampler's own stream, so that its draws are recorded: d uniforms u,
+    q = lo + (hi - lo) u, which is what np.random.uniform(lo, hi, d) computes."""
+    def make(s):
+        def UniformJump(x, it, beta):
+            return lo + (hi - lo) * s.stream.random(len(x)), 0
+
+        return UniformJump
+
+    return make
+
+
+def shrink_jump(s):
+    """A deterministic jump: qxy = -0.1 beta, a shift that depends on the iteration; one IEEE operation per element and step."""
+    def shrinkJump(x, it, beta):
+        return x * 0.5 + (0.25 * beta + 0.01 * float((it % 7) - 3)), -0.1 * beta
+
+    return shrinkJump
+
+
+def gen_cycle(PT, out):
+    """The COMPOSED cycle run by the reference's sample(): gradient jumps (NUTS / HMC, PTMCMCSampler.py:225-258) beside SCAM / AM / DE,
+    alone, tempered and with parameter groups; and custom jumps added with addProposalToCycle (tests/test_simple.py:94-97)."""
+    rs = np.random.RandomState(19)
+
+    def target(d, spread=0.0):
+        A = rs.randn(d, d)
+        C = A @ A.T / d + 0.4 * np.eye(d)
+        P = np.linalg.inv(C)
+        return rs.randn(d) * spread, (P + P.T) / 2.0, C
+
+    gkw = dict(thin=1, MALAweight=0, HMCstepsize=0.1, HMCsteps=12)   # (sample() defaults MALAweight to 20)
+    # G1: one chain; burn inside the run: NUTS goes from adaptation to its frozen step size, DE joins the cycle
+    d = 6
+    mu, P, C = target(d, 0.5)
+    L = DenseGrad(mu, P)
+    run_traj(PT, "traj_grad_single_d6", out, d, 1, L, flat_logp, mu + rs.randn(d) * 0.3, C * 0.8,
+             dict(Niter=300, covUpdate=50, burn=100, isave=100, Tskip=100, SCAMweight=20, AMweight=20, DEweight=20, NUTSweight=10,
+                  HMCweight=10, **gkw), seed=811, extra=dict(dense_mu=mu, dense_icov=P), grad=(L.grad, flat_grad, L.grad_long, flat_grad))
+    # G2: three ranks, swaps every 10: the jump objects stay with their rank, beta < 1 inside the trees
+    d = 5
+    mu, P, C = target(d, 0.5)
+    L = DenseGrad(mu, P)
+    run_traj(PT, "traj_grad_pt3_d5", out, d, 3, L, flat_logp, mu + rs.randn(d) * 0.3, C * 0.8,
+             dict(Niter=300, covUpdate=50, burn=100, isave=100, Tskip=10, SCAMweight=20, AMweight=20, DEweight=20, NUTSweight=10,
+                  HMCweight=10, **gkw), seed=812, extra=dict(dense_mu=mu, dense_icov=P), grad=(L.grad, flat_grad, L.grad_long, flat_grad))
+    # G3 / G4: parameter groups (no group drawn on a gradient pick; whitening from the full initial covariance)
+    d = 6
+    mu, P, C = target(d, 0.5)
+    L = DenseGrad(mu, P)
+    run_traj(PT, "traj_grad_groups_d6", out, d, 1, L, flat_logp, mu + rs.randn(d) * 0.3, C * 0.8,
+             dict(Niter=300, covUpdate=50, burn=100, isave=100, Tskip=100, SCAMweight=20, AMweight=20, DEweight=20, NUTSweight=10,
+                  HMCweight=10, **gkw), seed=813, extra=dict(dense_mu=mu, dense_icov=P), grad=(L.grad, flat_grad, L.grad_long, flat_grad),
+             groups=[[0, 1, 2], [3, 4, 5]])
+    mu, P, C = target(d, 0.5)
+    L = DenseGrad(mu, P)
+    run_traj(PT, "traj_grad_groups_pt2_d6", out, d, 2, L, flat_logp, mu + rs.randn(d) * 0.3, C * 0.8,
+             dict(Niter=300, covUpdate=50, burn=100, isave=100, Tskip=10, SCAMweight=20, AMweight=20, DEweight=20, NUTSweight=10,
+                  HMCweight=10, **gkw), seed=814, extra=dict(dense_mu=mu, dense_icov=P), grad=(L.grad, flat_grad, L.grad_long, flat_grad),
+             groups=[[0, 1, 2, 3, 4, 5], [3, 1], [2]])
+    # C1: the cycle of tests/test_simple.py at small size: UniformJump (weight 5) and a deterministic jump (weight 3), box prior, two ranks
+    d = 4
+    mu, P, C = target(d, 0.2)
+    lo, hi = -2.0 - 0.1 * np.arange(d), 1.8 + 0.1 * np.arange(d)
+    run_traj(PT, "traj_custom_d4", out, d, 2, Dense(mu, P), Box(lo, hi), rs.uniform(-0.5, 0.5, d), np.eye(d) * 0.05,
+             dict(Niter=400, covUpdate=50, burn=150, thin=1, isave=100, Tskip=10, SCAMweight=20, AMweight=20, DEweight=20), seed=815,
+             extra=dict(box_lo=lo, box_hi=hi, dense_mu=mu, dense_icov=P), jumps=[(uniform_jump(lo, hi), 5), (shrink_jump, 3)])
+    # C2: the deterministic jump with parameter groups (a custom pick draws no group)
+    d = 5
+    run_traj(PT, "traj_custom_groups_d5", out, d, 2, iso_logl, flat_logp, rs.randn(d) * 0.3, np.eye(d) * 0.05,
+             dict(Niter=400, covUpdate=50, burn=150, thin=1, isave=100, Tskip=10, SCAMweight=20, AMweight=20, DEweight=20), seed=816,
+             jumps=[(shrink_jump, 3)], groups=[[0, 1, 2, 3, 4], [3, 1], [2]])
 
 
 def gen_gradjump(out):
@@ -652,23 +889,27 @@ def gen_resume(PT, out):
     np.savez_compressed(os.path.join(out, "resume.npz"), **res)
 
 
-def main():
+def main(argv):
+    out = HERE
+    if "--out" in argv:
+        k = argv.index("--out")
+        out = argv[k + 1]
+        argv = argv[:k] + argv[k + 2:]
     PT = import_reference()
     tmp = tempfile.mkdtemp()
-    gen_ladder(PT, HERE)
-    gen_proposals(PT, HERE, tmp)
-    gen_welford(PT, HERE, tmp)
-    gen_debuffer(PT, HERE, tmp)
-    gen_ptswap(PT, HERE, tmp)
-    gen_trajectories(PT, HERE)
-    gen_gradjump(HERE)
-    gen_interval(HERE)
-    gen_config1(PT, HERE)
-    gen_resume(PT, HERE)
-    for f in sorted(os.listdir(HERE)):
+    gens = [("ladder", lambda: gen_ladder(PT, out)), ("proposals", lambda: gen_proposals(PT, out, tmp)),
+            ("welford", lambda: gen_welford(PT, out, tmp)), ("debuffer", lambda: gen_debuffer(PT, out, tmp)),
+            ("ptswap", lambda: gen_ptswap(PT, out, tmp)), ("trajectories", lambda: gen_trajectories(PT, out)),
+            ("cycle", lambda: gen_cycle(PT, out)), ("gradjump", lambda: gen_gradjump(out)), ("interval", lambda: gen_interval(out)),
+            ("config1", lambda: gen_config1(PT, out)), ("resume", lambda: gen_resume(PT, out))]
+    assert all(a in dict(gens) for a in argv), "unknown fixture group in %r" % (argv,)
+    for name, gen in gens:
+        if not argv or name in argv:
+            gen()
+    for f in sorted(os.listdir(out)):
         if f.endswith(".npz"):
-            print("%-28s %8d B" % (f, os.path.getsize(os.path.join(HERE, f))))
+            print("%-28s %8d B" % (f, os.path.getsize(os.path.join(out, f))))
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])
