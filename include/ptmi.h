@@ -471,13 +471,49 @@ int ptmi_gj_step(ptmi_handle h, void *work, const double *lnl /* dev [n] */, con
  * work: caller-owned device memory of ptmi_cj_work_bytes bytes, 16-byte aligned (the list, the listing's block counts, the offsets);
  * rows: device [W*T][ndim]; beta: device [W*T].  ptmi_accept / ptmi_accept_propose refuse (PTMI_EINVAL) while the stage of the current
  * proposals of an attached handle has not ended; so do these calls out of sequence.  Not in ptmi_device_iter mode
- * (PTMI_EUNSUPPORTED); parameter groups are fine (the stage never looks at them).  ptmi_create still refuses w_host > 0 together with
- * w_nuts + w_hmc > 0.  On the handle's stream. */
+ * (PTMI_EUNSUPPORTED); parameter groups are fine (the stage never looks at them).
+ * Beside gradient jumps: a split handle (ptmi_buffers.Q) takes w_host > 0 together with w_nuts + w_hmc > 0 -- the reference's cycle
+ * [custom entries, HMC, NUTS, SCAM, AM, DE] (PT:225-264, 988-1014), here in the pick order [custom, SCAM, AM, DE, NUTS, HMC] that propose()
+ * and the oracle's mh_one define.  Per proposal launch BOTH stages then run, ptmi_gj_begin / ptmi_gj_step ... and ptmi_cj_begin / ... /
+ * ptmi_cj_end, in either order: they serve disjoint chains (qaux[.][1] is PTMI_J_NUTS / PTMI_J_HMC, or >= PTMI_J_NTYPES), each writes
+ * its own chains' rows of the proposal buffer and their qaux[.][0] only, and ptmi_accept / ptmi_accept_propose refuse until both have
+ * ended.  Without the split buffers ptmi_create keeps refusing the combination, and ptmi_mh_steps refuses w_host > 0 as before.  On
+ * the handle's stream. */
 int ptmi_cj_attach(ptmi_handle h, uint64_t *cjstat /* dev [W][T][w_host][2] */, const int32_t *fun_of_pick /* host [w_host] */, int32_t nfun);
 int ptmi_cj_work_bytes(ptmi_handle h, size_t *bytes);
 int ptmi_cj_begin(ptmi_handle h, int64_t iter, void *work, double *rows /* dev [W*T][ndim] */, double *beta /* dev [W*T] */, int64_t *offs /* host [nfun+1] */);
 int ptmi_cj_end(ptmi_handle h, void *work, const double *rows /* dev [n][ndim] */, const double *qxy /* dev [n] or NULL: zeros */);
 int ptmi_cj_box_draw(ptmi_handle h, void *work, int32_t fun, const double *lo, const double *hi /* dev [ndim] */, double *rows /* dev: that function's span */);
+
+/* Auxiliary jumps as BATCHED device callbacks on the split path (csrc/ptmi_aux.hip): addAuxilaryJump(func) of the reference (PT:1017-1028)
+ * and the loop that runs every auxiliary jump on the result of the cycle entry, q, qxy_aux = aux(x, q, iter, beta); qxy += qxy_aux
+ * (PT:1062-1065), for EVERY chain at once.  Per proposal launch (ptmi_propose(iter), or the propose half of ptmi_accept_propose(iter - 1)),
+ * behind the gradient stage and the custom-jump stage where the handle has them:
+ *
+ *     ptmi_aux_begin(h, iter, xrows, beta);
+ *     ptmi_proposals(h, &Q);
+ *     for every auxiliary function, in the order they were added: (Q, qxy) = aux(xrows, Q, iter, beta), the qxy summed
+ *     ptmi_aux_end(h, Q or NULL, qxy or NULL);
+ *     likelihood callback on the proposals (ptmi_proposals), then ptmi_accept / ptmi_accept_propose
+ *
+ * ptmi_aux_attach (once, before the first ptmi_propose; a split handle: Q and qaux) declares that every proposal launch is followed by
+ * this stage: ptmi_accept / ptmi_accept_propose then refuse (PTMI_EINVAL) while the stage of the current proposals is pending or open.
+ * ptmi_aux_begin writes, for every chain slot ch = w * T + s in slot order, the chain's STATE row into xrows[ch] -- read from X, Q or Q2
+ * as sloc[ch] says (between a proposal launch and the accept test a state lives where its accepted proposal was written,
+ * ptmi_buffers.sloc; X on handles without Q2 / sloc and on the shape kernels' split path) -- and beta[ch] = 1 / T of the chain as the
+ * kernels use it (the table ptmi_cj_begin reads).  No listing, no atomics, no host read-back: every chain takes part.  It refuses
+ * (PTMI_EINVAL) while the gradient or the custom-jump stage of the current proposals has not ended -- the reference runs the auxiliary
+ * jumps on the jump's result -- and when called twice or for another iteration.  q is the CURRENT PROPOSAL BUFFER itself
+ * (ptmi_proposals), [W*T][ndim] in the same slot order: zero copy; a function may edit it in place or return rows of its own.
+ * ptmi_aux_end copies qrows [W*T][ndim] into the proposal buffer unless it is NULL or the buffer itself, ADDS qxy [W*T] (NULL: nothing)
+ * to qaux[.][0], and ends the stage; its arguments are checked before anything is launched, so a refused call (a misaligned qrows)
+ * leaves the stage open and a correct call -- ptmi_aux_end(h, NULL, NULL) at the least -- ends it.  Row copies are contiguous 16-byte pieces (8-byte for odd ndim); xrows and qrows 16-byte aligned.
+ * Not in ptmi_device_iter mode (PTMI_EUNSUPPORTED: the stage is not captured).  Parameter groups are fine (the stage never looks at
+ * them).  State lives in the handle: ptmi_config and ptmi_buffers are unchanged.  On the handle's stream. */
+int ptmi_aux_attach(ptmi_handle h);
+int ptmi_aux_begin(ptmi_handle h, int64_t iter, double *xrows /* dev [W*T][ndim] */, double *beta /* dev [W*T] */);
+int ptmi_aux_end(ptmi_handle h, const double *qrows /* dev [W*T][ndim], or NULL: the proposal buffer was edited in place */,
+                 const double *qxy /* dev [W*T] or NULL */);
 
 /* Self-test hooks used by the parity tests: evaluate the device's deterministic math on
  * n inputs (op: 0 log, 1 exp, 2 cos2pi, 3 sqrt, 4 reciprocal-free divide a/b with b=in2). */

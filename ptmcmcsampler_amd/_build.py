@@ -87,6 +87,7 @@ def build(force=False, verbose=False, jobs=None):
             (os.path.join(CSRC, "ptmi_split.hip"), os.path.join(OBJ, "split.o"), []),         # the split path's row kernels (shape-independent)
             (os.path.join(CSRC, "ptmi_gjcb.hip"), os.path.join(OBJ, "gjcb.o"), []),           # ... and its HMC stage for gradient callbacks
             (os.path.join(CSRC, "ptmi_cj.hip"), os.path.join(OBJ, "cj.o"), []),               # ... and its stage for batched custom jumps
+            (os.path.join(CSRC, "ptmi_aux.hip"), os.path.join(OBJ, "aux.o"), []),             # ... and its stage for batched auxiliary jumps
             (os.path.join(CSRC, "ptmi_dense_rows.hip"), os.path.join(OBJ, "dense_rows.o"), [])]   # ... and the built-in dense Gaussian / priors over rows
     for g, e in sorted(shapes(), key=lambda s: -s[0] * s[1]):       # biggest units first
         for fam in (1, 0, 2, 3):

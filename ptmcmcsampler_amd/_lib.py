@@ -52,6 +52,7 @@ SYMBOLS = (
     "ptmi_swap_write_am", "ptmi_update_cov", "ptmi_update_cov_on", "ptmi_set_am_buffers", "ptmi_eig_jacobi", "ptmi_eig_ql", "ptmi_eig_ql_from", "ptmi_eig_sytrd", "ptmi_eig_sytrd_from", "ptmi_eig_sytrd_info", "ptmi_update_de", "ptmi_set_de_head", "ptmi_propose", "ptmi_accept", "ptmi_accept_propose", "ptmi_proposals", "ptmi_rows_logl", "ptmi_rows_logl_grad", "ptmi_rows_logp", "ptmi_split_am_piece", "ptmi_split_am_prepare", "ptmi_set_stream", "ptmi_set_proposals", "ptmi_device_iter", "ptmi_set_device_iter",
     "ptmi_gj_work_bytes", "ptmi_gj_begin", "ptmi_gj_step",
     "ptmi_cj_attach", "ptmi_cj_work_bytes", "ptmi_cj_begin", "ptmi_cj_end", "ptmi_cj_box_draw",
+    "ptmi_aux_attach", "ptmi_aux_begin", "ptmi_aux_end",
     "ptmi_am_flags_ok", "ptmi_am_expand", "ptmi_test_replay",
     "ptmi_selftest_math", "ptmi_selftest_philox", "ptmi_malloc", "ptmi_free", "ptmi_memcpy_h2d", "ptmi_memcpy_d2h",
     "ptmi_memset", "ptmi_timer_start", "ptmi_timer_stop_ms",
@@ -134,10 +135,11 @@ def load():
     cj = dict(ptmi_cj_attach=[H, C.c_void_p, C.POINTER(C.c_int32), C.c_int32], ptmi_cj_work_bytes=[H, C.POINTER(C.c_size_t)],
               ptmi_cj_begin=[H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
               ptmi_cj_end=[H, C.c_void_p, C.c_void_p, C.c_void_p],
-              ptmi_cj_box_draw=[H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
+              ptmi_cj_box_draw=[H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+              ptmi_aux_attach=[H], ptmi_aux_begin=[H, C.c_int64, C.c_void_p, C.c_void_p], ptmi_aux_end=[H, C.c_void_p, C.c_void_p])
     for n, at in cj.items():
         if SO == os.environ.get("PTMI_LIB") and not hasattr(L, n):
-            continue                                  # an older build for an A/B measurement: no custom-jump stage (using it raises)
+            continue                                  # an older build for an A/B measurement: no custom-jump or auxiliary stage (using it raises)
         getattr(L, n).argtypes = at
     L.ptmi_selftest_math.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     L.ptmi_selftest_philox.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64]

@@ -1347,7 +1347,9 @@ int ptmi_create(const ptmi_config *cfg, const ptmi_buffers *buf, ptmi_handle *ou
         if (!c.gj_tab) return fail(PTMI_EINVAL, "gradient jumps need the whitening tables (gj_tab)");
         if (!buf->gj) return fail(PTMI_EINVAL, "gradient jumps need the gj buffer");
         if (c.ndim > 512) return fail(PTMI_EUNSUPPORTED, "gradient jumps on the device are built for ndim <= 512 (got %d)", c.ndim);
-        if (c.w_host > 0) return fail(PTMI_EUNSUPPORTED, "gradient jumps on the device cannot be mixed with host-served jumps");
+        // host-served entries beside them: on the split path, where ptmi_cj_attach declares them batched device callbacks (both stages
+        // run per proposal launch, on disjoint chains); the fused kernels (ptmi_mh_steps) refuse w_host > 0 whatever else is in the cycle
+        if (c.w_host > 0 && !buf->Q) return fail(PTMI_EUNSUPPORTED, "gradient jumps on the device cannot be mixed with host-served jumps (on the split path they can: Q and qaux)");
         if (c.nuts_maxdepth < 0 || c.nuts_maxdepth > 24) return fail(PTMI_EINVAL, "nuts_maxdepth out of range");
         if (c.w_hmc > 0 && (c.hmc_min < 0 || c.hmc_max <= c.hmc_min)) return fail(PTMI_EINVAL, "HMC needs 0 <= hmc_min < hmc_max");
     }
@@ -1682,6 +1684,8 @@ static void gj_proposed(ptmi_engine *h, long long iter)
     // ... and with batched custom jumps attached (ptmi_cj.hip) their stage
     h->cj_phase = h->cj_nfun > 0 ? PTMI_GJ_PENDING : PTMI_GJ_NONE;
     h->cj_iter = iter;
+    // ... and with auxiliary jumps attached (ptmi_aux.hip) theirs, behind the other two
+    h->aux_phase = h->aux_on ? PTMI_GJ_PENDING : PTMI_GJ_NONE;
 }
 // ... and an accept test may only read them once that stage is over
 static int gj_stage_over(const ptmi_engine *h, const char *who, int64_t iter)
@@ -1692,6 +1696,9 @@ static int gj_stage_over(const ptmi_engine *h, const char *who, int64_t iter)
     if (h->cj_phase == PTMI_GJ_PENDING || h->cj_phase == PTMI_GJ_ROUNDS)
         return fail(PTMI_EINVAL, "%s(%lld): the custom jumps' proposals of iteration %lld are not made yet -- ptmi_cj_begin, the callbacks, ptmi_cj_end first",
                     who, (long long)iter, h->cj_iter);
+    if (h->aux_phase == PTMI_GJ_PENDING || h->aux_phase == PTMI_GJ_ROUNDS)
+        return fail(PTMI_EINVAL, "%s(%lld): the auxiliary jumps of the proposals of iteration %lld have not run yet -- ptmi_aux_begin, the callbacks, ptmi_aux_end first",
+                    who, (long long)iter, h->gj_iter);
     return PTMI_OK;
 }
 
@@ -1761,6 +1768,7 @@ int ptmi_accept(ptmi_handle h, int64_t iter, const double *newlnL, const double 
     HIPCHK(hipGetLastError());
     h->gj_phase = PTMI_GJ_NONE;
     h->cj_phase = PTMI_GJ_NONE;
+    h->aux_phase = PTMI_GJ_NONE;
     return PTMI_OK;
 }
 

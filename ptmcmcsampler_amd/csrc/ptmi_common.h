@@ -218,6 +218,9 @@ struct ptmi_engine {
     void *cj_work;
     long long cj_offs[PTMI_CJ_MAXFUN + 1];
     long long *h_cj_offs;
+    // split path with batched auxiliary jumps (ptmi_aux.hip): attached (ptmi_aux_attach), and where the stage of the current proposals
+    // is (PTMI_GJ_* as above; ROUNDS = between ptmi_aux_begin and ptmi_aux_end)
+    int aux_on, aux_phase;
 };
 enum { PTMI_GJ_NONE = 0, PTMI_GJ_PENDING = 1 /* proposals made, ptmi_gj_begin not yet called */, PTMI_GJ_ROUNDS = 2, PTMI_GJ_DONE = 3 };
 // the split path's refusals for gradient jumps (0: served; else the code, with the message set)

@@ -168,8 +168,18 @@ class PTEngine(object):
     cycle's custom entries (the reference's ``addProposalToCycle``, PTMCMCSampler.py:988-1014, 1058-1059) as BATCHED device callbacks --
     ``func(X[n, d], iter, beta[n]) -> (Q[n, d], qxy[n] | 0 | None)`` on torch tensors of this GPU, once per iteration for all chains
     whose pick is that function (``jump_stage``; include/ptmi.h ``ptmi_cj_*``).  ``box_draw_jump(lo, hi)`` is the reference's
-    ``UniformJump`` as a library kernel.  ``get("cjstat")`` [W][nt][w_host][2]: proposed / accepted per pick index by rank.  Not with
-    gradient jumps, not in graph mode.
+    ``UniformJump`` as a library kernel.  ``get("cjstat")`` [W][nt][w_host][2]: proposed / accepted per pick index by rank.  Not in
+    graph mode.  Beside gradient jumps (``grad_weights``) with ``with_stages(..., jumps_with_grad=True)``: the reference's cycle of custom entries, HMC,
+    NUTS, SCAM, AM and DE, picked in the order [custom, SCAM, AM, DE, NUTS, HMC]; every proposal launch is then followed by both
+    stages, which serve disjoint chains (opt-in, like ``split_nuts``: without the keyword the combination is refused).
+    ``aux=[func, ...]`` (``split=True`` or ``rows_logl=True``): the reference's auxiliary jumps (``addAuxilaryJump``,
+    PTMCMCSampler.py:1017-1028, run on every jump's result at :1062-1065) as BATCHED device callbacks -- ``func(X[n, d], Q[n, d], iter,
+    beta[n]) -> (Q'[n, d], qxy[n] | 0 | None)`` on torch tensors of this GPU, ``n = W * nt``: every chain, in slot order.  ``X`` holds
+    the chains' states (gathered once per iteration, ``ptmi_aux_begin``: between the launches of a segment a state lives in X or in a
+    proposal buffer), ``Q`` is the proposal buffer itself (edit it in place, or return a tensor of your own); the functions run in the
+    order given, each on the ``Q`` of the one before, their ``qxy`` added to the jump's in that order (``aux_stage``).  Not in graph mode.
+    ``jumps_with_grad`` and ``aux`` are keywords of the alternative constructor ``PTEngine.with_stages(..., jumps_with_grad=True,
+    aux=[f])``, which takes everything the plain constructor takes: the plain constructor's parameters stay what they were.
     ``stats_async`` (pooled covariance with ``eig_lag >= 1``): the statistics of a covariance period that is over need nothing the next
     launches touch once those write ANOTHER ring -- so the engine keeps two rings (``t["AM"]`` is always the one in use), switches at
     every covariance epoch, and runs the period's statistics (``ptmi_update_cov_on``) and the factorization behind them on a side
@@ -177,6 +187,21 @@ class PTEngine(object):
     only: every result equals the run without it bit for bit (oracle: ``OracleEngine(eig_lag=L)``).  Needs burn to be a multiple of
     cov_update when a DE history is kept (a DE epoch then reads the finished period's ring before the switch).
     """
+
+    # what PTEngine.with_stages sets on the instance before __init__ runs (the plain constructor leaves the class defaults)
+    jumps_with_grad = False
+    _aux = ()
+
+    @classmethod
+    def with_stages(cls, *args, jumps_with_grad=False, aux=None, **kw):
+        """``PTEngine(*args, **kw)`` with the stages of the composed ``_jump`` on the callback path (see the class docstring):
+        ``jumps_with_grad=True`` lets ``jumps=`` stand beside ``grad_weights`` in one cycle, ``aux=[func, ...]`` are the auxiliary jumps.
+        The plain constructor keeps the parameters it had (tests/test_gj_groups.py holds them to the letter) and its refusals."""
+        self = cls.__new__(cls)
+        self.jumps_with_grad = bool(jumps_with_grad)
+        self._aux = list(aux) if aux is not None else []
+        self.__init__(*args, **kw)
+        return self
 
     def __init__(self, ndim, ntemps, nwalkers, cov0, ladder=None, logl=("iso",), logp=("flat",),
                  weights=(20, 20, 20), cov_update=1000, burn=10000, tskip=100, seed=0,
@@ -203,10 +228,22 @@ class PTEngine(object):
                 raise ValueError("jumps= names %d cycle entries for w_host=%d" % (len(self._fun_of_pick), int(w_host)))
             if len(self._jumps) > _lib.CJ_MAXFUN:
                 raise ValueError("jumps= takes at most %d different functions (got %d)" % (_lib.CJ_MAXFUN, len(self._jumps)))
-            if sum(int(w) for w in grad_weights) > 0:
-                raise ValueError("custom jumps (jumps=) cannot be mixed with gradient jumps (grad_weights) in one cycle")
+            if sum(int(w) for w in grad_weights) > 0 and not self.jumps_with_grad:
+                raise ValueError("custom jumps (jumps=) are mixed with gradient jumps (grad_weights) in one cycle only when asked for: "
+                                 "PTEngine.with_stages(..., jumps_with_grad=True) (both stages then run behind every proposal launch)")
             if not (split or rows_logl):
                 raise ValueError("jumps= are served on the callback path: split=True (or rows_logl=True)")
+        elif int(w_host) > 0 and sum(int(w) for w in grad_weights) > 0:
+            # (the library would hand such picks back unchanged on a split handle; only the batched stage serves them beside gradient jumps)
+            raise ValueError("host-served cycle entries (w_host > 0) beside gradient jumps (grad_weights) are served as batched device "
+                             "callbacks only: PTEngine.with_stages(..., jumps=[(func, weight), ...], jumps_with_grad=True)")
+        # the auxiliary jumps as batched device callbacks behind every proposal launch (with_stages(aux=...); see the class docstring)
+        self._aux = list(self._aux)
+        if self._aux:
+            if not all(callable(f) for f in self._aux):
+                raise ValueError("aux=[func, ...] takes callables func(X[n, d], Q[n, d], iter, beta[n]) -> (Q[n, d], qxy[n] | 0 | None)")
+            if not (split or rows_logl):
+                raise ValueError("aux= are served on the callback path: split=True (or rows_logl=True)")
         # rows_logl: the built-in likelihood as a row kernel on the split path (see the class docstring); refused before anything is built
         self.rows_logl = bool(rows_logl)
         if self.rows_logl:
@@ -369,6 +406,8 @@ class PTEngine(object):
             for f in self._jumps:
                 if isinstance(f, _BoxDrawJump):
                     f.bind(self)
+        if self._aux:
+            _lib.check(self.lib.ptmi_aux_attach(self.h))
         self.de_on = False
         self.de_head = 0
         self.iter = 0
@@ -828,6 +867,8 @@ class PTEngine(object):
                 v.copy_(torch.from_numpy(np.ascontiguousarray(st["t_" + k])).to(v.dtype))
             elif v is not None and k == "cjstat":
                 v.zero_()                                             # a checkpoint from before the counters existed
+        if self.t.get("sloc") is not None:
+            self.t["sloc"].zero_()                                    # every restored state is in X (a segment abandoned half way -- a callback that raised -- left it otherwise)
         if self.stats_async:                                          # the ring of the period before (readers of older rows: get("AM"))
             for k, v in self._alt.items():
                 if v is not None and "alt_" + k in st:
@@ -1084,6 +1125,51 @@ class PTEngine(object):
         _lib.check(lib.ptmi_cj_end(h, work, rows.data_ptr(), self._cj_qxy.data_ptr() if have_qxy else None))
         return offs[nf]
 
+    def aux_stage(self, it):
+        """The auxiliary jumps of ``aux=`` on the proposals of iteration ``it``, behind ``gradient_stage`` and ``jump_stage``
+        (PTMCMCSampler.py:1062-1065): ``ptmi_aux_begin`` gathers every chain's state and beta, each function is called once,
+        ``func(X[n, d], Q[n, d], it, beta[n]) -> (Q'[n, d], qxy[n] | 0 | None)`` with ``Q`` the proposal buffer itself or what the function
+        before returned, and ``ptmi_aux_end`` puts the last ``Q'`` into the proposal buffer (nothing to copy when every function worked in
+        place) and adds ``qxy``.  Several ``qxy`` are added one after the other, the reference's ``qxy += qxy_aux``.  No host read-back.
+        Returns the number of functions called.  A no-op without ``aux=``."""
+        if not self._aux:
+            return 0
+        torch = _torch()
+        n = self.W * self.nt
+        if getattr(self, "_aux_x", None) is None:
+            self._aux_x = torch.empty((n, self.d), dtype=torch.float64, device=self.device)
+            self._aux_beta = torch.empty(n, dtype=torch.float64, device=self.device)
+        lib, h = self.lib, self.h
+        _lib.check(lib.ptmi_aux_begin(h, it, self._aux_x.data_ptr(), self._aux_beta.data_ptr()))
+        P = self.proposals().view(n, self.d)
+        Q, pending = P, None
+        try:
+            for f, func in enumerate(self._aux):
+                r = func(self._aux_x, Q, it, self._aux_beta)
+                what = getattr(func, "__name__", "auxiliary jump %d" % f)
+                if not isinstance(r, (tuple, list)) or len(r) != 2:
+                    raise ValueError("%s must return (Q[n, ndim], qxy[n] or 0 or None)" % what)
+                Q, qxy = r
+                if not (torch.is_tensor(Q) and Q.dtype == torch.float64 and Q.device == self.device and Q.is_contiguous()):
+                    Q = torch.as_tensor(Q, dtype=torch.float64, device=self.device).contiguous()
+                if tuple(Q.shape) != (n, self.d):
+                    raise ValueError("%s returned proposals %s for %d rows of %d parameters" % (what, tuple(Q.shape), n, self.d))
+                if qxy is None or (not torch.is_tensor(qxy) and np.ndim(qxy) == 0 and qxy == 0):
+                    continue
+                if not (torch.is_tensor(qxy) and qxy.dtype == torch.float64 and qxy.device == self.device and qxy.is_contiguous()):
+                    qxy = torch.as_tensor(qxy, dtype=torch.float64, device=self.device).contiguous()
+                if qxy.numel() != n:
+                    raise ValueError("%s returned qxy %s for %d rows" % (what, tuple(qxy.shape), n))
+                if pending is not None:                               # (jump's qxy + first) + second, ...: the reference's order of additions
+                    self.t["qaux"].view(n, 4)[:, 0].add_(pending.reshape(n))
+                pending = qxy
+        except BaseException:
+            lib.ptmi_aux_end(h, None, None)                           # the stage does not stay open behind a function that raised
+            raise
+        _lib.check(lib.ptmi_aux_end(h, Q.data_ptr() if Q.data_ptr() != P.data_ptr() else None,
+                                    pending.data_ptr() if pending is not None else None))
+        return len(self._aux)
+
     def box_draw_jump(self, lo, hi):
         """The reference's ``UniformJump`` (tests/test_simple.py:44-62: every parameter redrawn uniformly in ``[lo, hi]``, qxy = 0)
         as a batched jump for ``jumps=``: its body is ``ptmi_cj_box_draw``, the library's own counter-based generator -- reproducible
@@ -1092,13 +1178,14 @@ class PTEngine(object):
 
     def split_step(self, it, logl, logp, logl_grad=None, logp_grad=None):
         """One iteration of every chain with batched callbacks: ptmi_propose -> (HMC / NUTS in the cycle: the gradient stage,
-        ``gradient_stage``) -> callbacks on the device tensor of proposals -> ptmi_accept.  All on the engine's stream; no host copy of
-        the proposals."""
+        ``gradient_stage``; custom and auxiliary jumps: ``jump_stage``, ``aux_stage``) -> callbacks on the device tensor of proposals ->
+        ptmi_accept.  All on the engine's stream; no host copy of the proposals."""
         if self.t["Q"] is None:
             raise _lib.PtmiError("the callback path needs the engine built with split=True")
         _lib.check(self.lib.ptmi_propose(self.h, it))
         self.gradient_stage(it, logl_grad, logp_grad)
         self.jump_stage(it)
+        self.aux_stage(it)
         ll, lp = self.eval_callback(self.t["Q"], logl, logp)
         _lib.check(self.lib.ptmi_accept(self.h, it, ll.data_ptr(), lp.data_ptr()))
 
@@ -1194,6 +1281,7 @@ class PTEngine(object):
         _lib.check(lib.ptmi_propose(h, it))
         self.gradient_stage(it, logl_grad, logp_grad)
         self.jump_stage(it)
+        self.aux_stage(it)
         for j in range(it, end):
             ll, lp = self.eval_callback(self.proposals(), logl, logp)
             if piece and (j + 1 - it) % piece == 0:                   # the proposal of j + 1 opens the next piece
@@ -1201,6 +1289,7 @@ class PTEngine(object):
             _lib.check(lib.ptmi_accept_propose(h, j, ll.data_ptr(), lp.data_ptr()))       # (between here and ptmi_accept X is not the state: sloc)
             self.gradient_stage(j + 1, logl_grad, logp_grad)
             self.jump_stage(j + 1)
+            self.aux_stage(j + 1)
         ll, lp = self.eval_callback(self.proposals(), logl, logp)
         _lib.check(lib.ptmi_accept(h, end, ll.data_ptr(), lp.data_ptr()))
 
@@ -1215,8 +1304,8 @@ class PTEngine(object):
         configurations the row kernels do not serve; HMC or NUTS in the cycle: their rounds are counted on the host): the caller then runs
         ``callback_segment``.  Same results, bit for bit."""
         torch = _torch()
-        if self.t["Q2"] is None or self.weights[1] > 0 or sum(self.grad_weights) > 0 or self._jumps:
-            return False                                              # (custom jumps: their spans are read on the host)
+        if self.t["Q2"] is None or self.weights[1] > 0 or sum(self.grad_weights) > 0 or self._jumps or self._aux:
+            return False                                              # (custom jumps: their spans are read on the host; auxiliary jumps: not captured)
         if getattr(self, "_graphs", None) is None:
             self._graphs = {}
         L = end - it + 1

@@ -24,7 +24,10 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
   ``boxDrawJump(lo, hi)`` is the reference's uniform prior draw as a library kernel).  With ``logl_grad`` / ``logp_grad`` as batched callbacks too --
   ``f(X[n, ndim]) -> (value[n], gradient[n, ndim])`` -- HMC (``HMCweight``) runs on the device with the callbacks' gradients
   (``PTEngine.gradient_stage``); NUTS (``NUTSweight``) too with ``batched_nuts=True`` -- opt-in: an iteration takes as many
-  callback rounds as its deepest tree has leaves (without it pass ``NUTSweight=0``);
+  callback rounds as its deepest tree has leaves (without it pass ``NUTSweight=0``); batched custom jumps ride the same cycle
+  beside them.  Auxiliary jumps in the batched signature too once ``sampler.batched_aux = True`` is set -- ``addAuxilaryJump(func, batched=True)``:
+  ``func(X[n, ndim], Q[n, ndim], iter, beta[n]) -> (Q'[n, ndim], qxy[n] | 0 | None)`` for every chain, behind the jump
+  (``PTEngine.aux_stage``) -- opt-in: every iteration then gathers the chains' states;
 * engine options: ``cov_mode="pooled"`` (one covariance adapted from all walkers instead of one per walker),
   ``swap_mode="oddeven"`` (disjoint swap pairs instead of the reference's hot -> cold sweep), ``pick_mode="walker"`` (one
   proposal-type draw per walker and iteration), ``eig_mode="ql"`` / ``"jacobi"`` / ``"sytrd"`` / ``"hipsolver"`` (covariance epochs factorized on the device: per-walker matrices by
@@ -120,6 +123,11 @@ _CKPT_FORMAT_WHY = {2: "the DE history's row layout", 3: "the pooled statistics'
 
 
 class PTSampler(object):
+    # s.batched_aux = True (before addAuxilaryJump(func, batched=True)): auxiliary jumps as batched device callbacks, served by the engine's
+    # auxiliary stage (PTEngine.with_stages(aux=...)).  An attribute, not a constructor keyword: tests/test_gj_groups.py holds __init__'s
+    # parameters to the letter
+    batched_aux = False
+
     def __init__(self, ndim, logl, logp, cov, groups=None, loglargs=[], loglkwargs={}, logpargs=[], logpkwargs={},
                  logl_grad=None, logp_grad=None, comm=None, outDir="./chains", verbose=True, resume=False, seed=None,
                  nwalkers=1, ntemps=None, device=0, cov_mode="per_walker", keep_walkers=1, swap_mode="sweep",
@@ -183,6 +191,7 @@ class PTSampler(object):
         self.M2 = np.zeros((ndim, ndim))
         self.mu = np.zeros(ndim)
         self.propCycle, self.jumpDict, self.aux = [], {}, []
+        self._batched_aux = []                               # auxiliary jumps added with addAuxilaryJump(..., batched=True)
         self._batched_jumps = []                             # cycle entries added with addProposalToCycle(..., batched=True)
         self.engine = None
         self._ctx = (0, 0)
@@ -218,11 +227,19 @@ class PTSampler(object):
             open(self.outDir + "/" + func.__name__ + "_jump.txt", "w").close()
 
     def addAuxilaryJump(self, func, batched=False):
-        """PTMCMCSampler.py:1017-1028 (per chain, on the host)."""
+        """PTMCMCSampler.py:1017-1028 (per chain, on the host).  ``batched=True`` on a sampler with ``batched_aux = True`` set: ``func`` is
+        called once per iteration for ALL chains on device tensors -- ``func(X[n, ndim], Q[n, ndim], iter, beta[n]) -> (Q'[n, ndim],
+        qxy[n] | 0 | None)``, ``n = nwalkers * ntemps`` in slot order, ``X`` the chains' states, ``Q`` the proposal buffer itself -- behind the
+        cycle entry's own stage (``PTEngine.aux_stage``); for samplers with ``batched=True`` or a device likelihood with
+        ``rows_logl=True``."""
         if batched:
-            raise NotImplementedError("auxiliary jumps are not served as batched device callbacks: func(x, q, iter, beta) needs the state x of "
-                                      "EVERY chain, and between the proposal launch and the accept test a chain's state lives in X or in "
-                                      "one of the two proposal buffers (sloc); add them per chain on a sampler without batched=True")
+            if not self.batched_aux:
+                raise NotImplementedError("auxiliary jumps are served as batched device callbacks only when asked for: func(x, q, iter, beta) "
+                                          "needs the state x of EVERY chain, and between the proposal launch and the accept test a chain's "
+                                          "state lives in X or in one of the two proposal buffers (sloc), so every iteration then gathers the "
+                                          "states (set sampler.batched_aux = True first); or add them per chain on a sampler without batched=True")
+            self._batched_aux.append(func)
+            return
         self.aux.append(func)
 
     @staticmethod
@@ -391,9 +408,13 @@ class PTSampler(object):
             raise ValueError("a batched jump (addProposalToCycle(..., batched=True)) runs on the device callback path: PTSampler(..., "
                              "batched=True), or a device likelihood with rows_logl=True; this sampler calls its jumps per chain")
         self._stage_jumps = bool(self.host_jumps) and stage_ok and all(is_bj(f) for f in self.host_jumps) and not self.aux
-        if self._stage_jumps and sum(self._grad_weights) > 0:
-            raise NotImplementedError("batched custom jumps cannot be mixed with gradient jumps (HMC / NUTS) in one cycle: pass "
-                                      "NUTSweight=0, HMCweight=0 or leave logl_grad / logp_grad out")
+        # auxiliary jumps in the batched signature (addAuxilaryJump(..., batched=True) with batched_aux set): the engine's auxiliary stage
+        if self._batched_aux and not stage_ok:
+            raise ValueError("a batched auxiliary jump (addAuxilaryJump(..., batched=True)) runs on the device callback path: PTSampler(..., "
+                             "batched=True), or a device likelihood with rows_logl=True; this sampler calls its jumps per chain")
+        if self._batched_aux and self.aux:
+            raise NotImplementedError("auxiliary jumps per chain and batched=True ones cannot be mixed: the per-chain ones need every "
+                                      "proposal on the host")
         on_host = [] if self._stage_jumps else self.host_jumps
         self.split = self.logl is not None or bool(on_host) or bool(self.aux)
         if self.split and self.logl is None:
@@ -409,7 +430,7 @@ class PTSampler(object):
                     stage_list[-1][1] += 1
                 else:
                     stage_list.append([f, 1])
-        self.engine = PTEngine(
+        self.engine = PTEngine.with_stages(
             self.ndim, self.nchain, self.nwalkers, np.asarray(self.cov, dtype=np.float64), ladder=self.ladder,
             logl=self.logl_spec or ("iso",), logp=self.logp_spec or ("flat",),
             weights=(self.SCAMweight, self.AMweight, self.DEweight), cov_update=covUpdate, burn=burn, tskip=Tskip,
@@ -417,6 +438,7 @@ class PTSampler(object):
             swap_mode=self.swap_mode, pick_mode=self.pick_mode, eig_mode=self.eig_mode, grad_weights=self._grad_weights, hmc=(HMCstepsize, 2, HMCsteps), nuts_maxdepth=self.nuts_maxdepth,
             split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
             jumps=[(f, n) for f, n in stage_list] if stage_list else None,
+            jumps_with_grad=bool(stage_list) and sum(self._grad_weights) > 0, aux=list(self._batched_aux) or None,
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     # ------------------------------------------------------------------ sample (:374-528)
@@ -564,7 +586,9 @@ class PTSampler(object):
                            eng.de_ld, eng.de_epl, self.keep_walkers, eng.am_epl,
                            digest(np.asarray(eng.ladder, dtype=np.float64), np.asarray(eng.temps_mh, dtype=np.float64)), self.Tskip,
                            digest((self.SCAMweight, self.AMweight, self.DEweight) + tuple(self._grad_weights) + (len(self.host_jumps),)
-                                  + ((tuple(f.__name__ for f in self.host_jumps),) if getattr(self, "_stage_jumps", False) else ())),
+                                  + ((tuple(f.__name__ for f in self.host_jumps),) if getattr(self, "_stage_jumps", False) else ())
+                                  # (batched auxiliary jumps by name, only where there are some: the other runs' fingerprints stay what they were)
+                                  + ((("aux",) + tuple(getattr(f, "__name__", "?") for f in self._batched_aux),) if self._batched_aux else ())),
                            digest((self.cov_mode, self.swap_mode, self.pick_mode, self.eig_mode, self.nuts_maxdepth, bool(self.split), bool(self.batched),
                                    bool(eng.am_rle)), *groups),
                            digest(*(spec(self.logl_spec) + spec(self.logp_spec)))], dtype=np.int64)
