@@ -52,7 +52,7 @@ enum { PTMI_LOGL_ISO = 0,      /* -1/2 sum x^2 */
                                 * N(0, I) on the box (a, b) in the coordinates p of all real numbers, x = (b - a) e^p / (1 + e^p) + a, the
                                 * log-Jacobian included: sum_i -x_i^2/2 - log(2 pi)/2 + log(b_i - a_i) + p_i - 2 log(1 + e^p_i);
                                 * par = a[d], w[d] = b - a, lw[d] = log w (the host's logarithm: a parameter, not part of the arithmetic).
-                                * Served by the kernel shapes of the gradient jumps (ndim <= 512, ptmi_lanes_for_grad) with or without them. */
+                                * Served by the fused kernels' shapes of the gradient jumps (ndim <= 512: at most 8 slots per lane) with or without them. */
 enum { PTMI_LOGP_FLAT = 0,     /* 0 everywhere */
        PTMI_LOGP_BOX = 1 };    /* 0 inside [lo,hi], -inf outside ; par = lo[d], hi[d] */
 
@@ -95,8 +95,11 @@ typedef struct ptmi_config {
     int32_t ngroups;         /* parameter groups (PTMCMCSampler.py:129-145); 0 or 1 = one group of all parameters */
     int32_t swap_mode;       /* PTMI_SWAP_SWEEP (the reference's hot -> cold sweep, :666-686) or PTMI_SWAP_ODDEVEN */
     /* Gradient jumps on the built-in likelihoods (the reference adds them when logl_grad / logp_grad are given,
-     * :225-258; nutsjump.py): cycle += [NUTS]*w_nuts + [HMC]*w_hmc.  ndim <= 512; the engine then shares a chain among
-     * ptmi_lanes_for_grad(ndim) lanes (at most 8 register slots per lane), which fixes the summation orders.  With parameter
+     * :225-258; nutsjump.py): cycle += [NUTS]*w_nuts + [HMC]*w_hmc.  The engine shares a chain among ptmi_lanes_for_grad(ndim)
+     * lanes, which fixes the summation orders.  ndim <= 512 (at most 8 register slots per lane) for the fused kernels (ptmi_mh_steps),
+     * for NUTS and for the interval family; 512 < ndim <= 2048: w_hmc alone (w_nuts == 0) on a split handle (ptmi_buffers.Q), served by
+     * ptmi_gj_begin / ptmi_gj_step with the whitening products on the matrix cores -- the proposal kernels then run in the ordinary
+     * 64-lane shape and ptmi_mh_steps refuses the handle (PTMI_EUNSUPPORTED).  With parameter
      * groups (ngroups > 1; not the interval family) SCAM / AM / DE move one group's parameters with that group's tables, a NUTS or
      * HMC pick draws no group and moves every parameter with the whitening tables of the full initial covariance (gj_tab). */
     int32_t w_nuts, w_hmc;
@@ -433,7 +436,14 @@ int ptmi_rows_logp(ptmi_handle h, const double *rows /* dev [n][ndim] */, int64_
  * calls out of sequence.  The shape kernels' split path (PTMI_SPLIT_ROWS=0, or a handle ptmi_split_rows_ok does not take) and
  * ptmi_device_iter mode are refused (PTMI_EUNSUPPORTED); parameter groups are fine (the proposal launch draws the group of a SCAM /
  * AM / DE pick and hands a gradient pick back unchanged; the stage never looks at groups: a gradient jump moves every parameter with the
- * whitening tables of the full initial covariance).  On the handle's stream. */
+ * whitening tables of the full initial covariance).  On the handle's stream.
+ *
+ * 512 < ndim <= 2048 (csrc/ptmi_gjcb_wide.hip; HMC only): the same calls, sequencing, work area (the HMC-only formula above: the
+ * whitened gradient of a round lives in the chains' row slots, which are free between the listing and the backward product) and bits.
+ * ptmi_gj_begin lists the HMC picks first and runs the forward and backward products over the listed chains only; a round is the
+ * gradient product, the step (one wave per listed chain), the backward product and the listing.  A product is n rows times one d x d
+ * table on v_mfma_f64_16x16x4_f64, every element one k-ascending fma chain from +0.0 as below 512-d (diagonal tables: d
+ * multiplications). */
 int ptmi_gj_work_bytes(ptmi_handle h, size_t *bytes);
 int ptmi_gj_begin(ptmi_handle h, int64_t iter, void *work, double *rows /* dev [W*T][ndim] */, int64_t *n);
 int ptmi_gj_step(ptmi_handle h, void *work, const double *lnl /* dev [n] */, const double *dlnl /* dev [n][ndim] */,

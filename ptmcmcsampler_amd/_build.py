@@ -86,6 +86,7 @@ def build(force=False, verbose=False, jobs=None):
             (os.path.join(CSRC, "ptmi_swap.hip"), os.path.join(OBJ, "swap.o"), []),           # the PT swap and the block-edge exchange
             (os.path.join(CSRC, "ptmi_split.hip"), os.path.join(OBJ, "split.o"), []),         # the split path's row kernels (shape-independent)
             (os.path.join(CSRC, "ptmi_gjcb.hip"), os.path.join(OBJ, "gjcb.o"), []),           # ... and its HMC stage for gradient callbacks
+            (os.path.join(CSRC, "ptmi_gjcb_wide.hip"), os.path.join(OBJ, "gjcb_wide.o"), []),   # ... the same stage beyond 512-d: whitening on the matrix cores
             (os.path.join(CSRC, "ptmi_cj.hip"), os.path.join(OBJ, "cj.o"), []),               # ... and its stage for batched custom jumps
             (os.path.join(CSRC, "ptmi_aux.hip"), os.path.join(OBJ, "aux.o"), []),             # ... and its stage for batched auxiliary jumps
             (os.path.join(CSRC, "ptmi_dense_rows.hip"), os.path.join(OBJ, "dense_rows.o"), [])]   # ... and the built-in dense Gaussian / priors over rows

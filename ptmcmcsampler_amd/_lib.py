@@ -167,5 +167,5 @@ def device_count():
 def lanes_for(ndim, grad=False):
     """Lanes that share one chain (ptmi_lanes_for / ptmi_lanes_for_grad)."""
     if grad:
-        return 4 if ndim <= 32 else (16 if ndim <= 112 else (64 if ndim <= 512 else 0))
+        return 4 if ndim <= 32 else (16 if ndim <= 112 else (64 if ndim <= 2048 else 0))
     return 4 if ndim <= 104 else (16 if ndim <= 416 else 64)

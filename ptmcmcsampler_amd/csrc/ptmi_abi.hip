@@ -1078,6 +1078,7 @@ static bool pick_shape(int d, bool grad, Shape *s)
     static const Shape table[] = {
 #define PTMI_TABLE_ENTRY(G_, E_) {G_, E_},
         PTMI_SHAPE_LIST(PTMI_TABLE_ENTRY)};
+    if (d > PTMI_GJ_REG_MAX) grad = false;           // beyond the fused gradient kernels the proposal kernels run in the ordinary 64-lane shape
     const int G = grad ? ptmi_lanes_for_grad(d) : ptmi_lanes_for(d);
     for (const Shape &c : table)
         if (c.G == G && c.G * c.EPL >= d && (!grad || c.EPL <= 8) && (!ptmi_shape_exact(c.G, c.EPL) || c.G * c.EPL == d)) { *s = c; return true; }
@@ -1246,8 +1247,9 @@ extern "C" {
 const char *ptmi_last_error(void) { return g_err; }
 int ptmi_version(void) { return PTMI_VERSION; }
 int ptmi_lanes_for(int ndim) { return ndim <= 104 ? 4 : (ndim <= 416 ? 16 : 64); }
-// gradient jumps keep seven chain vectors in registers: at most 8 slots per lane (shapes (4,8), (16,7), (64,8))
-int ptmi_lanes_for_grad(int ndim) { return ndim <= 32 ? 4 : (ndim <= 112 ? 16 : (ndim <= 512 ? 64 : 0)); }
+// gradient jumps keep seven chain vectors in registers: at most 8 slots per lane (shapes (4,8), (16,7), (64,8)); beyond 512-d the
+// callback path's HMC stage (ptmi_gjcb_wide.hip) keeps them in its work area: 64 lanes up to 2048
+int ptmi_lanes_for_grad(int ndim) { return ndim <= 32 ? 4 : (ndim <= 112 ? 16 : (ndim <= 2048 ? 64 : 0)); }
 
 // PT:699-720: geometric ladder T_i = Tmin * tstep^i; the spacing is 1 + sqrt(2/ndim) unless Tmax (> 0) or tstep (> 0)
 // fixes it.  Host arithmetic in the reference's operation order (libm pow / exp / log, as NumPy's scalar path).
@@ -1346,7 +1348,11 @@ int ptmi_create(const ptmi_config *cfg, const ptmi_buffers *buf, ptmi_handle *ou
     if (gj) {
         if (!c.gj_tab) return fail(PTMI_EINVAL, "gradient jumps need the whitening tables (gj_tab)");
         if (!buf->gj) return fail(PTMI_EINVAL, "gradient jumps need the gj buffer");
-        if (c.ndim > 512) return fail(PTMI_EUNSUPPORTED, "gradient jumps on the device are built for ndim <= 512 (got %d)", c.ndim);
+        if (c.ndim > 2048) return fail(PTMI_EUNSUPPORTED, "gradient jumps on the device stop at ndim 2048 (got %d)", c.ndim);
+        // 512 < ndim <= 2048: HMC through the batched gradient stage of a split handle (ptmi_gj_begin / ptmi_gj_step, ptmi_gjcb_wide.hip)
+        if (c.ndim > PTMI_GJ_REG_MAX && (c.w_nuts > 0 || !buf->Q || c.logl_kind == PTMI_LOGL_INTERVAL))
+            return fail(PTMI_EUNSUPPORTED, "gradient jumps on the device are built for ndim <= 512 (got %d); up to 2048 a split handle "
+                                           "(ptmi_buffers.Q) runs HMC alone (w_nuts == 0) through ptmi_gj_begin / ptmi_gj_step", c.ndim);
         // host-served entries beside them: on the split path, where ptmi_cj_attach declares them batched device callbacks (both stages
         // run per proposal launch, on disjoint chains); the fused kernels (ptmi_mh_steps) refuse w_host > 0 whatever else is in the cycle
         if (c.w_host > 0 && !buf->Q) return fail(PTMI_EUNSUPPORTED, "gradient jumps on the device cannot be mixed with host-served jumps (on the split path they can: Q and qaux)");
@@ -1417,7 +1423,12 @@ int ptmi_create(const ptmi_config *cfg, const ptmi_buffers *buf, ptmi_handle *ou
             return e2 != hipSuccess ? fail(PTMI_EHIP, "group tables: %s", hipGetErrorString(e2)) : rc;
         }
     }
-    if (gj) {
+    if (gj && c.ndim > PTMI_GJ_REG_MAX) {                                            // the callback path alone: the tables, no scratch of the fused kernels
+        if ((rc = upload(&h->d_gj_tab, c.gj_tab, 3LL * c.ndim * c.ndim))) {
+            ptmi_destroy(h);
+            return rc;
+        }
+    } else if (gj) {
         const size_t nch = (size_t)c.nwalkers * c.ntemps, lanes = (size_t)s.G * s.EPL;
         const size_t nvec = (size_t)GJV_TOP + (size_t)GJL_VECS * (c.nuts_maxdepth + 1);
         hipError_t e3 = hipMalloc((void **)&h->d_gj_scr, sizeof(double) * nvec * lanes * nch);
@@ -1436,6 +1447,8 @@ int ptmi_create(const ptmi_config *cfg, const ptmi_buffers *buf, ptmi_handle *ou
             ptmi_destroy(h);
             return e3 != hipSuccess ? fail(PTMI_EHIP, "gradient-jump scratch: %s", hipGetErrorString(e3)) : rc;
         }
+    }
+    if (gj) {
         // diagonal whitening (cov0 diagonal: the curved-likelihood runs start from the identity): a product is d multiplications
         // (the oracle's tab_vec defines the same rule)
         h->gj_diag = 1;
@@ -1605,6 +1618,9 @@ int ptmi_mh_steps(ptmi_handle h, int64_t iter0, int32_t nsteps)
 {
     if (!h) return fail(PTMI_EINVAL, "NULL handle");
     if (nsteps < 0 || iter0 < 0) return fail(PTMI_EINVAL, "iter0/nsteps negative");
+    if (h->cfg.w_nuts + h->cfg.w_hmc > 0 && h->cfg.ndim > PTMI_GJ_REG_MAX)
+        return fail(PTMI_EUNSUPPORTED, "ptmi_mh_steps: the fused gradient kernels are built for ndim <= 512 (got %d); beyond, HMC runs on the "
+                                       "split path (ptmi_propose / ptmi_gj_begin / ptmi_gj_step)", h->cfg.ndim);
     if (nsteps == 0) return PTMI_OK;
     KArgs a = make_args(h);
     a.iter0 = iter0; a.nsteps = nsteps;

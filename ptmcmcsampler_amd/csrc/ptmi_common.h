@@ -142,6 +142,10 @@ enum { GJV_TM = 0, GJV_RM = 1, GJV_GM = 2, GJV_TP = 3, GJV_RP = 4, GJV_GP = 5, G
 enum { GJL_FAR_T = 0, GJL_FAR_R = 1, GJL_CAND_T = 2, GJL_CAND_G = 3, GJL_VECS = 4 };
 enum { GJS_LOGP = 0, GJS_N = 1, GJS_ALPHA = 2, GJS_NALPHA = 3, GJS_SCALARS = 4 };
 
+// ndim up to which gradient jumps keep a chain's vectors in 8 register slots of G lanes: the fused kernels (ptmi_gj.inc.h), NUTS and the
+// callback path's kernels of ptmi_gjcb.hip; beyond it, up to 2048, HMC alone on the callback path (ptmi_gjcb_wide.hip)
+constexpr int PTMI_GJ_REG_MAX = 512;
+
 template <int G>
 __device__ __forceinline__ double group_bcast_lane(double v, int src)
 {

@@ -20,86 +20,20 @@
 // A round is three launches: the step (gj_step_kernel: every listed chain), then the listing (gj_count_kernel, gj_fill_kernel: the
 // chains still moving in ascending chain slot -- block counts, then each block's offset from the counts before it and a ballot scan
 // inside: no atomics, the order is the slots' order), then the count read back by the host.
-#include "ptmi_common.h"
+//
+// 512 < ndim <= 2048 (HMC only): the same calls and work area with the kernels of ptmi_gjcb_wide.hip -- the whitening products on the
+// matrix cores, one wave per listed chain in the step -- in the order wide_begin / wide_round below give them.
+#include "ptmi_gjcb.h"
 
 namespace {
 
-constexpr int EMAX = 8;              // slots per lane: ptmi_lanes_for_grad keeps ndim <= 8 G
+constexpr int EMAX = 8;              // slots per lane: ptmi_lanes_for_grad keeps ndim <= 8 G for the kernels of this unit
 constexpr int VB = 2048;             // doubles of the block's vector staging area: (256 / G) chains x 8 G elements
-constexpr int LB = 1024;             // chains per block of the listing kernels
-enum { ST_ACT = 0, ST_STAGE = 1, ST_LEFT = 2, ST_NLEAP = 3 };   // int32 scalars of a chain in the work area
-
-// NUTS chains (handles with w_nuts > 0): vector slots of a call [slot][nch][d] -- the initial point, its gradient and the step-size
-// search's momenta, the sample, the two ends (t, r, g) -- then per stack height h the pending left subtree's far end (t, r) and candidate t
-// (its candidate gradient, which the fused kernels carry, is never read: not kept) ...
-enum { NV_Q0 = 0, NV_G0 = 1, NV_R0 = 2, NV_SAMPLE = 3, NV_TM = 4, NV_RM = 5, NV_GM = 6, NV_TP = 7, NV_RP = 8, NV_GP = 9, NV_TOP = 10 };
-enum { NL_FAR_T = 0, NL_FAR_R = 1, NL_CAND_T = 2, NL_VECS = 3 };
-// ... the call's doubles [nch][ND_N] (the pending leapfrog's step, logp0, the search's joint of (q0, r0), its k and eps, the call's joint,
-// logu, lnprob, n) and int32 [nch][NI_N] (phase, draws, leapfrogs, tree height j, direction, pending heights, the search's loop turn and
-// flags), and the stack's scalars [nch][levels][4] (logp, n, alpha, nalpha)
-enum { ND_LEPS = 0, ND_LOGP0 = 1, ND_FJ0 = 2, ND_FK = 3, ND_FEPS = 4, ND_JOINT = 5, ND_LOGU = 6, ND_LNPROB = 7, ND_N = 8, ND_NSC = 9 };
-enum { NI_PHASE = 0, NI_NM = 1, NI_NS = 2, NI_NLEAP = 3, NI_J = 4, NI_DIR = 5, NI_PEND = 6, NI_LOOP = 7, NI_UP = 8, NI_GINF = 9, NI_NSC = 10 };
+constexpr int LB = GJ_LB;            // chains per block of the listing kernels
+// (the work area, its scalars' names and the kernels' arguments: ptmi_gjcb.h)
 // what the gradient of a NUTS chain's round belongs to: the call's initial point, the search's first leapfrog (eps = 1), a turn of its
 // halving loop, a turn of its doubling-or-halving loop, a leaf of the tree
 enum { PH_FIRST = 0, PH_FRE1 = 1, PH_HALVE = 2, PH_DOUBLE = 3, PH_LEAF = 4 };
-
-// The work area (ptmi_gj_work_bytes): q, p, xs [nch][d] doubles (whitened position and momentum; the row a listed chain hands to the
-// callback), joint0 [nch], ist [nch][4] int32 (listed, stage, leapfrogs left, leapfrogs taken), list [nch] int32 (the round's chains),
-// bcnt [nblk] int32 (the listing's block counts), n (int64: the round's count); with NUTS (levels = nuts_maxdepth + 1 > 0) then nv
-// [NV_TOP + 3 levels][nch][d], nd [nch][ND_NSC], ni [nch][NI_NSC], nst [nch][levels][4].
-struct Work {
-    double *q, *p, *xs, *joint0;
-    int32_t *ist, *list, *bcnt;
-    long long *n;
-    double *nv, *nd, *nst;
-    int32_t *ni;
-};
-inline size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
-inline size_t work_layout(long long nch, int d, int levels, char *base, Work *w)
-{
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += al16(bytes); return p; };
-    const size_t nblk = (size_t)((nch + LB - 1) / LB);
-    Work t;
-    t.q = (double *)take(sizeof(double) * (size_t)nch * d);
-    t.p = (double *)take(sizeof(double) * (size_t)nch * d);
-    t.xs = (double *)take(sizeof(double) * (size_t)nch * d);
-    t.joint0 = (double *)take(sizeof(double) * (size_t)nch);
-    t.ist = (int32_t *)take(sizeof(int32_t) * 4 * (size_t)nch);
-    t.list = (int32_t *)take(sizeof(int32_t) * (size_t)nch);
-    t.bcnt = (int32_t *)take(sizeof(int32_t) * nblk);
-    t.n = (long long *)take(sizeof(long long));
-    t.nv = t.nd = t.nst = nullptr;
-    t.ni = nullptr;
-    if (levels > 0) {
-        t.nv = (double *)take(sizeof(double) * (size_t)(NV_TOP + NL_VECS * levels) * nch * d);
-        t.nd = (double *)take(sizeof(double) * (size_t)ND_NSC * nch);
-        t.ni = (int32_t *)take(sizeof(int32_t) * (size_t)NI_NSC * nch);
-        t.nst = (double *)take(sizeof(double) * 4 * (size_t)levels * nch);
-    }
-    if (w) *w = t;
-    return off;
-}
-
-struct GjArgs {
-    Work w;
-    const double *tab;               // [3][d][d] whitening tables (GJT_*: 0 backward, 1 forward, 2 gradient)
-    int diag;                        // the tables are diagonal (ptmi_create): a product is d multiplications
-    int d, nt, W, ntg, temp0, walker0;
-    long long nch, n;                // chains; the round's listed chains (gj_step_kernel)
-    u64 seed;
-    long long it;
-    int hmc_min, hmc_max;
-    double eps;
-    int levels, nuts_maxdepth, gj_nburn;   // NUTS: stack heights of the work area (0: an HMC-only handle), the cap, nburn of dual averaging
-    double nuts_delta;
-    double *Q;                       // the current proposal buffer
-    double *qaux, *gj;
-    const int32_t *temp_of;
-    const double *beta;
-    const double *lnl, *dlnl, *lp, *dlp;   // the callback's values of the round before (lp / dlp may be NULL: a flat prior)
-};
-enum { TB = 0, TF = 1, TG = 2 };
 
 // Table t of the two a kernel uses: in LDS (staged at the kernel's start: slot 0 and 1 of `tl`) or the global copy.
 template <bool TL>
@@ -743,13 +677,24 @@ int launch(ptmi_engine *h, const GjArgs &a, bool begin)
     return PTMI_OK;
 }
 
-// the listing of the round and its count on the host (the round's one synchronisation)
-int list_round(ptmi_engine *h, const GjArgs &a, double *rows, int64_t *n)
+// the listing's kernels: the chains still moving into list[] (and their count into the work area); copy: their rows of xs into rows[]
+void list_kernels(ptmi_engine *h, const GjArgs &a, double *rows, bool copy)
 {
     const unsigned nblk = (unsigned)((a.nch + LB - 1) / LB);
     hipLaunchKernelGGL(gj_count_kernel, dim3(nblk), dim3(LB), 0, h->stream, (const int32_t *)a.w.ist, a.nch, a.w.bcnt);
     hipLaunchKernelGGL(gj_fill_kernel, dim3(nblk), dim3(LB), 0, h->stream, (const int32_t *)a.w.ist, a.nch, (const int32_t *)a.w.bcnt,
-                       (const double *)a.w.xs, a.d, a.w.list, rows, a.w.n);
+                       (const double *)a.w.xs, copy ? a.d : 0, a.w.list, rows, a.w.n);
+}
+
+// the listing of the round and its count on the host (the round's one synchronisation)
+int list_round(ptmi_engine *h, const GjArgs &a, double *rows, int64_t *n, long long bound)
+{
+    if (a.d > PTMI_GJ_REG_MAX) {                                           // wide rows: a wave per row copies them (ptmi_gjcb_wide.hip)
+        list_kernels(h, a, rows, false);
+        if (int rc = ptmi_gjw_rows(h, a, rows, bound)) return rc;
+    } else {
+        list_kernels(h, a, rows, true);
+    }
     HIPCHK(hipGetLastError());
     if (!h->h_gj_n) HIPCHK(hipHostMalloc((void **)&h->h_gj_n, sizeof(long long)));
     HIPCHK(hipMemcpyAsync(h->h_gj_n, a.w.n, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
@@ -758,6 +703,23 @@ int list_round(ptmi_engine *h, const GjArgs &a, double *rows, int64_t *n)
     h->gj_n = *n;
     h->gj_phase = *n > 0 ? PTMI_GJ_ROUNDS : PTMI_GJ_DONE;
     return PTMI_OK;
+}
+
+// 512 < ndim <= 2048 (ptmi_gjcb_wide.hip).  begin: the HMC picks are listed FIRST, so that the row tiles of the forward and backward
+// products hold picks only (their count stays on the device: the grid covers every chain and the blocks past the count leave); a round:
+// the gradient product (into xs, free since the listing copied it out), the step, the backward product, the listing.
+int wide_begin(ptmi_engine *h, const GjArgs &a, double *rows)
+{
+    if (int rc = ptmi_gjw_mark(h, a)) return rc;
+    list_kernels(h, a, rows, false);
+    if (int rc = ptmi_gjw_product(h, a, TF, true)) return rc;
+    return ptmi_gjw_product(h, a, TB, true);
+}
+int wide_round(ptmi_engine *h, const GjArgs &a)
+{
+    if (int rc = ptmi_gjw_product(h, a, TG, false)) return rc;
+    if (int rc = ptmi_gjw_step(h, a)) return rc;
+    return ptmi_gjw_product(h, a, TB, false);
 }
 
 }  // namespace
@@ -795,8 +757,8 @@ int ptmi_gj_begin(ptmi_handle h, int64_t iter, void *work, double *rows, int64_t
     if (((uintptr_t)work & 15) != 0) return fail(PTMI_EINVAL, "ptmi_gj_begin: the work area must be 16-byte aligned");
     h->gj_work = work;
     GjArgs a = make_gj_args(h, work);
-    if (int rc = launch(h, a, true)) return rc;
-    return list_round(h, a, rows, n);
+    if (int rc = a.d > PTMI_GJ_REG_MAX ? wide_begin(h, a, rows) : launch(h, a, true)) return rc;
+    return list_round(h, a, rows, n, a.nch);
 }
 
 int ptmi_gj_step(ptmi_handle h, void *work, const double *lnl, const double *dlnl, const double *lp, const double *dlp, double *rows,
@@ -809,8 +771,8 @@ int ptmi_gj_step(ptmi_handle h, void *work, const double *lnl, const double *dln
     GjArgs a = make_gj_args(h, work);
     a.n = h->gj_n;
     a.lnl = lnl; a.dlnl = dlnl; a.lp = lp; a.dlp = dlp;
-    if (int rc = launch(h, a, false)) return rc;
-    return list_round(h, a, rows, n);
+    if (int rc = a.d > PTMI_GJ_REG_MAX ? wide_round(h, a) : launch(h, a, false)) return rc;
+    return list_round(h, a, rows, n, a.n);                               // (a round lists no more chains than the one before)
 }
 
 }  // extern "C"

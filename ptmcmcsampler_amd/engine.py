@@ -126,6 +126,9 @@ class PTEngine(object):
     the trees built round by round from the batched gradient callbacks (``gradient_stage``).  Opt-in: an iteration then takes as
     many host-synchronised callback rounds as its deepest tree has leaves (a chain's first NUTS call up to ~200 more for the
     step-size search), and the stage's work area grows with ``nuts_maxdepth`` (include/ptmi.h ``ptmi_gj_work_bytes``).
+    ``grad_weights`` beyond 512 parameters, up to 2048: HMC alone on the callback path -- ``split=True`` or ``rows_logl=True`` with
+    ``grad_weights=(0, w_hmc)``; the stage's whitening products then run on the matrix cores (csrc/ptmi_gjcb_wide.hip).  NUTS
+    (``grad_weights[0] > 0``, ``split_nuts=True``), the fused kernels' gradient jumps and the interval family stop at 512: ValueError.
     ``eig_mode``: who factorizes the adapted covariance at a covariance epoch (PTMCMCSampler.py:797-803): ``"lapack"`` = the
     host, exactly as the reference (``np.linalg.svd`` per walker); ``"jacobi"`` = ``ptmi_eig_jacobi`` on the device, one
     block per walker, no host round trip (ndim <= 101, one parameter group; same subspaces, its own sign rule); ``"ql"`` =
@@ -160,7 +163,7 @@ class PTEngine(object):
     built-in likelihood and prior as ROW kernels over the launch's proposals (``ptmi_rows_logl``, ``ptmi_rows_logp``; for the dense
     family one matrix-core product per iteration, csrc/ptmi_dense_rows.hip), accept -- instead of the fused step kernels, which beyond
     104 parameters stream the d x d table per chain-step from L2.  The same chains bit for bit (the row kernels restate the oracle's
-    sums); HMC / NUTS in the cycle are served by ``ptmi_rows_logl_grad`` through the batched gradient stage (ndim <= 512).  Whatever
+    sums); HMC / NUTS in the cycle are served by ``ptmi_rows_logl_grad`` through the batched gradient stage (NUTS: ndim <= 512; HMC: ndim <= 2048).  Whatever
     ``run_callback`` supports; not with ``w_host`` or a sharded ladder (``ntemps_global`` / ``temp0``).  ``am_mode="auto"`` is ``"rows"``
     here (the split path stores every rank-0 row), so with a POOLED covariance the bits are those of the fused path with
     ``am_mode="rows"``; its default ``"rle"`` sums the same pooled statistics in another order.
@@ -316,6 +319,18 @@ class PTEngine(object):
             raise ValueError("the callback path (split=True) runs HMC with batched gradient callbacks, not NUTS: grad_weights=(0, w_hmc)")
         self.split_nuts = bool(split_nuts)
         has_gj = sum(self.grad_weights) > 0
+        if int(ndim) > 512 and (has_gj or split_nuts):
+            # beyond the fused gradient kernels (ndim <= 512): HMC alone, through the batched gradient stage of the callback path
+            if int(ndim) > 2048:
+                raise ValueError("gradient jumps (grad_weights) stop at ndim 2048 (got %d)" % int(ndim))
+            if self.grad_weights[0] > 0 or split_nuts:
+                raise ValueError("NUTS (grad_weights[0] > 0, split_nuts=True) is built for ndim <= 512 (got %d): beyond, up to 2048, "
+                                 "the callback path runs HMC alone, grad_weights=(0, w_hmc)" % int(ndim))
+            if not split:
+                raise ValueError("gradient jumps in the fused kernels are built for ndim <= 512 (got %d): beyond, up to 2048, HMC runs "
+                                 "on the callback path (split=True or rows_logl=True, grad_weights=(0, w_hmc))" % int(ndim))
+            if logl[0] == "interval":
+                raise ValueError("the interval likelihood is built for ndim <= 512 (got %d)" % int(ndim))
         self.gj_tab = np.zeros(0)
         if has_gj:
             import scipy.linalg as sl

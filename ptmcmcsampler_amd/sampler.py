@@ -166,11 +166,18 @@ class PTSampler(object):
         self.device_grads = self.logl_spec is not None and logl_grad is True and logp_grad is True
         if self.logl_spec is not None and not self.device_grads and (logl_grad is not None or logp_grad is not None):
             raise ValueError("with a device likelihood pass logl_grad=True, logp_grad=True to use its built-in gradients")
+        # beyond the 512 parameters of the fused gradient kernels the built-in gradients are served on the row path (HMC through the
+        # batched gradient stage, ptmi_rows_logl_grad as its callback): chosen here, beside resolve_rows_logl, unless the caller decided
+        if self.device_grads and rows_logl is None and int(ndim) > self.GRAD_FUSED_MAX and self.resolve_rows_logl(ndim, logl, logp, True):
+            self.rows_logl = True
         if self.logl_spec is None and logl_grad is not None and logp_grad is not None:
             self.logl_grad = _function_wrapper(logl_grad, loglargs, loglkwargs)
             self.logp_grad = _function_wrapper(logp_grad, logpargs, logpkwargs)
         # batched_nuts=True: NUTS on the batched gradient callbacks too (PTEngine(split_nuts=True))
         self.batched_nuts = bool(batched_nuts)
+        if self.batched_nuts and int(ndim) > self.GRAD_FUSED_MAX:
+            raise ValueError("batched_nuts=True is built for ndim <= %d (got %d): beyond, up to 2048, the batched gradient callbacks run HMC "
+                             "alone" % (self.GRAD_FUSED_MAX, int(ndim)))
         if self.batched_nuts and not (self.batched and self.logl_grad is not None and self.logp_grad is not None):
             raise ValueError("batched_nuts=True runs NUTS on batched gradient callbacks: it needs batched=True with callable logl_grad and "
                              "logp_grad")
@@ -195,6 +202,8 @@ class PTSampler(object):
         self._batched_jumps = []                             # cycle entries added with addProposalToCycle(..., batched=True)
         self.engine = None
         self._ctx = (0, 0)
+
+    GRAD_FUSED_MAX = 512     # parameters up to which the fused kernels (and NUTS anywhere) serve the gradient jumps
 
     @staticmethod
     def resolve_rows_logl(ndim, logl, logp, rows_logl=None):
@@ -286,6 +295,9 @@ class PTSampler(object):
             raise NotImplementedError("batched gradient callbacks (batched=True with logl_grad / logp_grad) run HMC only unless NUTS is "
                                       "asked for (NUTSweight=%r): pass NUTSweight=0, or batched_nuts=True to build the NUTS trees "
                                       "round by round from the callbacks" % (NUTSweight,))
+        if (self.device_grads or self._batched_grads) and self.ndim > self.GRAD_FUSED_MAX and NUTSweight > 0:
+            raise NotImplementedError("NUTS on the device is built for ndim <= %d (got %d, NUTSweight=%r): pass NUTSweight=0; HMC "
+                                      "(HMCweight) runs up to 2048 parameters" % (self.GRAD_FUSED_MAX, self.ndim, NUTSweight))
         if maxIter is None:
             maxIter = Niter
         self.ladder, self.covUpdate, self.burn, self.Tskip = ladder, covUpdate, burn, Tskip

@@ -4,6 +4,7 @@ callback rounds per iteration (mean, max), rows per round (mean, and the share o
 with --profile -- the library's kernels' share of the wall time against the callback's.
 
     python tools/gj_callback_timing.py [--ntemps 64 --nwalkers 1024 --ndim 40 --iters 50 --warmup 10] [--profile] [--only CALLBACK CYCLE]
+    python tools/gj_callback_timing.py --ndim 1000 --nwalkers 256 --epoch 1000 --only iso hmc     (beyond 512-d: HMC, the iso callback)
 
 Two callbacks, each with five cycles -- SCAM + HMC, HMC only, NUTS only, SCAM + NUTS, and sample()'s default mix SCAM = AM = DE = NUTS =
 HMC = 20 (NUTS on the split path: PTEngine(split_nuts=True)).  The NUTS cycles are timed in steady state: after --nuts-warmup
@@ -28,7 +29,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 LIB_KERNELS = ("split_rows_kernel", "gj_begin_kernel", "gj_step_kernel", "gj_count_kernel", "gj_fill_kernel", "rows_iso_kernel", "am_",
-               "set_iter_kernel")
+               "set_iter_kernel", "gjw_")                      # gjw_: the stage beyond 512-d (csrc/ptmi_gjcb_wide.hip)
 
 
 def interval_callbacks(d, a=0.0, b=10.0):
@@ -59,9 +60,13 @@ def run_case(args, which, cycle):
     nuts = grad_weights[0] > 0
     warmup = args.nuts_warmup if nuts else args.warmup
     # the default mix: its covariance epoch, DE's start and the end of NUTS's step-size adaptation all fall inside the warm-up
-    burn = warmup if weights[1] + weights[2] > 0 else 100000
+    burn = warmup if weights[1] + weights[2] > 0 else args.epoch     # (the AM ring is nwalkers x epoch x ndim doubles)
     logl_name = ("iso",) if which == "iso" else ("interval", 0.0, 10.0)
-    g = PTEngine(d, nt, W, np.eye(d) * (0.5 if which == "interval" else 1.0), logl=logl_name, weights=weights, grad_weights=grad_weights,
+    cov0 = np.eye(d) * (0.5 if which == "interval" else 1.0)
+    if args.full_cov:                                            # full whitening tables (the identity's are diagonal: d multiplications)
+        A = np.random.RandomState(1).randn(d, d)
+        cov0 = A @ A.T / d + 0.5 * np.eye(d)
+    g = PTEngine(d, nt, W, cov0, logl=logl_name, weights=weights, grad_weights=grad_weights,
                  hmc=(args.eps, 2, args.hmc_steps), cov_update=burn, burn=burn, tskip=0, seed=5, split=True, split_nuts=nuts,
                  cov_mode="pooled", am_mode="rows")
     if which == "iso":
@@ -105,7 +110,7 @@ def run_case(args, which, cycle):
     allrows = np.array([n for r in rows for n in r], dtype=np.int64)
     r = dict(callback=which, cycle=cycle, ndim=d, ntemps=nt, nwalkers=W, iters=args.iters, wall_s=wall,
              updates_per_s=W * nt * args.iters / wall, leapfrogs_per_s=float(nleap) / wall,
-             rounds_per_iter=float(allrows.size) / args.iters, rounds_per_iter_max=int(nrounds.max()) if nrounds.size else 0,
+             rounds_per_iter=float(allrows.size) / args.iters, us_per_round=1e6 * wall / max(1, allrows.size), rounds_per_iter_max=int(nrounds.max()) if nrounds.size else 0,
              rows_per_round=float(allrows.mean()) if allrows.size else 0.0,
              rounds_under_1pct=float((allrows < 0.01 * W * nt).mean()) if allrows.size else 0.0,
              hmc_share=float(js[..., 4, 0].sum() / js[..., 0].sum()), hmc_accept=float(js[..., 4, 1].sum() / max(1, js[..., 4, 0].sum())))
@@ -144,6 +149,9 @@ def main():
     ap.add_argument("--nuts-warmup", type=int, default=30)
     ap.add_argument("--eps", type=float, default=0.4)
     ap.add_argument("--hmc-steps", type=int, default=50)
+    ap.add_argument("--epoch", type=int, default=100000, help="covariance epoch and burn of the cycles without AM / DE: beyond the run; "
+                    "a smaller one keeps the AM ring of a large ndim in memory")
+    ap.add_argument("--full-cov", action="store_true", help="a full initial covariance instead of the identity: full whitening tables")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--only", nargs=2, metavar=("CALLBACK", "CYCLE"))
     ap.add_argument("--out", default=None, help="profile databases go under this directory (default: a temporary one)")
@@ -158,7 +166,7 @@ def main():
             cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", os.path.join(out, name), "-o", name, "--", sys.executable,
                    os.path.abspath(__file__), "--only", which, cycle] + [
                 "--%s=%s" % (k.replace("_", "-"), getattr(args, k)) for k in ("ndim", "ntemps", "nwalkers", "iters", "warmup", "nuts_warmup", "eps",
-                                                                              "hmc_steps")]
+                                                                              "hmc_steps", "epoch")] + (["--full-cov"] if args.full_cov else [])
             p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
             if p.returncode != 0:
                 print(p.stdout[-3000:])
