@@ -525,6 +525,36 @@ int ptmi_aux_begin(ptmi_handle h, int64_t iter, double *xrows /* dev [W*T][ndim]
 int ptmi_aux_end(ptmi_handle h, const double *qrows /* dev [W*T][ndim], or NULL: the proposal buffer was edited in place */,
                  const double *qxy /* dev [W*T] or NULL */);
 
+/* The likelihood callback only inside the prior's support, on the split path's batched callbacks (csrc/ptmi_sup.hip).  The reference
+ * reads lp = logp(y) and calls logl(y) only when lp != -inf (PT:605-612; the first evaluation the same, PT:479-487).  Between the prior
+ * callback and the likelihood callback over n_in rows of ndim doubles -- the proposal buffer, or any other row tensor:
+ *
+ *     lp = prior callback on rows_in [n_in][ndim]
+ *     ptmi_sup_begin(h, work, lp, n_in, &n);
+ *     n == n_in: vals = likelihood callback on rows_in itself (no copy);  out = vals
+ *     n == 0:    no likelihood call;                                      ptmi_sup_end(h, work, NULL, out)
+ *     else:      ptmi_sup_rows(h, work, rows_in, rows);  vals = likelihood callback on rows[0 .. n);  ptmi_sup_end(h, work, vals, out)
+ *
+ * ptmi_sup_begin lists the rows k with lp[k] != -inf in ascending k -- NaN and +inf are listed: the reference tests lp == -inf and
+ * nothing else -- and leaves pos[k], the row's rank in the list or -1, in the work area: counts per block of 1024 rows, ONE block that
+ * scans the block counts once, the ranks by ballots inside each block.  No atomics: the same order on every run.  *n (HOST) is the
+ * number of listed rows: one stream synchronisation, the only read-back the stage adds.  A new ptmi_sup_begin replaces an open stage; one that is
+ * REFUSED (a NULL or misaligned argument, n_in out of range, ptmi_device_iter mode) has launched nothing and changed nothing: a stage that
+ * was open stays open, as it does behind a refused ptmi_sup_rows / ptmi_sup_end.
+ * ptmi_sup_rows copies listed row j to rows[j] (launched behind the read-back: its grid is sized from n, a row to a wave; contiguous
+ * 16-byte pieces, 8-byte for odd ndim); nothing is launched when n == 0.  ptmi_sup_end writes out[k] = pos[k] >= 0 ? vals[pos[k]] : -inf
+ * for all n_in rows (vals == NULL: -inf everywhere) and ends the stage.
+ * work: caller-owned device memory of ptmi_sup_work_bytes(n_in) bytes, 16-byte aligned (pos, the list, the block counts and starts, the
+ * total); rows_in and rows 16-byte aligned (8-byte for odd ndim).  ptmi_sup_rows / ptmi_sup_end refuse (PTMI_EINVAL) without a
+ * ptmi_sup_begin on the same work area; n_in outside [1, 2^31) and misaligned pointers are refused too.  Not in ptmi_device_iter
+ * mode (PTMI_EUNSUPPORTED: the count is read on the host).  The accept test never reads the likelihood of a row whose prior is -inf,
+ * so a run with the stage equals a run without it bit for bit for any row-wise callback.  State lives in the handle: ptmi_config and
+ * ptmi_buffers are unchanged.  On the handle's stream. */
+int ptmi_sup_work_bytes(ptmi_handle h, int64_t n_in, size_t *bytes);
+int ptmi_sup_begin(ptmi_handle h, void *work, const double *lp /* dev [n_in] */, int64_t n_in, int64_t *n /* host */);
+int ptmi_sup_rows(ptmi_handle h, void *work, const double *rows_in /* dev [n_in][ndim] */, double *rows /* dev [n][ndim] */);
+int ptmi_sup_end(ptmi_handle h, void *work, const double *vals /* dev [n] or NULL */, double *out /* dev [n_in] */);
+
 /* Self-test hooks used by the parity tests: evaluate the device's deterministic math on
  * n inputs (op: 0 log, 1 exp, 2 cos2pi, 3 sqrt, 4 reciprocal-free divide a/b with b=in2). */
 int ptmi_selftest_math(int device, int op, const double *in, const double *in2, double *out, int64_t n);

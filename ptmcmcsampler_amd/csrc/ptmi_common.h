@@ -225,6 +225,11 @@ struct ptmi_engine {
     // split path with batched auxiliary jumps (ptmi_aux.hip): attached (ptmi_aux_attach), and where the stage of the current proposals
     // is (PTMI_GJ_* as above; ROUNDS = between ptmi_aux_begin and ptmi_aux_end)
     int aux_on, aux_phase;
+    // the likelihood callback inside the prior's support (ptmi_sup.hip): the work area of the open stage (nullptr: none; between
+    // ptmi_sup_begin and ptmi_sup_end), the rows it was offered and the rows it listed, and the pinned word the count is read into
+    void *sup_work;
+    long long sup_nin, sup_n;
+    long long *h_sup_n;
 };
 enum { PTMI_GJ_NONE = 0, PTMI_GJ_PENDING = 1 /* proposals made, ptmi_gj_begin not yet called */, PTMI_GJ_ROUNDS = 2, PTMI_GJ_DONE = 3 };
 // the split path's refusals for gradient jumps (0: served; else the code, with the message set)

@@ -183,6 +183,13 @@ class PTEngine(object):
     order given, each on the ``Q`` of the one before, their ``qxy`` added to the jump's in that order (``aux_stage``).  Not in graph mode.
     ``jumps_with_grad`` and ``aux`` are keywords of the alternative constructor ``PTEngine.with_stages(..., jumps_with_grad=True,
     aux=[f])``, which takes everything the plain constructor takes: the plain constructor's parameters stay what they were.
+    ``with_stages(..., logl_in_support=True)`` (``split=True`` or ``rows_logl=True``): the likelihood callback is called only on rows
+    inside the prior's support, as the reference does it (``lp = logp(y)``; ``logl(y)`` only when ``lp != -inf``, PTMCMCSampler.py:605-612,
+    479-487) -- ``eval_callback`` lists the rows whose prior is not -inf (include/ptmi.h ``ptmi_sup_*``: one host read-back per iteration),
+    hands ``logl`` the compacted rows ``[n, d]`` and scatters its ``n`` values back.  For likelihoods that are undefined outside the support
+    (a Cholesky factorization, a logarithm of a parameter) and for expensive ones under a tight prior; the chains are the same bit for
+    bit for a row-wise callback.  The gradient callbacks are not filtered (the reference's are not either, nutsjump.py:71-76).  With a flat
+    prior (``logp=None``) the stage launches nothing.  Not in graph mode.  ``support_counts``: (rows offered, rows handed to ``logl``).
     ``stats_async`` (pooled covariance with ``eig_lag >= 1``): the statistics of a covariance period that is over need nothing the next
     launches touch once those write ANOTHER ring -- so the engine keeps two rings (``t["AM"]`` is always the one in use), switches at
     every covariance epoch, and runs the period's statistics (``ptmi_update_cov_on``) and the factorization behind them on a side
@@ -194,15 +201,18 @@ class PTEngine(object):
     # what PTEngine.with_stages sets on the instance before __init__ runs (the plain constructor leaves the class defaults)
     jumps_with_grad = False
     _aux = ()
+    logl_in_support = False
 
     @classmethod
-    def with_stages(cls, *args, jumps_with_grad=False, aux=None, **kw):
+    def with_stages(cls, *args, jumps_with_grad=False, aux=None, logl_in_support=False, **kw):
         """``PTEngine(*args, **kw)`` with the stages of the composed ``_jump`` on the callback path (see the class docstring):
-        ``jumps_with_grad=True`` lets ``jumps=`` stand beside ``grad_weights`` in one cycle, ``aux=[func, ...]`` are the auxiliary jumps.
+        ``jumps_with_grad=True`` lets ``jumps=`` stand beside ``grad_weights`` in one cycle, ``aux=[func, ...]`` are the auxiliary jumps,
+        ``logl_in_support=True`` hands the likelihood callback only the rows whose prior is not -inf (``eval_callback``).
         The plain constructor keeps the parameters it had (tests/test_gj_groups.py holds them to the letter) and its refusals."""
         self = cls.__new__(cls)
         self.jumps_with_grad = bool(jumps_with_grad)
         self._aux = list(aux) if aux is not None else []
+        self.logl_in_support = bool(logl_in_support)
         self.__init__(*args, **kw)
         return self
 
@@ -247,6 +257,11 @@ class PTEngine(object):
                 raise ValueError("aux=[func, ...] takes callables func(X[n, d], Q[n, d], iter, beta[n]) -> (Q[n, d], qxy[n] | 0 | None)")
             if not (split or rows_logl):
                 raise ValueError("aux= are served on the callback path: split=True (or rows_logl=True)")
+        # the likelihood callback only inside the prior's support (with_stages(logl_in_support=True); see the class docstring)
+        self.support_counts = (0, 0)                                  # rows offered to the stage, rows it handed to logl
+        if self.logl_in_support and not (split or rows_logl):
+            raise ValueError("logl_in_support=True is a stage of the callback path: split=True (or rows_logl=True); the fused kernels "
+                             "have no likelihood callback to spare")
         # rows_logl: the built-in likelihood as a row kernel on the split path (see the class docstring); refused before anything is built
         self.rows_logl = bool(rows_logl)
         if self.rows_logl:
@@ -1001,19 +1016,28 @@ class PTEngine(object):
         self.iter = last
 
     # ------------------------------------------------------------------ batched callbacks
-    def _cb_values(self, v):
-        """A callback's return value as a contiguous f64 tensor of W * nt values on this GPU (no copy when it already is one)."""
+    def _cb_values(self, v, n=None, what="the callback"):
+        """A callback's return value as a contiguous f64 tensor on this GPU (no copy when it already is one): W * nt values as [W][nt],
+        or ``n`` values (the rows the support stage handed over); another count is a ValueError that names it."""
         torch = _torch()
-        if not (torch.is_tensor(v) and v.dtype == torch.float64 and v.device == self.device and v.is_contiguous() and v.numel() == self.W * self.nt):
-            v = torch.as_tensor(v, dtype=torch.float64, device=self.device).reshape(self.W, self.nt).contiguous()
-        return v
+        want = self.W * self.nt if n is None else int(n)
+        if not (torch.is_tensor(v) and v.dtype == torch.float64 and v.device == self.device and v.is_contiguous()):
+            v = torch.as_tensor(v, dtype=torch.float64, device=self.device).contiguous()
+        if v.numel() != want:
+            raise ValueError("%s returned %d values for n = %d rows" % (what, v.numel(), want))
+        return v if n is not None else v.reshape(self.W, self.nt)
 
     def eval_callback(self, X, logl, logp):
         """logp then logl of every row of the device tensor X [W][nt][d] through BATCHED callbacks
         ``f(X[n, d]) -> [n]`` (torch tensors on this GPU in, the same out): the device-side form of the reference's
         ``_function_wrapper`` boundary (PTMCMCSampler.py:1072-1086, called at :605-611).  Nothing is copied to the host.
         ``logp=None`` is the flat prior (no launch at all).  Where the prior is -inf the likelihood value is not used: the reference
-        does not even call it (:607-608), here the accept test never reads it (ptmi_accept: -inf prior => -inf posterior)."""
+        does not even call it (:607-608), here the accept test never reads it (ptmi_accept: -inf prior => -inf posterior).
+        ``with_stages(logl_in_support=True)``: the reference's rule itself -- ``logl`` is handed only the rows whose prior is not -inf
+        (``ptmi_sup_begin`` lists them in row order, one host read-back: their number ``n``): the tensor itself when that is every row
+        (no copy), no call at all when it is none, else the listed rows compacted into ``rows[:n]`` (``ptmi_sup_rows``) and its ``n``
+        values put back, -inf elsewhere (``ptmi_sup_end``).  A likelihood that is only defined inside the support runs that way; for a
+        row-wise callback the chains are the same bit for bit.  ``support_counts`` = (rows offered, rows handed to ``logl``) so far."""
         flat = X.view(-1, self.d)
         if logp is None:
             if getattr(self, "_lp_zero", None) is None:
@@ -1021,7 +1045,37 @@ class PTEngine(object):
             lp = self._lp_zero
         else:
             lp = self._cb_values(logp(flat))
+            if self.logl_in_support:
+                return self._logl_in_support(flat, lp, logl), lp
         return self._cb_values(logl(flat)), lp
+
+    def _logl_in_support(self, flat, lp, logl):
+        """``eval_callback`` with the support stage: the likelihood values [W][nt] of the rows ``flat`` whose prior ``lp`` is not -inf."""
+        torch = _torch()
+        n_in = self.W * self.nt
+        lib, h = self.lib, self.h
+        if getattr(self, "_sup_work", None) is None:
+            nb = C.c_size_t(0)
+            _lib.check(lib.ptmi_sup_work_bytes(h, n_in, C.byref(nb)))
+            self._sup_work = torch.empty(nb.value, dtype=torch.uint8, device=self.device)
+            self._sup_rows = None                                     # [n_in][d], at the first partly supported batch
+        work = self._sup_work.data_ptr()
+        n = C.c_int64(0)
+        _lib.check(lib.ptmi_sup_begin(h, work, lp.data_ptr(), n_in, C.byref(n)))
+        n = int(n.value)
+        self.support_counts = (self.support_counts[0] + n_in, self.support_counts[1] + n)
+        if n == n_in:
+            return self._cb_values(logl(flat), what="logl")           # (the stage left open is replaced by the next ptmi_sup_begin)
+        out = torch.empty((self.W, self.nt), dtype=torch.float64, device=self.device)
+        if n == 0:
+            _lib.check(lib.ptmi_sup_end(h, work, None, out.data_ptr()))
+            return out
+        if self._sup_rows is None:
+            self._sup_rows = torch.empty((n_in, self.d), dtype=torch.float64, device=self.device)
+        _lib.check(lib.ptmi_sup_rows(h, work, flat.data_ptr(), self._sup_rows.data_ptr()))
+        v = self._cb_values(logl(self._sup_rows[:n]), n, "logl (logl_in_support: of %d rows)" % n_in)
+        _lib.check(lib.ptmi_sup_end(h, work, v.data_ptr(), out.data_ptr()))
+        return out
 
     def init_state_callback(self, p0, logl, logp, i0=0):
         """init_state for a likelihood that lives in a batched callback (:479-487)."""
@@ -1316,11 +1370,14 @@ class PTEngine(object):
         must be graph-safe (no host synchronisation, the same launches for every batch: any fixed torch expression or device
         kernel is).  What the captured launches bake in -- the DE ring's head, whether DE is in the cycle -- is part of the cache
         key.  Returns False where it does not apply (AM entries in the cycle: their increments are listed on the host's iteration;
-        configurations the row kernels do not serve; HMC or NUTS in the cycle: their rounds are counted on the host): the caller then runs
+        configurations the row kernels do not serve; HMC or NUTS in the cycle: their rounds are counted on the host; ``logl_in_support`` with a
+        prior callback: its count is read on the host): the caller then runs
         ``callback_segment``.  Same results, bit for bit."""
         torch = _torch()
         if self.t["Q2"] is None or self.weights[1] > 0 or sum(self.grad_weights) > 0 or self._jumps or self._aux:
             return False                                              # (custom jumps: their spans are read on the host; auxiliary jumps: not captured)
+        if self.logl_in_support and logp is not None:
+            return False                                              # (the support stage reads its count on the host)
         if getattr(self, "_graphs", None) is None:
             self._graphs = {}
         L = end - it + 1

@@ -27,7 +27,9 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
   callback rounds as its deepest tree has leaves (without it pass ``NUTSweight=0``); batched custom jumps ride the same cycle
   beside them.  Auxiliary jumps in the batched signature too once ``sampler.batched_aux = True`` is set -- ``addAuxilaryJump(func, batched=True)``:
   ``func(X[n, ndim], Q[n, ndim], iter, beta[n]) -> (Q'[n, ndim], qxy[n] | 0 | None)`` for every chain, behind the jump
-  (``PTEngine.aux_stage``) -- opt-in: every iteration then gathers the chains' states;
+  (``PTEngine.aux_stage``) -- opt-in: every iteration then gathers the chains' states.  ``sampler.logl_in_support = True`` (before
+  ``sample()``; also with a device likelihood and ``rows_logl=True``): ``logl`` gets only the rows whose prior is not -inf, the reference's
+  rule (PTMCMCSampler.py:605-612) -- for likelihoods undefined outside the support; opt-in: one more host read-back per iteration;
 * engine options: ``cov_mode="pooled"`` (one covariance adapted from all walkers instead of one per walker),
   ``swap_mode="oddeven"`` (disjoint swap pairs instead of the reference's hot -> cold sweep), ``pick_mode="walker"`` (one
   proposal-type draw per walker and iteration), ``eig_mode="ql"`` / ``"jacobi"`` / ``"sytrd"`` / ``"hipsolver"`` (covariance epochs factorized on the device: per-walker matrices by
@@ -127,6 +129,10 @@ class PTSampler(object):
     # auxiliary stage (PTEngine.with_stages(aux=...)).  An attribute, not a constructor keyword: tests/test_gj_groups.py holds __init__'s
     # parameters to the letter
     batched_aux = False
+    # s.logl_in_support = True (before sample()): on the device callback path -- batched=True, or a device likelihood with rows_logl=True --
+    # the likelihood is called only on the rows inside the prior's support, as the reference calls it (PTMCMCSampler.py:605-612;
+    # PTEngine.with_stages(logl_in_support=True)).  An attribute for the same reason as batched_aux
+    logl_in_support = False
 
     def __init__(self, ndim, logl, logp, cov, groups=None, loglargs=[], loglkwargs={}, logpargs=[], logpkwargs={},
                  logl_grad=None, logp_grad=None, comm=None, outDir="./chains", verbose=True, resume=False, seed=None,
@@ -424,6 +430,14 @@ class PTSampler(object):
         if self._batched_aux and not stage_ok:
             raise ValueError("a batched auxiliary jump (addAuxilaryJump(..., batched=True)) runs on the device callback path: PTSampler(..., "
                              "batched=True), or a device likelihood with rows_logl=True; this sampler calls its jumps per chain")
+        if self.logl_in_support and not stage_ok:
+            if self.logl is not None:
+                raise ValueError("logl_in_support = True is a stage of the device callback path (PTSampler(..., batched=True), or a device "
+                                 "likelihood with rows_logl=True): this sampler calls logl per chain, and per chain it is already called "
+                                 "only where the prior is not -inf")
+            raise ValueError("logl_in_support = True is a stage of the device callback path (PTSampler(..., batched=True), or a device "
+                             "likelihood with rows_logl=True): this sampler's likelihood runs inside the fused step kernels, which have no "
+                             "callback to spare")
         if self._batched_aux and self.aux:
             raise NotImplementedError("auxiliary jumps per chain and batched=True ones cannot be mixed: the per-chain ones need every "
                                       "proposal on the host")
@@ -451,6 +465,7 @@ class PTSampler(object):
             split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
             jumps=[(f, n) for f, n in stage_list] if stage_list else None,
             jumps_with_grad=bool(stage_list) and sum(self._grad_weights) > 0, aux=list(self._batched_aux) or None,
+            logl_in_support=bool(self.logl_in_support),
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     # ------------------------------------------------------------------ sample (:374-528)
