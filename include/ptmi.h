@@ -304,15 +304,25 @@ int ptmi_am_expand(ptmi_handle h, int32_t w0, int32_t nw, int64_t iter_lo, int64
  * largest component positive.  Same subspaces as LAPACK, but not its column signs: a run adapted this way is not a
  * bit-replica of one adapted through the host.  Asynchronous on the handle's stream. */
 int ptmi_eig_jacobi(ptmi_handle h);
-/* The same by Householder tridiagonalization + implicit QL iterations (oracle: orc_eig_ql; ndim <= 128): one block of two waves per
- * matrix, two per CU at ndim = 100.  The choice for thousands of per-walker covariances: a 100 x 100 matrix takes a quarter of the
- * Jacobi kernel's time on the nearly degenerate spectra an isotropic target adapts to.  Eigenvalues in absolute value, descending;
- * sign rule as ptmi_eig_jacobi.  Asynchronous on the handle's stream. */
+/* The same by Householder tridiagonalization + implicit QL iterations (oracle: orc_eig_ql; ndim <= 1024, parameter groups included: one
+ * factorization per group's block, a group may not repeat a parameter).  The choice for thousands of per-walker covariances: a
+ * 100 x 100 matrix takes a quarter of the Jacobi kernel's time on the nearly degenerate spectra an isotropic target adapts to.
+ * Eigenvalues in absolute value, descending; sign rule as ptmi_eig_jacobi.  Asynchronous on the handle's stream.  Two forms, the same
+ * bits (a matrix here is the full covariance or a group's block):
+ *  - up to 128 x 128 the matrix lives in LDS: one block of two waves per matrix, two per CU at ndim = 100; from 64 matrices on as
+ *    three kernels, reduce -> the scalar chains of all matrices at once -> apply (PTMI_QL_SPLIT = 1 / 0 forces either, a test hook);
+ *  - beyond, up to 1024 x 1024 (csrc/ptmi_eig_wide.hip), always as reduce -> chains -> apply with the matrix in a global scratch, the
+ *    apply step tiled over matrices x rows.  The scratch is some 7 n^2 doubles per matrix (15 MB at 512, 59 MB at 1024): the
+ *    matrices are factorized in batches that fit 4096 MB (at least one matrix per batch), queued one after another on the stream;
+ *    results do not depend on the batch.  A matrix whose rotations do not fit the record (3 n^2) is redone with the chain and the
+ *    rows together; PTMI_QL_SPLIT = 0 (the same test hook) sends every matrix that way.
+ * ndim > 1024: PTMI_EUNSUPPORTED. */
 int ptmi_eig_ql(ptmi_handle h);
 /* ptmi_eig_ql on `stream` (NULL: the handle's), reading `cov_in` (NULL: the cov buffer) and writing `Ut_out` / `S_out` (NULL: the Ut / S
  * buffers), one parameter group: the engine's eig_lag with per-walker covariances runs the factorization of a covariance epoch
  * (:797-803) on a side stream beside the step launches that follow and puts its tables into force a fixed number of launches later
- * (oracle: OracleEngine(eig_lag=L)).  One call at a time per handle. */
+ * (oracle: OracleEngine(eig_lag=L)).  Both forms of ptmi_eig_ql, ndim <= 1024; the scratch is the handle's: one call at a time per
+ * handle. */
 int ptmi_eig_ql_from(ptmi_handle h, void *stream, const double *cov_in, double *Ut_out, double *S_out);
 /* The same for ONE large pooled covariance (3 <= ndim <= 1024; the engine's eig_mode "sytrd"), all of it the library's own kernels:
  * Householder tridiagonalization in ONE kernel with the matrix in the LDS of its blocks (csrc/ptmi_eig.hip sytrd_lds_kernel), the

@@ -83,6 +83,7 @@ def build(force=False, verbose=False, jobs=None):
     os.makedirs(OBJ, exist_ok=True)
     work = [(os.path.join(CSRC, "ptmi_abi.hip"), os.path.join(OBJ, "abi.o"), []),
             (os.path.join(CSRC, "ptmi_eig.hip"), os.path.join(OBJ, "eig.o"), []),             # the device eigensolvers ("jacobi", "ql", "sytrd")
+            (os.path.join(CSRC, "ptmi_eig_wide.hip"), os.path.join(OBJ, "eig_wide.o"), []),   # ... "ql" beyond 128 x 128: the matrix in a global scratch
             (os.path.join(CSRC, "ptmi_swap.hip"), os.path.join(OBJ, "swap.o"), []),           # the PT swap and the block-edge exchange
             (os.path.join(CSRC, "ptmi_split.hip"), os.path.join(OBJ, "split.o"), []),         # the split path's row kernels (shape-independent)
             (os.path.join(CSRC, "ptmi_gjcb.hip"), os.path.join(OBJ, "gjcb.o"), []),           # ... and its HMC stage for gradient callbacks

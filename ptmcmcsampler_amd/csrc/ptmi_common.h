@@ -21,7 +21,8 @@ int ptmi_fail(int code, const char *fmt, ...);
 //   PTMI_SWAP_FUSED          0: the swap as swap_prepare_kernel + swap_sweep_kernel, not swap_fused_kernel [1]
 //   PTMI_ULDS_PERS           0: SCAM-only cycles with one table take a table copy per block, not the persistent kernel [1]
 //   PTMI_SPLIT_ROWS          0: the split path through the shape kernels' propose / accept, not the row kernels [1]
-//   PTMI_QL_SPLIT            1 / 0: ptmi_eig_ql as reduce -> chain -> apply / as one kernel per matrix [1 from 64 matrices on]
+//   PTMI_QL_SPLIT            1 / 0: ptmi_eig_ql as reduce -> chain -> apply / as one kernel per matrix [1 from 64 matrices on]; beyond
+//                            128 x 128, 0: chain and rows together in the redo kernel, not recorded rotations + apply [1]
 //   PTMI_GJ_SOLO             chains with a wave of their own in the gradient-jump launch order [a 32nd of the chains, at most 1024]
 //   PTMI_GJ_LDS_LEVELS       heights of the NUTS tree stack kept in LDS, the rest in global scratch [11]
 //   PTMI_GJ_NOPAIR           nonzero: diagonal tables at 4 lanes per chain run one chain per wave, not two [0]
@@ -195,6 +196,8 @@ struct ptmi_engine {
     void *d_qlg_scr;             // ptmi_eig_ql with parameter groups: a group's packed matrices, their eigenvectors and eigenvalues
     int32_t *gsize_host;         // [Ng] parameters per group (host copy of d_gsize)
     void *d_ql_scr;              // ptmi_eig_ql with many matrices: the transformations, tridiagonal matrices and recorded rotations (QlScratch)
+    void *d_qlw_scr;             // ... beyond 128 x 128 (ptmi_eig_wide.hip): the same for one batch of matrices, and its size
+    size_t qlw_scr_bytes;
     void *d_rle_ent;             // pooled statistics over run-length-compacted rows: the stored rows of each slab, 16 bytes each [nrows]
                                  // (PoolEnt, ptmi_abi.hip: the row inside its slab, the square root of its run length) ...
     int32_t *d_rle_cnt;          // ... and how many each slab has [nslab]

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ptmi_common.h"
+#include "ptmi_eig_ql.h"
 
 // ---------------------------------------------------------- eigensolver
 // Batched symmetric eigensolver for the per-walker covariances (PT:797-803 calls LAPACK's SVD once per epoch; a batch of
@@ -19,14 +20,6 @@
 constexpr int JAC_THREADS = 512;                            // 8 lanes per row pair, up to 64 pairs (ndim <= 101 uses 51)
 constexpr int JAC_L = 8;
 constexpr int JAC_MAX_SWEEPS = 30;
-// sum over the eight lanes of a pair: xor 4, xor 2, xor 1 (the oracle's ((s0+s4)+(s2+s6)) + ((s1+s5)+(s3+s7)))
-__device__ __forceinline__ double jac_oct_sum(double p)
-{
-    p = p + __shfl_xor(p, 4, 64);
-    p = p + dppf64<0x4E>(p);     // xor 2
-    p = p + dppf64<0xB1>(p);     // xor 1
-    return p;
-}
 __global__ __launch_bounds__(JAC_THREADS) void eig_jacobi_kernel(const double *cov, double *Ut, double *S, int d, int ut_stride, int s_stride)
 {
     extern __shared__ __attribute__((aligned(16))) double jsm[];     // W[d][d], V[d][d]: all of the CU's LDS at d = 101
@@ -122,34 +115,6 @@ __global__ __launch_bounds__(JAC_THREADS) void eig_jacobi_kernel(const double *c
     }
 }
 
-// sqrt(x) and 1 / sqrt(x)'s partner 1 / r of a rotation, for x in the middle of the exponent range: the compiler's own correctly
-// rounded sequences (v_rsq_f64 / v_rcp_f64 + the fma refinements of its sqrt and division lowerings) without their range scaling,
-// special-value tests and fix-ups -- 17 instead of 29 instructions on the chain that bounds eig_ql_chain_kernel, the same bits
-// wherever no scaling would have been applied; anything else takes the plain operations.
-__device__ __forceinline__ void ql_root_and_reciprocal(double x, double &r, double &ri)
-{
-    if (x > 0x1p-600 && x < 0x1p600) {                              // uniform in the chain kernel
-        const double y = __builtin_amdgcn_rsq(x);
-        double g = x * y, hh = 0.5 * y;
-        const double r0 = __builtin_fma(-hh, g, 0.5);
-        g = __builtin_fma(g, r0, g);
-        hh = __builtin_fma(hh, r0, hh);
-        double dd = __builtin_fma(-g, g, x);
-        g = __builtin_fma(dd, hh, g);
-        dd = __builtin_fma(-g, g, x);
-        r = __builtin_fma(dd, hh, g);
-        double q = __builtin_amdgcn_rcp(r);
-        double e = __builtin_fma(-r, q, 1.0);
-        q = __builtin_fma(q, e, q);
-        e = __builtin_fma(-r, q, 1.0);
-        q = __builtin_fma(q, e, q);
-        e = __builtin_fma(-r, q, 1.0);
-        ri = __builtin_fma(e, q, q);
-    } else {
-        r = det_sqrt(x);
-        ri = 1.0 / r;
-    }
-}
 int ptmi_eig_jacobi(ptmi_handle h)
 {
     if (!h) return fail(PTMI_EINVAL, "NULL handle");
@@ -181,7 +146,6 @@ int ptmi_eig_jacobi(ptmi_handle h)
 //  * QL: ONE wave (64 lanes, rows k and k + 64 of the eigenvector matrix each) runs the scalar recurrence in every lane and turns
 //    its rows; nothing is synchronised inside this phase.
 constexpr int QL_THREADS = 128;
-constexpr int QL_MAXIT = 60;
 // the oracle's QL_DOT8: eight interleaved fma chains, term k into chain k mod 8 (a dependent f64 operation costs a lone wave some 20
 // cycles: one chain of 100 terms is 2000 cycles, eight side by side 300)
 template <class FA, class FB>
@@ -397,16 +361,6 @@ __global__ __launch_bounds__(QL_THREADS) void eig_ql_kernel(const double *cov, d
 // eig_ql_apply_kernel then turns the eigenvector rows with them, a thread per row and no scalar work.  Same operations on the
 // same values in the same order as orc_eig_ql: same bits.  A matrix whose rotations do not fit the record (3 n^2; nearly degenerate
 // 100 x 100 spectra take 0.8 n^2) is flagged and redone by the apply kernel with the chain and the rows together.
-typedef double qls_d2 __attribute__((ext_vector_type(2)));
-struct QlScratch {
-    double *z;          // [nmat][n][n]  the accumulated transformations, row-major
-    qls_d2 *de;         // [nmat][n]     {d[i], e[i]} (subdiagonal shifted: e[i] couples i and i + 1)
-    double *ev;         // [nmat][n]     the eigenvalues the chains end with
-    qls_d2 *rot;        // [nmat][cap]   the rotations, in the order they are applied
-    int32_t *hdr;       // [nmat][2 capit]  l, m of every QL iteration
-    int32_t *cnt;       // [nmat][2]     iterations recorded, overflow flag
-    int cap, capit;
-};
 // Reduction and accumulation for the three-kernel form, 256 threads: a dot product is the work of an OCT of lanes -- lane c runs chain
 // c of QL_DOT8 (terms k = c, c + 8, ...), the butterfly xor 4, xor 2, xor 1 is the oracle's ((s0 + s4) + (s2 + s6)) + ((s1 + s5) +
 // (s3 + s7)) in every lane -- 32 products at a time; the rank-two update and the column updates are 16 x 16 tilings of their
@@ -504,97 +458,7 @@ __global__ __launch_bounds__(QLR_THREADS) void eig_ql_reduce_kernel(const double
     for (int i = t; i < n; i += QLR_THREADS) deo[i] = qls_d2{pq[i], i + 1 < n ? e[i + 1] : 0.0};
 }
 
-// the QL iterations on {d, e} pairs in LDS (one wave; every lane runs the scalar recurrence).  ROWS: the lane also turns rows t and
-// t + 64 of zt (the eigenvector matrix TRANSPOSED in LDS: column c at zt[c n ...], so that the lanes' rows sit side by side);
-// else the rotations and the iterations' (l, m) are recorded.  Returns the iterations (negative: an eigenvalue did not converge).
-template <bool ROWS>
-__device__ __forceinline__ int ql_iterate(qls_d2 *de, int n, int t, double *zt, qls_d2 *rot, int32_t *hdr, int cap, int capit, int *overflow)
-{
-    const int k0 = t, k1 = t + 64;
-    const bool r0 = ROWS && k0 < n, r1 = ROWS && k1 < n;
-    int iters = 0, nrot = 0;
-    bool over = false, failed = false;
-    double f = 0.0, tst1 = 0.0;
-    for (int l = 0; l < n && !failed; ++l) {
-        const qls_d2 del = de[l];
-        const double t0 = __builtin_fabs(del.x) + __builtin_fabs(del.y);
-        if (tst1 < t0) tst1 = t0;
-        int m = l;
-        while (m < n - 1 && tst1 + __builtin_fabs(de[m].y) != tst1) ++m;
-        double dlf = del.x;
-        if (m > l) {
-            int it = 0;
-            double el;
-            do {
-                if (++it > QL_MAXIT) { failed = true; break; }
-                if (!ROWS) {
-                    if (iters >= capit || nrot + (m - l) > cap) over = true;
-                    if (!over && t == 0) { hdr[2 * iters] = l; hdr[2 * iters + 1] = m; }
-                }
-                ++iters;
-                const qls_d2 pl = de[l], pl1 = de[l + 1];
-                const double g = pl.x, e_l = pl.y;
-                const double p0 = (pl1.x - g) / (2.0 * e_l);
-                const double rr0 = det_sqrt(p0 * p0 + 1.0);
-                const double pr = p0 + (p0 >= 0.0 ? rr0 : -rr0);
-                const double dl = e_l / pr, dl1 = e_l * pr;
-                const double h = g - dl;
-                const double el1 = pl1.y;
-                double p = de[m].x;
-                asm volatile("" ::: "memory");
-                if (t == 0) { de[l].x = dl; de[l + 1].x = dl1; }
-                for (int i = l + 2 + t; i < n; i += 64) de[i].x = de[i].x - h;
-                asm volatile("" ::: "memory");
-                f = f + h;
-                if (m == l + 1) p = dl1; else if (m >= l + 2) p = p - h;
-                double c = 1.0, c2 = 1.0, c3 = 1.0, s = 0.0, s2 = 0.0;
-                qls_d2 nx = de[m - 1];
-                double zb0 = r0 ? zt[m * n + k0] : 0.0, zb1 = r1 ? zt[m * n + k1] : 0.0;
-                for (int i = m - 1; i >= l; --i) {
-                    c3 = c2; c2 = c; s2 = s;
-                    const double di = nx.x, ei = nx.y;
-                    if (i > l) nx = de[i - 1];
-                    double za0 = 0.0, za1 = 0.0;
-                    if (ROWS) { za0 = r0 ? zt[i * n + k0] : 0.0; za1 = r1 ? zt[i * n + k1] : 0.0; }
-                    const double gg = c * ei, hh = c * p;
-                    double r, ri;
-                    ql_root_and_reciprocal(p * p + ei * ei, r, ri);
-                    const double e1 = s * r;
-                    s = ei * ri;
-                    c = p * ri;
-                    p = c * di - s * gg;
-                    const double d1 = hh + s * (c * gg + s * di);
-                    if (t == 0) de[i + 1] = qls_d2{d1, e1};
-                    if (ROWS) {
-                        if (r0) zt[(i + 1) * n + k0] = s * za0 + c * zb0;
-                        if (r1) zt[(i + 1) * n + k1] = s * za1 + c * zb1;
-                        zb0 = c * za0 - s * zb0;
-                        zb1 = c * za1 - s * zb1;
-                    } else if (!over && t == 0) {
-                        rot[nrot + (m - 1 - i)] = qls_d2{c, s};
-                    }
-                }
-                if (ROWS) {
-                    if (r0) zt[l * n + k0] = zb0;
-                    if (r1) zt[l * n + k1] = zb1;
-                }
-                nrot += m - l;
-                p = -s * s2 * c3 * el1 * e_l / dl1;
-                el = s * p;
-                dlf = c * p;
-                asm volatile("" ::: "memory");
-                if (t == 0) de[l] = qls_d2{dlf, el};
-                asm volatile("" ::: "memory");
-            } while (tst1 + __builtin_fabs(el) != tst1);
-        }
-        asm volatile("" ::: "memory");
-        if (t == 0) de[l] = qls_d2{dlf + f, 0.0};
-        asm volatile("" ::: "memory");
-    }
-    if (overflow) *overflow = over ? 1 : 0;
-    return failed ? -iters - 1 : iters;
-}
-
+// (the QL iterations themselves, ql_iterate, are in ptmi_eig_ql.h: the wide unit's redo runs them on rows in global memory)
 __global__ __launch_bounds__(64) void eig_ql_chain_kernel(int n, QlScratch q)
 {
     extern __shared__ __attribute__((aligned(16))) double qsm[];
@@ -805,6 +669,11 @@ __global__ __launch_bounds__(128, 2) void eig_ql_apply_reg_kernel(double *Ut, do
     }
 }
 
+void eig_ql_chain_launch(hipStream_t stream, int n, int nmat, const QlScratch &q)
+{
+    hipLaunchKernelGGL(eig_ql_chain_kernel, dim3(nmat), dim3(64), sizeof(double) * 2 * (size_t)n, stream, n, q);
+}
+
 // (the kernels from here to the divide-and-conquer solver's have C names)
 extern "C" {
 
@@ -812,9 +681,10 @@ extern "C" {
 static int eig_ql_run(ptmi_engine *h, int n, int nmat, const double *cov, double *Ut, double *S)
 {
     const ptmi_config &c = h->cfg;
-    const int d = n, dmax = c.ndim;
+    const int d = n, dmax = c.ndim < 128 ? c.ndim : 128;               // (the scratch below: a matrix beyond 128 goes to the wide kernels)
+    if (d > 1024) return fail(PTMI_EUNSUPPORTED, "the QL eigensolver factorizes matrices up to 1024 x 1024 (this one: %d x %d)", d, d);
+    if (d > 128) return eig_ql_wide_run(h, d, nmat, cov, Ut, S);     // the matrix in a global scratch (ptmi_eig_wide.hip)
     const size_t lds = sizeof(double) * ((((size_t)d * d + 1) & ~(size_t)1) + 2 * (size_t)d);
-    if (lds > 160 * 1024 || d > 128) return fail(PTMI_EUNSUPPORTED, "the QL eigensolver keeps the %d x %d matrix in LDS: ndim <= 128", d, d);
     const bool split = ptmi_env("PTMI_QL_SPLIT", nmat >= 64) != 0;    // 1 / 0 forces the three-kernel / the one-kernel form (a test hook)
     if (split) {
         // many matrices: reduce -> the scalar chains of all of them at once -> apply (see eig_ql_chain_kernel)
@@ -840,7 +710,7 @@ static int eig_ql_run(ptmi_engine *h, int n, int nmat, const double *cov, double
             HIPCHK(hipFuncSetAttribute((const void *)eig_ql_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
         hipLaunchKernelGGL(eig_ql_reduce_kernel, dim3(nmat), dim3(QLR_THREADS), lds, h->stream, cov, d, q);
-        hipLaunchKernelGGL(eig_ql_chain_kernel, dim3(nmat), dim3(64), sizeof(double) * 2 * (size_t)d, h->stream, d, q);
+        eig_ql_chain_launch(h->stream, d, nmat, q);
         const bool regs = d <= QLA_N;
         if (regs)
             hipLaunchKernelGGL(eig_ql_apply_reg_kernel, dim3(nmat), dim3(128), 0, h->stream, Ut, S, d, d * d, d, (const double *)q.z,
@@ -859,11 +729,11 @@ static int eig_ql_run(ptmi_engine *h, int n, int nmat, const double *cov, double
 // parameter order, packed into an m x m matrix per walker ...
 __global__ __launch_bounds__(256) void group_gather_kernel(const double *cov, const double *gmask, int d, int m, double *sub)
 {
-    __shared__ int idx[128];
+    __shared__ int idx[1024];
     const double *mk = gmask;                                            // [d] membership of this group
     if (threadIdx.x == 0) {
         int k = 0;
-        for (int i = 0; i < d && k < 128; ++i) if (mk[i] != 0.0) idx[k++] = i;
+        for (int i = 0; i < d && k < 1024; ++i) if (mk[i] != 0.0) idx[k++] = i;
     }
     __syncthreads();
     const double *cw = cov + (size_t)blockIdx.x * d * d;
@@ -875,7 +745,7 @@ __global__ __launch_bounds__(256) void group_gather_kernel(const double *cov, co
 __global__ __launch_bounds__(256) void group_embed_kernel(const double *usub, const double *ssub, const double *gmask, int d, int m, int ng, int gi,
                                                           double *Ut, double *S)
 {
-    __shared__ int pos[128];                                             // position of parameter i inside the group, or -1
+    __shared__ int pos[1024];                                            // position of parameter i inside the group, or -1
     if (threadIdx.x == 0) {
         int k = 0;
         for (int i = 0; i < d; ++i) pos[i] = gmask[i] != 0.0 ? k++ : -1;
@@ -897,7 +767,7 @@ int ptmi_eig_ql(ptmi_handle h)
     if (!h->buf.cov || !h->buf.Ut || !h->buf.S) return fail(PTMI_EINVAL, "cov / Ut / S buffers missing");
     const int d = c.ndim, nmat = c.cov_per_walker ? c.nwalkers : 1;
     if (c.ngroups <= 1) return eig_ql_run(h, d, nmat, (const double *)h->buf.cov, h->buf.Ut, h->buf.S);
-    if (d > 128) return fail(PTMI_EUNSUPPORTED, "the QL eigensolver keeps a matrix in LDS: ndim <= 128");
+    if (d > 1024) return fail(PTMI_EUNSUPPORTED, "the QL eigensolver with parameter groups: ndim <= 1024 (got %d)", d);
     // one factorization per parameter group, as the reference's loop over self.groups (PT:797-803)
     if (!h->d_qlg_scr) HIPCHK(hipMalloc((void **)&h->d_qlg_scr, sizeof(double) * (size_t)nmat * (2 * (size_t)d * d + d)));
     double *sub = (double *)h->d_qlg_scr, *usub = sub + (size_t)nmat * d * d, *ssub = usub + (size_t)nmat * d * d;
@@ -928,6 +798,8 @@ int ptmi_eig_ql_from(ptmi_handle h, void *stream, const double *cov_in, double *
     if (stream) view.stream = (hipStream_t)stream;
     const int rc = eig_ql_run(&view, c.ndim, c.cov_per_walker ? c.nwalkers : 1, cov, Uo, So);
     h->d_ql_scr = view.d_ql_scr;                                         // (made by the first call)
+    h->d_qlw_scr = view.d_qlw_scr;
+    h->qlw_scr_bytes = view.qlw_scr_bytes;
     return rc;
 }
 

@@ -132,8 +132,9 @@ class PTEngine(object):
     ``eig_mode``: who factorizes the adapted covariance at a covariance epoch (PTMCMCSampler.py:797-803): ``"lapack"`` = the
     host, exactly as the reference (``np.linalg.svd`` per walker); ``"jacobi"`` = ``ptmi_eig_jacobi`` on the device, one
     block per walker, no host round trip (ndim <= 101, one parameter group; same subspaces, its own sign rule); ``"ql"`` =
-    ``ptmi_eig_ql``, Householder tridiagonalization + implicit QL on the device (ndim <= 128; a quarter of the Jacobi kernel's time
-    on nearly degenerate spectra, two matrices per CU: the choice for thousands of per-walker covariances);
+    ``ptmi_eig_ql``, Householder tridiagonalization + implicit QL on the device (ndim <= 1024, parameter groups included; up to 128 x 128 the
+    matrix lives in LDS -- a quarter of the Jacobi kernel's time on nearly degenerate spectra, two matrices per CU -- beyond that in a
+    global scratch, factorized in batches: the choice for thousands of per-walker covariances, the oracle's bits at every size);
     ``"hipsolver"`` = the ROCm library's symmetric eigensolver on the engine's stream (``torch.linalg.eigh`` on the device
     tensor: no host round trip either; with parameter groups one call per group's block) -- the choice for large ndim, where the host's LAPACK call is the
     epoch (1000 x 1000: 22 ms against 83 ms on 8 host threads; at ndim = 100 the host's 0.6 ms wins).  Like LAPACK's, its
