@@ -565,6 +565,34 @@ int ptmi_sup_begin(ptmi_handle h, void *work, const double *lp /* dev [n_in] */,
 int ptmi_sup_rows(ptmi_handle h, void *work, const double *rows_in /* dev [n_in][ndim] */, double *rows /* dev [n][ndim] */);
 int ptmi_sup_end(ptmi_handle h, void *work, const double *vals /* dev [n] or NULL */, double *out /* dev [n_in] */);
 
+/* Marginal posterior histograms of EVERY cold chain, accumulated on the device (csrc/ptmi_hist.hip).  The AM ring holds the rank-0 row
+ * of every walker for every iteration of the current covariance period (updateChains, :327-328: the post-swap row at swap iterations,
+ * the repeated row behind a rejection); these calls bin every element of it.  For parameter j the caller fixes lo[j] < hi[j], nbins
+ * and scale[j] = nbins / (hi[j] - lo[j]) in double precision; an element x that stands for n iterations is counted as
+ *
+ *     t = (x - lo[j]) * scale[j]              one subtraction, one multiplication, no fma
+ *     if not (t >= 0.0):  under[j] += n       x < lo, and NaN
+ *     elif t >= nbins:    over[j]  += n       x >= hi (as scale rounds), +inf
+ *     else:               counts[j][(int)t] += n
+ *
+ * counts: DEVICE uint64 [ndim][nbins + 2] in PARAMETER order whatever the ring's row format (ptmi_am_row_format): columns
+ * 0 .. nbins - 1 the bins, column nbins = under, column nbins + 1 = over; caller-owned, zeroed by the caller, 8-byte aligned.
+ * ptmi_hist_attach (once per handle) takes it with lo / scale (HOST [ndim]; lo finite, scale finite and positive; the library keeps
+ * device copies) and 2 <= nbins <= 1024; anything else: PTMI_EINVAL.  State lives in the handle: ptmi_config and ptmi_buffers are
+ * unchanged, and a handle that never attaches launches what it launched before.
+ * ptmi_hist_update adds iterations iter_lo .. iter_hi of every walker from the handle's CURRENT ring (ptmi_set_am_buffers): both in one
+ * covariance period, E < iter_lo <= iter_hi <= E + cov_update with E = ((iter_hi - 1) / cov_update) * cov_update (PTMI_EINVAL for a
+ * range that crosses a period, and before ptmi_hist_attach; the message says which); iter_hi < iter_lo: nothing to do.  Without AMflag
+ * every row counts once; with it a row without NEW / KEY repeats the last stored row before it (ptmi_am_expand's rule; ring row 1 of
+ * a period is a KEY row, so the walk back never leaves the period): every stored row is read once and carries the length of its run
+ * clipped to [iter_lo, iter_hi].  The caller counts every iteration once (ranges that do not overlap) and calls before the ring
+ * wraps; the ring is only read.  On a handle with temp0 != 0: PTMI_OK, nothing done (as ptmi_update_cov).  Rings of 2^32 rows or more:
+ * PTMI_EUNSUPPORTED.  Asynchronous on the handle's stream, no host synchronisation; no atomics per element (a block adds its private
+ * tile to counts once). */
+int ptmi_hist_attach(ptmi_handle h, uint64_t *counts /* dev [ndim][nbins+2], caller-owned, caller-zeroed */,
+                     const double *lo /* host [ndim] */, const double *scale /* host [ndim] */, int32_t nbins);
+int ptmi_hist_update(ptmi_handle h, int64_t iter_lo, int64_t iter_hi);
+
 /* Self-test hooks used by the parity tests: evaluate the device's deterministic math on
  * n inputs (op: 0 log, 1 exp, 2 cos2pi, 3 sqrt, 4 reciprocal-free divide a/b with b=in2). */
 int ptmi_selftest_math(int device, int op, const double *in, const double *in2, double *out, int64_t n);

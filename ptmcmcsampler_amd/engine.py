@@ -63,6 +63,41 @@ def factorize(cov, per_walker):
 
 
 
+def hist_spec(ndim, hist):
+    """``hist=(lo, hi, nbins)`` of ``PTEngine.with_stages`` -> (lo [ndim], hi [ndim], nbins), checked: scalars or [ndim], lo < hi and
+    finite, 2 <= nbins <= 1024 (``ptmi_hist_attach``)."""
+    try:
+        lo, hi, nbins = hist
+    except (TypeError, ValueError):
+        raise ValueError("hist=(lo, hi, nbins)") from None
+    if int(nbins) != nbins or not 2 <= int(nbins) <= 1024:
+        raise ValueError("hist: 2 <= nbins <= 1024 (got %r)" % (nbins,))
+    out = []
+    for name, v in (("lo", lo), ("hi", hi)):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim == 0:
+            v = np.full(ndim, float(v))
+        if v.shape != (ndim,):
+            raise ValueError("hist: %s is a scalar or has ndim = %d entries (got shape %r)" % (name, ndim, v.shape))
+        out.append(np.ascontiguousarray(v))
+    lo, hi = out
+    bad = ~(np.isfinite(lo) & np.isfinite(hi) & (lo < hi))
+    scale = int(nbins) / np.where(bad, 1.0, hi - lo)
+    bad |= ~np.isfinite(scale)
+    if bad.any():
+        j = int(np.flatnonzero(bad)[0])
+        raise ValueError("hist: lo < hi, both finite (parameter %d: lo = %r, hi = %r)" % (j, lo[j], hi[j]))
+    return lo, hi, int(nbins)
+
+
+def hist_edges(lo, hi, nbins):
+    """The bin edges lo + k (hi - lo) / nbins, [d][nbins + 1]; the last one is hi itself."""
+    k = np.arange(nbins + 1, dtype=np.float64)
+    e = lo[:, None] + k[None, :] * ((hi - lo) / nbins)[:, None]
+    e[:, nbins] = hi
+    return e
+
+
 def interval_par(a, b, d):
     """Parameters of the ("interval", a, b) family (include/ptmi.h PTMI_LOGL_INTERVAL): a, w = b - a, log w."""
     a = np.broadcast_to(np.asarray(a, np.float64), (d,))
@@ -191,6 +226,12 @@ class PTEngine(object):
     (a Cholesky factorization, a logarithm of a parameter) and for expensive ones under a tight prior; the chains are the same bit for
     bit for a row-wise callback.  The gradient callbacks are not filtered (the reference's are not either, nutsjump.py:71-76).  With a flat
     prior (``logp=None``) the stage launches nothing.  Not in graph mode.  ``support_counts``: (rows offered, rows handed to ``logl``).
+    ``with_stages(..., hist=(lo, hi, nbins), hist_from=None)``: the marginal posterior histograms of EVERY walker's cold chain, accumulated
+    on the device from the AM ring (include/ptmi.h ``ptmi_hist_*``: ``t = (x - lo) * (nbins / (hi - lo))``, below 0 and NaN -> ``under``, at
+    or above ``nbins`` -> ``over``, else bin ``int(t)``).  ``lo`` / ``hi``: scalars or ``[ndim]``; iterations ``hist_from + 1`` on are counted
+    (default ``hist_from = burn``).  ``update_cov`` counts the period that ends before it touches anything else, so every way of running
+    the engine is served; ``hist_sync(it)`` counts up to an iteration inside a period, ``hist_counts(it=None)`` returns the result.  The
+    ring is only read: the chains are the same bits with and without.  ``t["hist"]`` and ``hist_iter`` are part of ``checkpoint()``.
     ``stats_async`` (pooled covariance with ``eig_lag >= 1``): the statistics of a covariance period that is over need nothing the next
     launches touch once those write ANOTHER ring -- so the engine keeps two rings (``t["AM"]`` is always the one in use), switches at
     every covariance epoch, and runs the period's statistics (``ptmi_update_cov_on``) and the factorization behind them on a side
@@ -203,17 +244,21 @@ class PTEngine(object):
     jumps_with_grad = False
     _aux = ()
     logl_in_support = False
+    _hist = None
+    _hist_from = None
 
     @classmethod
-    def with_stages(cls, *args, jumps_with_grad=False, aux=None, logl_in_support=False, **kw):
+    def with_stages(cls, *args, jumps_with_grad=False, aux=None, logl_in_support=False, hist=None, hist_from=None, **kw):
         """``PTEngine(*args, **kw)`` with the stages of the composed ``_jump`` on the callback path (see the class docstring):
         ``jumps_with_grad=True`` lets ``jumps=`` stand beside ``grad_weights`` in one cycle, ``aux=[func, ...]`` are the auxiliary jumps,
-        ``logl_in_support=True`` hands the likelihood callback only the rows whose prior is not -inf (``eval_callback``).
+        ``logl_in_support=True`` hands the likelihood callback only the rows whose prior is not -inf (``eval_callback``),
+        ``hist=(lo, hi, nbins)`` with ``hist_from`` accumulates the marginal histograms of every cold chain (``hist_counts``).
         The plain constructor keeps the parameters it had (tests/test_gj_groups.py holds them to the letter) and its refusals."""
         self = cls.__new__(cls)
         self.jumps_with_grad = bool(jumps_with_grad)
         self._aux = list(aux) if aux is not None else []
         self.logl_in_support = bool(logl_in_support)
+        self._hist, self._hist_from = hist, hist_from
         self.__init__(*args, **kw)
         return self
 
@@ -263,6 +308,16 @@ class PTEngine(object):
         if self.logl_in_support and not (split or rows_logl):
             raise ValueError("logl_in_support=True is a stage of the callback path: split=True (or rows_logl=True); the fused kernels "
                              "have no likelihood callback to spare")
+        # posterior histograms of the cold chains (with_stages(hist=(lo, hi, nbins), hist_from=...); see the class docstring)
+        self.hist_spec = None
+        if self._hist is not None:
+            self.hist_spec = hist_spec(int(ndim), self._hist)
+            self.hist_from = int(burn) if self._hist_from is None else int(self._hist_from)
+            if self.hist_from < 0:
+                raise ValueError("hist_from = %d: the first iteration counted is hist_from + 1 >= 1" % self.hist_from)
+            self.hist_iter = self.hist_from
+        elif self._hist_from is not None:
+            raise ValueError("hist_from= goes with hist=(lo, hi, nbins)")
         # rows_logl: the built-in likelihood as a row kernel on the split path (see the class docstring); refused before anything is built
         self.rows_logl = bool(rows_logl)
         if self.rows_logl:
@@ -439,6 +494,13 @@ class PTEngine(object):
                     f.bind(self)
         if self._aux:
             _lib.check(self.lib.ptmi_aux_attach(self.h))
+        if self.hist_spec is not None:
+            # uint64 [d][nbins + 2] (bins, under, over) in parameter order; in self.t: checkpoints carry it by itself
+            lo, hi, nbins = self.hist_spec
+            self.t["hist"] = z((d, nbins + 2), i64)
+            self._hist_scale = nbins / (hi - lo)
+            _lib.check(self.lib.ptmi_hist_attach(self.h, C.c_void_p(self.t["hist"].data_ptr()), lo.ctypes.data_as(_lib._dp),
+                                                 self._hist_scale.ctypes.data_as(_lib._dp), nbins))
         self.de_on = False
         self.de_head = 0
         self.iter = 0
@@ -774,6 +836,8 @@ class PTEngine(object):
         """Covariance epoch after iteration ``it_done`` (:545-560): device Welford, host SVD."""
         if not self.owns_cold:
             return
+        if self.hist_spec is not None:
+            self._hist_sync(it_done)                                  # before the statistics, and before stats_async switches rings
         # A factorization still pending from the epoch before (eig_lag >= the launches of a period) is finished here at the latest.
         # On the side stream (device factorizations) it goes on BESIDE this epoch's statistics, which do not read the table: they are
         # queued first, the wait for the old table comes behind them -- the same table in force for the same launches either way.
@@ -852,6 +916,39 @@ class PTEngine(object):
             self._eig_begin(self._st)
         self._eig_wait = self.eig_lag
 
+    # ------------------------------------------------------------------ posterior histograms
+    def hist_sync(self, it):
+        """Count iterations ``(hist_iter, it]`` of every walker's cold chain into ``t["hist"]`` (``ptmi_hist_update``: asynchronous, the
+        ring is only read).  ``it`` lies in the covariance period the ring holds; ``update_cov`` calls this at every period's end, so
+        a caller only needs it for counts up to an iteration inside a period.  Nothing to do up to ``hist_from``."""
+        if self.hist_spec is None:
+            raise ValueError("no histogram: PTEngine.with_stages(..., hist=(lo, hi, nbins))")
+        if int(it) > self.iter:
+            raise ValueError("hist_sync(%d): the engine has reached iteration %d; the ring's rows beyond it are the period before's" % (int(it), self.iter))
+        self._hist_sync(it)
+
+    def _hist_sync(self, it):
+        it = int(it)
+        if it <= self.hist_iter:
+            return
+        base = ((it - 1) // self.cov_update) * self.cov_update
+        if self.hist_iter < base and self.owns_cold:
+            raise ValueError("hist_sync(%d): iterations %d..%d are no longer in the ring (it holds the period after %d); every period "
+                             "must end through update_cov" % (it, self.hist_iter + 1, base, base))
+        _lib.check(self.lib.ptmi_hist_update(self.h, self.hist_iter + 1, it))
+        self.hist_iter = it
+
+    def hist_counts(self, it=None):
+        """The histograms up to iteration ``it`` (default: the current one): a dict of ``counts`` uint64 [d][nbins], ``under`` / ``over``
+        [d] (below ``lo`` and NaN / at or above ``hi``), ``edges`` [d][nbins + 1], ``first_iter`` / ``last_iter`` (the iterations counted,
+        of every one of ``nwalkers`` cold chains)."""
+        self.hist_sync(self.iter if it is None else it)
+        lo, hi, nbins = self.hist_spec
+        a = self.t["hist"].cpu().numpy().view(np.uint64)
+        return dict(counts=np.ascontiguousarray(a[:, :nbins]), under=a[:, nbins].copy(), over=a[:, nbins + 1].copy(),
+                    edges=hist_edges(lo, hi, nbins), first_iter=np.int64(self.hist_from + 1), last_iter=np.int64(self.hist_iter),
+                    nwalkers=np.int64(self.W))
+
     def update_de(self, it_done=None):
         if self.owns_cold and self.t["DE"] is not None:
             if it_done is not None:
@@ -877,12 +974,16 @@ class PTEngine(object):
                   eig_epochs=self.eig_epochs,
                   # eig_lag: an epoch's table that is not in force yet (its covariance is in t_cov; restore() factorizes it again)
                   eig_pending=int(self._eig_pending), eig_wait=int(self._eig_wait))
+        if self.hist_spec is not None:
+            st["hist_iter"] = self.hist_iter
         if self.stats_async:
             st.update({"alt_" + k: v.cpu().numpy() for k, v in self._alt.items() if v is not None})
         return st
 
     def restore(self, st):
         torch = _torch()
+        if self.hist_spec is not None and ("hist_iter" not in st or "t_hist" not in st):      # refused before anything is touched
+            raise ValueError("the checkpoint carries no histogram: it was written by a run without hist=")
         # whatever this engine has under way is void -- and is brought to an end FIRST: a factorization on the side stream (its thread
         # joined, its result dropped), statistics still running beside the launches (stats_async: they write cov / mu / M2)
         if self._eig_pending:
@@ -906,6 +1007,8 @@ class PTEngine(object):
                     v.copy_(torch.from_numpy(np.ascontiguousarray(st["alt_" + k])).to(v.dtype))
         self.iter, self.swap_proposed = int(st["iter"]), int(st["swap_proposed"])
         self.eig_epochs = int(st["eig_epochs"])                       # (behind _eig_finish, which counts the dropped table)
+        if self.hist_spec is not None:
+            self.hist_iter = int(st["hist_iter"])
         if self.t["DE"] is not None:
             self.set_de_head(int(st["de_head"]))
             if int(st["de_on"]):

@@ -30,6 +30,11 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
   (``PTEngine.aux_stage``) -- opt-in: every iteration then gathers the chains' states.  ``sampler.logl_in_support = True`` (before
   ``sample()``; also with a device likelihood and ``rows_logl=True``): ``logl`` gets only the rows whose prior is not -inf, the reference's
   rule (PTMCMCSampler.py:605-612) -- for likelihoods undefined outside the support; opt-in: one more host read-back per iteration;
+* ``sampler.posterior_hist = (lo, hi, nbins)`` (before ``sample()``; any likelihood, any path): the marginal posterior histograms of
+  EVERY walker's cold chain after ``burn`` -- not only of the ``keep_walkers`` whose samples are written -- accumulated on the device
+  from the AM ring (``PTEngine.with_stages(hist=...)``): ``<outDir>/hist.npz`` (``counts``, ``under``, ``over``, ``edges``, ``first_iter``,
+  ``last_iter``, ``nwalkers``) at every save, ``sampler.hist`` after the run; ``checkpoint=True`` runs resume the counts, a replay of
+  chain files cannot;
 * engine options: ``cov_mode="pooled"`` (one covariance adapted from all walkers instead of one per walker),
   ``swap_mode="oddeven"`` (disjoint swap pairs instead of the reference's hot -> cold sweep), ``pick_mode="walker"`` (one
   proposal-type draw per walker and iteration), ``eig_mode="ql"`` / ``"jacobi"`` / ``"sytrd"`` / ``"hipsolver"`` (covariance epochs factorized on the device: per-walker matrices by
@@ -133,6 +138,11 @@ class PTSampler(object):
     # the likelihood is called only on the rows inside the prior's support, as the reference calls it (PTMCMCSampler.py:605-612;
     # PTEngine.with_stages(logl_in_support=True)).  An attribute for the same reason as batched_aux
     logl_in_support = False
+    # s.posterior_hist = (lo, hi, nbins) (before sample()): the marginal posterior histograms of EVERY walker's cold chain after burn,
+    # accumulated on the device (PTEngine.with_stages(hist=...)): <outDir>/hist.npz at every save, s.hist after the run.  lo / hi:
+    # scalars or [ndim].  An attribute for the same reason as batched_aux
+    posterior_hist = None
+    hist = None
 
     def __init__(self, ndim, logl, logp, cov, groups=None, loglargs=[], loglkwargs={}, logpargs=[], logpkwargs={},
                  logl_grad=None, logp_grad=None, comm=None, outDir="./chains", verbose=True, resume=False, seed=None,
@@ -366,6 +376,10 @@ class PTSampler(object):
         if self._resuming or self._replaying:
             if self.verbose:
                 print("Resuming run from chain file {0}".format(self.fname))
+        if self._replaying and self.posterior_hist is not None:
+            raise NotImplementedError("posterior_hist counts every walker's cold chain on the device; chain files hold the kept walkers' "
+                                      "thinned rows only, so a replayed run cannot continue the counts: resume from a device checkpoint "
+                                      "(PTSampler(..., checkpoint=True) from the first run on)")
         if self._replaying:
             # PTMCMCSampler.py:290-313: the text rows are all there is (chains the reference wrote, or a run of ours without
             # checkpoints).  In the reference every MPI rank replays its own chain_<T>.txt; here the one process replays
@@ -465,7 +479,7 @@ class PTSampler(object):
             split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
             jumps=[(f, n) for f, n in stage_list] if stage_list else None,
             jumps_with_grad=bool(stage_list) and sum(self._grad_weights) > 0, aux=list(self._batched_aux) or None,
-            logl_in_support=bool(self.logl_in_support),
+            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist,
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     # ------------------------------------------------------------------ sample (:374-528)
@@ -617,7 +631,10 @@ class PTSampler(object):
                                   # (batched auxiliary jumps by name, only where there are some: the other runs' fingerprints stay what they were)
                                   + ((("aux",) + tuple(getattr(f, "__name__", "?") for f in self._batched_aux),) if self._batched_aux else ())),
                            digest((self.cov_mode, self.swap_mode, self.pick_mode, self.eig_mode, self.nuts_maxdepth, bool(self.split), bool(self.batched),
-                                   bool(eng.am_rle)), *groups),
+                                   bool(eng.am_rle))
+                                  # (the histogram's bins, only where there are some: the other runs' fingerprints stay what they were)
+                                  + ((("hist", eng.hist_from, eng.hist_spec[2]),) if eng.hist_spec is not None else ()), *groups,
+                                  *(eng.hist_spec[:2] if eng.hist_spec is not None else ())),
                            digest(*(spec(self.logl_spec) + spec(self.logp_spec)))], dtype=np.int64)
 
     def _load_checkpoint(self):
@@ -922,7 +939,19 @@ class PTSampler(object):
                 self.jumpDict[name][1] += int(dec[s0, 2] > 0.5)
 
     # ------------------------------------------------------------------ output files (:341-372, :722-766)
+    def _write_hist(self, iter):
+        """The histograms up to iteration ``iter`` (of the current covariance period) -> self.hist and <outDir>/hist.npz."""
+        self.engine.iter = max(self.engine.iter, int(iter))          # (the sampler's loops step the engine themselves)
+        self.hist = self.engine.hist_counts(iter)
+        tmp = os.path.join(self.outDir, "hist.tmp.npz")
+        np.savez(tmp, **self.hist)
+        os.replace(tmp, os.path.join(self.outDir, "hist.npz"))
+
     def writeOutput(self, iter):
+        if self.posterior_hist is not None and self.engine.hist_spec is None:
+            raise ValueError("posterior_hist was set after the engine was built: set it before the first sample()")
+        if self.engine.hist_spec is not None and iter > 0:
+            self._write_hist(iter)                                    # ahead of the checkpoint: it carries the counts up to here
         if iter // self.thin >= self.ind_next_write:
             self._counters()
             self._writeToFile(iter)
