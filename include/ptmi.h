@@ -593,6 +593,34 @@ int ptmi_hist_attach(ptmi_handle h, uint64_t *counts /* dev [ndim][nbins+2], cal
                      const double *lo /* host [ndim] */, const double *scale /* host [ndim] */, int32_t nbins);
 int ptmi_hist_update(ptmi_handle h, int64_t iter_lo, int64_t iter_hi);
 
+/* The ladder's summaries for the log-evidence, accumulated on the device (csrc/ptmi_ev.hip): per walker and LOCAL RANK r the moments
+ * of lnL that thermodynamic integration needs and the running log-sum-exp of dbeta[r] * lnL that the stepping-stone estimator needs.
+ * Every call of ptmi_ev_update takes one sample of every cell (w, r) from the handle's state as it stands:
+ *
+ *     l = lnL[w][slot_of[w][r]];   a = dbeta[r] * l
+ *     !isfinite(l)            -> skipped += 1, nothing else
+ *     first sample of a cell  -> c = l; s1 = 0; s2 = 0; m = a; es = 1
+ *     else                    -> t = l - c; s1 += t; s2 += t * t
+ *                                a <= m: es += exp(a - m)        else: es = es * exp(m - a) + 1; m = a
+ *     taken += 1
+ *
+ * every operation rounded on its own (no fma), exp the library's deterministic exponential (ptmi_selftest_math op 1).  So after n
+ * samples mean lnL = c + s1 / n, sum (lnL - c)^2 = s2, and sum exp(dbeta[r] lnL) = exp(m) * es.  The caller decides WHEN to sample:
+ * behind ptmi_swap the state is the post-swap one of that iteration, the row the reference's chain files hold for it.
+ * acc: DEVICE double [5][W][T], planes c, s1, s2, m, es; cnt: DEVICE uint64 [2][W][T], planes taken, skipped; both plane-major and
+ * indexed by local rank (not by slot), caller-owned, zeroed by the caller, 8-byte aligned.  dbeta: HOST [T] (the library keeps a
+ * device copy), dbeta[r] = beta of the next colder rank - beta of rank r for r >= 1, computed by the caller in double precision from
+ * temps_mh (beta = 1 / T); dbeta[0] is the caller's too: 0 where rank 0 is the coldest of the whole ladder, the gap to the
+ * neighbouring block's hottest rank on a sharded ladder.  Every entry finite and >= 0.  ptmi_ev_attach: once per handle; a second
+ * attach, NULL or misaligned buffers, a bad dbeta: PTMI_EINVAL, the message says which.  State lives in the handle: ptmi_config and
+ * ptmi_buffers are unchanged, and a handle that never attaches launches what it launched before.
+ * ptmi_ev_update (PTMI_EINVAL before ptmi_ev_attach): one thread per cell on the handle's stream, no host synchronisation, no atomics,
+ * graph-capturable; it reads slot_of and lnL and touches nothing else of the handle.  Every cell is a sequential recurrence in time:
+ * the result does not depend on the launch geometry. */
+int ptmi_ev_attach(ptmi_handle h, double *acc /* dev [5][W][T] */, uint64_t *cnt /* dev [2][W][T] */,
+                   const double *dbeta /* host [T] */);
+int ptmi_ev_update(ptmi_handle h);
+
 /* Self-test hooks used by the parity tests: evaluate the device's deterministic math on
  * n inputs (op: 0 log, 1 exp, 2 cos2pi, 3 sqrt, 4 reciprocal-free divide a/b with b=in2). */
 int ptmi_selftest_math(int device, int op, const double *in, const double *in2, double *out, int64_t n);

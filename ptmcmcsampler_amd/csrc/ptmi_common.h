@@ -235,6 +235,8 @@ struct ptmi_engine {
     long long *h_sup_n;
     // posterior histograms of the cold chains (ptmi_hist.hip): the state of ptmi_hist_attach, or nullptr
     struct ptmi_hist_state *hist;
+    // the ladder's summaries for the log-evidence (ptmi_ev.hip): the state of ptmi_ev_attach, or nullptr
+    struct ptmi_ev_state *ev;
 };
 enum { PTMI_GJ_NONE = 0, PTMI_GJ_PENDING = 1 /* proposals made, ptmi_gj_begin not yet called */, PTMI_GJ_ROUNDS = 2, PTMI_GJ_DONE = 3 };
 // the split path's refusals for gradient jumps (0: served; else the code, with the message set)
@@ -246,6 +248,8 @@ hipError_t ptmi_am_scratch_alloc(ptmi_engine *h, bool am_main);
 void ptmi_dc_plan_free(ptmi_engine *h);
 // posterior histograms (ptmi_hist.hip): frees h->hist, for ptmi_destroy
 void ptmi_hist_free(ptmi_engine *h);
+// log-evidence summaries (ptmi_ev.hip): frees h->ev, for ptmi_destroy
+void ptmi_ev_free(ptmi_engine *h);
 // swap (ptmi_swap.hip): bytes of a record of d_pre (SwapPre), for ptmi_create
 constexpr size_t PTMI_SWAP_PRE_BYTES = 48;
 

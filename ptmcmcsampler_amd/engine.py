@@ -232,6 +232,16 @@ class PTEngine(object):
     (default ``hist_from = burn``).  ``update_cov`` counts the period that ends before it touches anything else, so every way of running
     the engine is served; ``hist_sync(it)`` counts up to an iteration inside a period, ``hist_counts(it=None)`` returns the result.  The
     ring is only read: the chains are the same bits with and without.  ``t["hist"]`` and ``hist_iter`` are part of ``checkpoint()``.
+    ``with_stages(..., evidence=True, evidence_from=None, evidence_every=1)``: the ladder's summaries for the log-evidence ln Z (include/ptmi.h
+    ``ptmi_ev_*``, evidence.py): per walker and rank the count, mean and variance of lnL (shifted sums) and the running log-sum-exp of
+    ``dbeta_r * lnL``, ``dbeta_r = beta_{r-1} - beta_r`` from ``temps_mh`` (``hot_chain=True``: beta = 1e-80 at the last rank, the last
+    stone reaches the prior).  ``swap(it)`` -- the one call every path swaps through -- takes a sample behind the swap when
+    ``it > evidence_from`` (default ``burn``) and ``(it // tskip) % evidence_every == 0``: the POST-swap state of a swap iteration, the row
+    the reference's chain files hold for it.  The sampling period is ``tskip * evidence_every`` iterations; with autocorrelation times
+    in the hundreds of iterations (tau about 600 at 100-d) a sample every ``tskip`` iterations loses next to nothing
+    against one per iteration.  ``evidence_moments()`` returns the accumulators, ``evidence()`` the estimates (thermodynamic integration,
+    its second-order correction, stepping stones; per walker and with standard errors from the walkers' scatter).  lnL is only read:
+    the chains are the same bits with and without.  ``t["ev_acc"]``, ``t["ev_cnt"]`` and ``ev_epochs`` are part of ``checkpoint()``.
     ``stats_async`` (pooled covariance with ``eig_lag >= 1``): the statistics of a covariance period that is over need nothing the next
     launches touch once those write ANOTHER ring -- so the engine keeps two rings (``t["AM"]`` is always the one in use), switches at
     every covariance epoch, and runs the period's statistics (``ptmi_update_cov_on``) and the factorization behind them on a side
@@ -246,19 +256,25 @@ class PTEngine(object):
     logl_in_support = False
     _hist = None
     _hist_from = None
+    _ev = False
+    _ev_from = None
+    _ev_every = 1
 
     @classmethod
-    def with_stages(cls, *args, jumps_with_grad=False, aux=None, logl_in_support=False, hist=None, hist_from=None, **kw):
+    def with_stages(cls, *args, jumps_with_grad=False, aux=None, logl_in_support=False, hist=None, hist_from=None,
+                    evidence=False, evidence_from=None, evidence_every=1, **kw):
         """``PTEngine(*args, **kw)`` with the stages of the composed ``_jump`` on the callback path (see the class docstring):
         ``jumps_with_grad=True`` lets ``jumps=`` stand beside ``grad_weights`` in one cycle, ``aux=[func, ...]`` are the auxiliary jumps,
         ``logl_in_support=True`` hands the likelihood callback only the rows whose prior is not -inf (``eval_callback``),
-        ``hist=(lo, hi, nbins)`` with ``hist_from`` accumulates the marginal histograms of every cold chain (``hist_counts``).
+        ``hist=(lo, hi, nbins)`` with ``hist_from`` accumulates the marginal histograms of every cold chain (``hist_counts``),
+        ``evidence=True`` with ``evidence_from`` / ``evidence_every`` (default 1) the ladder's lnL summaries for ln Z (``evidence``).
         The plain constructor keeps the parameters it had (tests/test_gj_groups.py holds them to the letter) and its refusals."""
         self = cls.__new__(cls)
         self.jumps_with_grad = bool(jumps_with_grad)
         self._aux = list(aux) if aux is not None else []
         self.logl_in_support = bool(logl_in_support)
         self._hist, self._hist_from = hist, hist_from
+        self._ev, self._ev_from, self._ev_every = bool(evidence), evidence_from, evidence_every
         self.__init__(*args, **kw)
         return self
 
@@ -318,6 +334,26 @@ class PTEngine(object):
             self.hist_iter = self.hist_from
         elif self._hist_from is not None:
             raise ValueError("hist_from= goes with hist=(lo, hi, nbins)")
+        # the ladder's summaries for the log-evidence (with_stages(evidence=True, evidence_from=..., evidence_every=...); see the class docstring)
+        self.evidence_on = bool(self._ev)
+        if self.evidence_on:
+            if int(ntemps) < 2:
+                raise ValueError("evidence=True needs a ladder: ntemps = %d is one temperature, there is nothing to integrate over" % int(ntemps))
+            if int(tskip) <= 0:
+                raise ValueError("evidence=True samples behind the swaps: tskip = %d proposes none" % int(tskip))
+            if (ntemps_global is not None and int(ntemps_global) != int(ntemps)) or int(temp0) != 0:
+                raise ValueError("evidence=True serves a whole ladder on one GPU: on a sharded ladder (ntemps_global / temp0) the engine would "
+                                 "not know the gap to the neighbouring block (ptmi_ev_attach takes it as dbeta[0]; ShardedPTEngine has no such stage yet)")
+            self.evidence_from = int(burn) if self._ev_from is None else int(self._ev_from)
+            if self.evidence_from < 0:
+                raise ValueError("evidence_from = %d: the first iteration sampled lies behind evidence_from >= 0" % self.evidence_from)
+            every = self._ev_every
+            if not isinstance(every, (int, np.integer)) or int(every) < 1:
+                raise ValueError("evidence_every = %r: every k-th swap epoch is sampled, k >= 1" % (every,))
+            self.evidence_every = int(every)
+            self.ev_epochs = 0
+        elif self._ev_from is not None or self._ev_every != 1:
+            raise ValueError("evidence_from= and evidence_every= go with evidence=True")
         # rows_logl: the built-in likelihood as a row kernel on the split path (see the class docstring); refused before anything is built
         self.rows_logl = bool(rows_logl)
         if self.rows_logl:
@@ -501,6 +537,15 @@ class PTEngine(object):
             self._hist_scale = nbins / (hi - lo)
             _lib.check(self.lib.ptmi_hist_attach(self.h, C.c_void_p(self.t["hist"].data_ptr()), lo.ctypes.data_as(_lib._dp),
                                                  self._hist_scale.ctypes.data_as(_lib._dp), nbins))
+        if self.evidence_on:
+            # double [5][W][nt] (shift, s1, s2, m, es) and uint64 [2][W][nt] (taken, skipped), plane-major, by local rank; in self.t:
+            # checkpoints carry them by themselves
+            from .evidence import dbeta_of
+            self.t["ev_acc"] = z((5, W, nt))
+            self.t["ev_cnt"] = z((2, W, nt), i64)
+            self.ev_dbeta = np.ascontiguousarray(dbeta_of(self.temps_mh))
+            _lib.check(self.lib.ptmi_ev_attach(self.h, C.c_void_p(self.t["ev_acc"].data_ptr()), C.c_void_p(self.t["ev_cnt"].data_ptr()),
+                                               self.ev_dbeta.ctypes.data_as(_lib._dp)))
         self.de_on = False
         self.de_head = 0
         self.iter = 0
@@ -976,6 +1021,8 @@ class PTEngine(object):
                   eig_pending=int(self._eig_pending), eig_wait=int(self._eig_wait))
         if self.hist_spec is not None:
             st["hist_iter"] = self.hist_iter
+        if self.evidence_on:
+            st["ev_epochs"] = self.ev_epochs
         if self.stats_async:
             st.update({"alt_" + k: v.cpu().numpy() for k, v in self._alt.items() if v is not None})
         return st
@@ -984,6 +1031,8 @@ class PTEngine(object):
         torch = _torch()
         if self.hist_spec is not None and ("hist_iter" not in st or "t_hist" not in st):      # refused before anything is touched
             raise ValueError("the checkpoint carries no histogram: it was written by a run without hist=")
+        if self.evidence_on and any(k not in st for k in ("ev_epochs", "t_ev_acc", "t_ev_cnt")):
+            raise ValueError("the checkpoint carries no evidence accumulators: it was written by a run without evidence=True")
         # whatever this engine has under way is void -- and is brought to an end FIRST: a factorization on the side stream (its thread
         # joined, its result dropped), statistics still running beside the launches (stats_async: they write cov / mu / M2)
         if self._eig_pending:
@@ -1009,6 +1058,8 @@ class PTEngine(object):
         self.eig_epochs = int(st["eig_epochs"])                       # (behind _eig_finish, which counts the dropped table)
         if self.hist_spec is not None:
             self.hist_iter = int(st["hist_iter"])
+        if self.evidence_on:
+            self.ev_epochs = int(st["ev_epochs"])
         if self.t["DE"] is not None:
             self.set_de_head(int(st["de_head"]))
             if int(st["de_on"]):
@@ -1100,6 +1151,29 @@ class PTEngine(object):
         """PT swap of iteration ``it`` with the whole ladder on this GPU (:631-697)."""
         _lib.check(self.lib.ptmi_swap(self.h, it))
         self.swap_proposed += 1
+        if self.evidence_on and it > self.evidence_from and (it // self.tskip) % self.evidence_every == 0:
+            _lib.check(self.lib.ptmi_ev_update(self.h))               # the post-swap lnL of every (walker, rank): one sample
+            self.ev_epochs += 1
+
+    # ------------------------------------------------------------------ log-evidence
+    def evidence_moments(self):
+        """The accumulators of the evidence stage by ``[W][T]`` (T the ranks, coldest first): ``n`` / ``skipped`` (uint64: samples taken,
+        and samples left out because lnL was not finite), ``shift``, ``s1``, ``s2`` (mean lnL = shift + s1 / n, sum (lnL - shift)^2 = s2),
+        ``m``, ``es`` (sum exp(dbeta_r lnL) = exp(m) es), and ``betas [T]`` = 1 / ``temps_mh``."""
+        if not self.evidence_on:
+            raise ValueError("no evidence stage: PTEngine.with_stages(..., evidence=True)")
+        acc = self.t["ev_acc"].cpu().numpy()
+        cnt = self.t["ev_cnt"].cpu().numpy().view(np.uint64)
+        return dict(n=cnt[0].copy(), skipped=cnt[1].copy(), shift=acc[0].copy(), s1=acc[1].copy(), s2=acc[2].copy(), m=acc[3].copy(),
+                    es=acc[4].copy(), betas=1.0 / self.temps_mh)
+
+    def evidence(self):
+        """ln Z from the samples so far (``evidence.estimates``): ``lnZ_ti``, ``lnZ_ti_corrected``, ``lnZ_ss``, each per walker and with
+        the standard error of the walkers' scatter, ``mean`` / ``var`` of lnL per rank, ``beta_min`` (the range below the hottest beta is
+        not integrated; with ``hot_chain=True`` it is nil)."""
+        from .evidence import estimates
+        mo = self.evidence_moments()
+        return estimates(mo["betas"], mo["n"], mo["shift"], mo["s1"], mo["s2"], mo["m"], mo["es"])
 
     def run(self, niter):
         """Advance ``niter`` iterations (:499-503 for every chain)."""

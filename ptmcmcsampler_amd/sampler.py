@@ -35,6 +35,15 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
   from the AM ring (``PTEngine.with_stages(hist=...)``): ``<outDir>/hist.npz`` (``counts``, ``under``, ``over``, ``edges``, ``first_iter``,
   ``last_iter``, ``nwalkers``) at every save, ``sampler.hist`` after the run; ``checkpoint=True`` runs resume the counts, a replay of
   chain files cannot;
+* ``sampler.log_evidence = True`` or ``{"every": k}`` (before ``sample()``; any likelihood, any path; a ladder of at least two
+  temperatures): the log-evidence ln Z from the whole ladder of EVERY walker.  Behind every swap after ``burn`` (every k-th with
+  ``every``) the device folds the post-swap lnL of every (walker, rank) into per-temperature moments (``PTEngine.with_stages(evidence=True)``,
+  csrc/ptmi_ev.hip) -- where the reference keeps one text file per temperature (``writeHotChains``) to be integrated offline.
+  ``sampler.evidence`` after the run and ``<outDir>/evidence.npz`` at every save: ``lnZ_ti`` (thermodynamic integration, trapezoid),
+  ``lnZ_ti_corrected`` (its second-order term from the variances), ``lnZ_ss`` (stepping stones), each ``*_per_walker`` and with
+  ``*_sem`` from the walkers' scatter, ``mean`` / ``var`` of lnL per rank, ``beta_min`` (the range below the hottest beta is not
+  integrated: run with ``hotChain=True`` to reach the prior), and the moments themselves (``evidence.py``); ``checkpoint=True`` runs
+  resume the accumulators, a replay of chain files cannot;
 * engine options: ``cov_mode="pooled"`` (one covariance adapted from all walkers instead of one per walker),
   ``swap_mode="oddeven"`` (disjoint swap pairs instead of the reference's hot -> cold sweep), ``pick_mode="walker"`` (one
   proposal-type draw per walker and iteration), ``eig_mode="ql"`` / ``"jacobi"`` / ``"sytrd"`` / ``"hipsolver"`` (covariance epochs factorized on the device: per-walker matrices by
@@ -143,6 +152,11 @@ class PTSampler(object):
     # scalars or [ndim].  An attribute for the same reason as batched_aux
     posterior_hist = None
     hist = None
+    # s.log_evidence = True, or {"every": k} (before sample()): ln Z from the ladder of EVERY walker -- per-temperature lnL moments taken on
+    # the device behind every (k-th) swap after burn (PTEngine.with_stages(evidence=True)): <outDir>/evidence.npz at every save, s.evidence
+    # after the run.  An attribute for the same reason as batched_aux
+    log_evidence = False
+    evidence = None
 
     def __init__(self, ndim, logl, logp, cov, groups=None, loglargs=[], loglkwargs={}, logpargs=[], logpkwargs={},
                  logl_grad=None, logp_grad=None, comm=None, outDir="./chains", verbose=True, resume=False, seed=None,
@@ -380,6 +394,10 @@ class PTSampler(object):
             raise NotImplementedError("posterior_hist counts every walker's cold chain on the device; chain files hold the kept walkers' "
                                       "thinned rows only, so a replayed run cannot continue the counts: resume from a device checkpoint "
                                       "(PTSampler(..., checkpoint=True) from the first run on)")
+        if self._replaying and self.log_evidence:
+            raise NotImplementedError("log_evidence sums the lnL of every walker's whole ladder on the device; chain files hold the kept "
+                                      "walkers' thinned rows only, so a replayed run cannot continue the sums: resume from a device checkpoint "
+                                      "(PTSampler(..., checkpoint=True) from the first run on)")
         if self._replaying:
             # PTMCMCSampler.py:290-313: the text rows are all there is (chains the reference wrote, or a run of ours without
             # checkpoints).  In the reference every MPI rank replays its own chain_<T>.txt; here the one process replays
@@ -479,8 +497,19 @@ class PTSampler(object):
             split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
             jumps=[(f, n) for f, n in stage_list] if stage_list else None,
             jumps_with_grad=bool(stage_list) and sum(self._grad_weights) > 0, aux=list(self._batched_aux) or None,
-            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist,
+            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **self._evidence_kw(),
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
+
+    def _evidence_kw(self):
+        """``log_evidence`` -> the keywords of ``PTEngine.with_stages`` (none where it is off; ``evidence_from`` is the engine's default, burn)."""
+        le = self.log_evidence
+        if le is None or le is False:
+            return {}
+        if le is True:
+            return dict(evidence=True)
+        if isinstance(le, dict) and set(le) <= {"every"}:
+            return dict(evidence=True, evidence_every=le.get("every", 1))
+        raise ValueError('log_evidence is True or {"every": k} (got %r)' % (le,))
 
     # ------------------------------------------------------------------ sample (:374-528)
     def sample(self, p0, Niter, ladder=None, Tmin=1, Tmax=None, Tskip=100, isave=1000, covUpdate=1000, SCAMweight=20,
@@ -634,7 +663,9 @@ class PTSampler(object):
                                    bool(eng.am_rle))
                                   # (the histogram's bins, only where there are some: the other runs' fingerprints stay what they were)
                                   + ((("hist", eng.hist_from, eng.hist_spec[2]),) if eng.hist_spec is not None else ()), *groups,
-                                  *(eng.hist_spec[:2] if eng.hist_spec is not None else ())),
+                                  *(eng.hist_spec[:2] if eng.hist_spec is not None else ()),
+                                  # (the evidence stage's sampling, only where it is on)
+                                  *((("evidence", eng.evidence_from, eng.evidence_every),) if eng.evidence_on else ())),
                            digest(*(spec(self.logl_spec) + spec(self.logp_spec)))], dtype=np.int64)
 
     def _load_checkpoint(self):
@@ -947,7 +978,22 @@ class PTSampler(object):
         np.savez(tmp, **self.hist)
         os.replace(tmp, os.path.join(self.outDir, "hist.npz"))
 
+    def _write_evidence(self):
+        """The estimates from the samples so far, with the moments they come from -> self.evidence and <outDir>/evidence.npz."""
+        from .evidence import estimates
+        mo = self.engine.evidence_moments()
+        ev = estimates(mo["betas"], mo["n"], mo["shift"], mo["s1"], mo["s2"], mo["m"], mo["es"])
+        ev.update(mo)
+        self.evidence = ev
+        tmp = os.path.join(self.outDir, "evidence.tmp.npz")
+        np.savez(tmp, **ev)
+        os.replace(tmp, os.path.join(self.outDir, "evidence.npz"))
+
     def writeOutput(self, iter):
+        if self.log_evidence and not self.engine.evidence_on:
+            raise ValueError("log_evidence was set after the engine was built: set it before the first sample()")
+        if self.engine.evidence_on and iter > 0:
+            self._write_evidence()                                    # ahead of the checkpoint: it carries the sums up to here
         if self.posterior_hist is not None and self.engine.hist_spec is None:
             raise ValueError("posterior_hist was set after the engine was built: set it before the first sample()")
         if self.engine.hist_spec is not None and iter > 0:
