@@ -118,7 +118,10 @@ ENGINE_CASES = [
     (21, 3, 5, (3, 0, 2), {}),                                # odd ndim: 8-byte pieces
     (21, 3, 5, (3, 2, 2), {}),
     (20, 4, 6, (3, 2, 2), dict(pick_mode="walker")),
-    (6, 2, 700, (3, 2, 2), dict(cov_mode="pooled")),          # 1400 chains: two blocks of the listing
+    # 1400 chains: two blocks of the listing -- a second block's start, no more: cj_gather_kernel's strided sums over the blocks
+    # (32 partial sums per function, block b in partial b % 32) take their second step from 33 blocks on, which
+    # test_listing_beyond_one_stride_of_blocks reaches
+    (6, 2, 700, (3, 2, 2), dict(cov_mode="pooled")),
 ]
 
 
@@ -169,6 +172,131 @@ def test_stage_between_row_kernels_and_between_shape_kernels(mods, d, nt, W, wei
     assert (js[..., 0].sum(-1) + cj[..., 0].sum(-1) == g.iter).all()
     assert cj[..., 0].sum(axis=(0, 1)).min() > 0 and (cj[..., 1] <= cj[..., 0]).all() and cj[..., 1].sum() > 0
     assert 0 < g.get("nacc").sum() < W * nt * g.iter
+
+
+LB, STRIDE = 1024, 32                                         # chain slots per listing block, partial sums per function (csrc/ptmi_cj.hip)
+
+
+def _box_uniforms(orc, seed, it, sid, d):
+    """The d uniforms of the library's box draw for stream ``sid`` at iteration ``it`` (test_box_draw_holds_the_oracles_uniforms)."""
+    u = np.empty(d)
+    for i in range(d):
+        wd = orc.philox([it & 0xFFFFFFFF, it >> 32, sid, SLOT_CJ + (i >> 1)], [seed & 0xFFFFFFFF, seed >> 32])
+        word = ((wd[3] << 32) | wd[2]) if (i & 1) else ((wd[1] << 32) | wd[0])
+        u[i] = (word >> 11) * 2.0 ** -53
+    return u
+
+
+@pytest.mark.parametrize("d,pick_mode", [(6, "chain"), (5, "chain"), (6, "walker")])
+def test_listing_beyond_one_stride_of_blocks(mods, d, pick_mode):
+    """7 x 10 007 = 70 049 chains: 69 listing blocks, 417 slots in the last.  cj_gather_kernel sums the block counts of a function in
+    32 strided partial sums (``for (b = part; b < nblk; b += 32)``: ptot, and ppre for the blocks before its own): from 33 blocks on the
+    loop takes a second step, here a second and a third, and the blocks 32 .. 68 have counts of earlier strides in their ppre.  A wrong
+    start sends rows to the wrong chains, and nothing the device compares with itself notices.
+
+    So every jump stage of the run is held to NumPy, from what the proposal launch left: the picks in qaux[.][1], temp_of and the
+    proposal buffer give, per function, the ascending slot list; each callback must have been handed exactly those rows and
+    beta[temp_of], in that order (hence offs); after ptmi_cj_end the proposal buffer holds what the callbacks returned at the listed
+    chains and its old bits everywhere else, qaux[.][0] the qxy.  The box draw (cj_box_kernel reads list[k0 + k]) is held to the
+    oracle's Philox for rows at both ends of its span and seeded ones between.  Three functions of weights 3, 2, 1 beside SCAM and DE;
+    16-byte and 8-byte pieces; pick_mode "walker": runs of 7 slots share a function.  Swaps (3), covariance epochs (4) and the DE
+    activation (8) lie inside, so temp_of is not the identity."""
+    from ptmcmcsampler_amd.engine import box_draw_jump
+    orc, _lib, PTEngine = mods
+    nt, W, seed = 7, 10007, 31
+    n = W * nt
+    nblk = -(-n // LB)
+    assert nblk == 69 and nblk > 2 * STRIDE and n - (nblk - 1) * LB == 417
+    rs = np.random.RandomState(d + nt)
+    lo, hi = -0.4 - 0.1 * rs.rand(d), 0.4 + 0.1 * rs.rand(d)
+    A = rs.randn(d, d)
+    cov0 = (A @ A.T / d + 0.5 * np.eye(d)) * 0.01
+    p0 = rs.randn(W, nt, d) * 0.05
+    log = []
+
+    def stretchJump(X, it, beta):
+        return X * 0.5 + (0.05 * beta)[:, None], -0.1 * beta
+
+    def shiftJump(X, it, beta):
+        X += 0.01 * float((it % 5) - 2)                       # in place: the same rows come back
+        return X, None
+
+    def logl(X):
+        return -0.5 * (X * X).sum(-1)
+
+    g = PTEngine(d, nt, W, cov0, weights=(3, 0, 2), cov_update=4, burn=8, tskip=3, seed=seed, split=True, cov_mode="pooled", pick_mode=pick_mode,
+                 jumps=[(stretchJump, 3), (box_draw_jump(lo, hi), 2), (shiftJump, 1)])
+    nb = C.c_size_t(0)
+    _lib.check(g.lib.ptmi_cj_work_bytes(g.h, C.byref(nb)))
+    al16 = lambda v: (v + 15) & ~15                                   # noqa: E731
+    assert nb.value == al16(4 * n) + 4 * nblk * _lib.CJ_MAXFUN + al16(8 * (_lib.CJ_MAXFUN + 1))   # the library's own block count
+    nf, fop, beta_of = len(g._jumps), np.asarray(g._fun_of_pick), 1.0 / g.temps_mh
+    assert nf == 3 and fop.tolist() == [0, 0, 0, 1, 1, 2]
+
+    def recorded(f, func):
+        def call(X, it, beta):
+            given = (X.clone(), beta.clone())
+            Q, qxy = func(X, it, beta)
+            log.append((f, it, given[0], given[1], Q.clone(), None if qxy is None else qxy.clone()))
+            return Q, qxy
+        return call
+
+    g._jumps[:] = [recorded(f, func) for f, func in enumerate(g._jumps)]
+    stage, seen = g.jump_stage, dict(stages=0, rows=np.zeros(nf, np.int64), moved=0)
+
+    def checked_stage(it):
+        g.sync()
+        before = g.proposals().cpu().numpy().reshape(n, d).copy()
+        qa = g.t["qaux"].cpu().numpy().reshape(n, 4).copy()
+        temp_of = g.get("temp_of").reshape(n).astype(np.int64)
+        del log[:]
+        total = stage(it)
+        g.sync()
+        after = g.proposals().cpu().numpy().reshape(n, d)
+        qa2 = g.t["qaux"].cpu().numpy().reshape(n, 4)
+        what = "%s d=%d iteration %d" % (pick_mode, d, it)
+        pick = qa[:, 1].astype(np.int64) - _lib.J_NTYPES
+        fun = np.where((pick >= 0) & (pick < len(fop)), fop[np.clip(pick, 0, len(fop) - 1)], -1)
+        if pick_mode == "walker":
+            assert (fun.reshape(W, nt) == fun.reshape(W, nt)[:, :1]).all(), what
+        want_after, want_qxy = before.copy(), qa[:, 0].copy()
+        assert [e[0] for e in log] == [f for f in range(nf) if (fun == f).any()] and all(e[1] == it for e in log), what
+        for f, _, X, beta, Q, qxy in log:
+            slots = np.flatnonzero(fun == f)                          # ascending: the order of the list
+            assert_same(X.cpu().numpy(), before[slots], "%s: the rows function %d was handed" % (what, f))
+            assert_same(beta.cpu().numpy(), beta_of[temp_of[slots]], "%s: the beta function %d was handed" % (what, f))
+            want_after[slots] = Q.cpu().numpy()
+            want_qxy[slots] = 0.0 if qxy is None else qxy.cpu().numpy()
+            seen["rows"][f] += len(slots)
+            if f == 0:
+                assert_same(Q.cpu().numpy(), before[slots] * 0.5 + (0.05 * beta_of[temp_of[slots]])[:, None], what + ": stretchJump")
+            if f == 1:                                                # the library's draw: both ends of the span and seeded rows between
+                q = Q.cpu().numpy()
+                assert (q >= lo).all() and (q <= hi).all(), what
+                ks = np.unique(np.concatenate([[0, 1, len(slots) - 2, len(slots) - 1], np.random.RandomState(it).randint(0, len(slots), 12)]))
+                for k in ks:
+                    sid = (slots[k] // nt) * nt + int(temp_of[slots[k]])
+                    assert_same(q[k], lo + (hi - lo) * _box_uniforms(orc, seed, it, int(sid), d), "%s: the box draw of list entry %d" % (what, k))
+        assert total == (fun >= 0).sum() == sum(len(e[2]) for e in log), what
+        assert list(g._cj_offs) == [int((fun >= 0)[fun < f].sum()) for f in range(nf + 1)], what + ": offs"   # the chains of the functions before f
+        assert_same(after, want_after, what + ": the proposal buffer behind ptmi_cj_end")
+        assert_same(qa2[:, 0], want_qxy, what + ": qxy")
+        assert_same(qa2[:, 1:], qa[:, 1:], what + ": the rest of qaux")
+        seen["stages"] += 1
+        seen["moved"] += int((temp_of != np.tile(np.arange(nt), W)).sum())
+        return total
+
+    g.jump_stage = checked_stage
+    g.init_state_callback(p0, logl, None)
+    for m, fused in ((4, True), (3, False), (4, True)):
+        g.run_callback(m, logl, None, fused=fused)
+    g.sync()
+    assert g.iter == 11 and seen["stages"] == 11 and seen["moved"] > 0 and g.get("nswap").sum() > 0
+    # every function had rows in every stage, in about the proportion of its weight (3 : 2 : 1 of 9 before DE joins, of 11 after)
+    assert (seen["rows"] > 11 * n // 22).all() and seen["rows"][0] > seen["rows"][1] > seen["rows"][2]
+    cj = g.get("cjstat").astype(np.int64)
+    assert (g.get("jstat").astype(np.int64)[..., 0].sum(-1) + cj[..., 0].sum(-1) == g.iter).all()
+    assert cj[..., 0].sum() == seen["rows"].sum() and cj[..., 1].sum() > 0
 
 
 def test_accept_is_refused_inside_the_stage_and_empty_spans_are_not_called(mods):

@@ -83,16 +83,17 @@ def _oracle_side(orc, d, nt, W, weights, like, extra):
         logl = ("dense", rs.randn(d) * 0.05, (P + P.T) / 2.0)
     seen = dict(stretch=0, shift=0, out=0, outside=0)
     pairs = _jump_pairs(lo, hi, seen)
-    kw = dict(weights=weights, cov_update=20, burn=40, tskip=7, seed=31, logl=logl, logp=("box", lo, hi), am_mode="rows", **extra)
+    kw = dict(weights=weights, cov_update=20, burn=40, tskip=7, seed=31, logl=logl, logp=("box", lo, hi), am_mode="rows")
+    kw.update(extra)
     o = orc.OracleEngine(d, nt, W, cov0, jumps=[(fn, w) for _, fn, w in pairs], **kw)
     o.init_state(p0)
     return o, kw, p0, cov0, lo, hi, seen
 
 
-def _reached(o, seen, W, nt):
+def _reached(o, seen, W, nt, niter=105):
     """The run went where the case is for."""
     js, cj = o.jstat.astype(np.int64), o.cjstat.astype(np.int64)
-    assert cj.shape == (W, nt, 5, 2) and (js[..., 0].sum(-1) + cj[..., 0].sum(-1) == 105).all()
+    assert cj.shape == (W, nt, 5, 2) and (js[..., 0].sum(-1) + cj[..., 0].sum(-1) == niter).all()
     assert seen["stretch"] == cj[..., :2, 0].sum() and seen["shift"] == cj[..., 2, 0].sum() and seen["out"] == cj[..., 4, 0].sum()
     assert cj[..., 4, 1].sum() <= seen["out"] - seen["outside"]       # a proposal outside the box is never accepted
     if W * nt > 1:
@@ -101,7 +102,7 @@ def _reached(o, seen, W, nt):
         assert js[..., 2, 0].sum() > 0                                 # DE joined behind the custom entries
     if nt > 1:
         assert o.nswap.sum() > 0
-    assert o.cfg.de_on == 1 and o.iter == 105
+    assert o.cfg.de_on == 1 and o.iter == niter
 
 
 CASES = [
@@ -112,16 +113,28 @@ CASES = [
     (20, 4, 6, (3, 2, 2), "dense", dict(pick_mode="walker")),         # one pick per walker
     (5, 2, 3, (3, 2, 2), "iso", dict(groups=[[0, 1, 2, 3, 4], [3, 1], [2]])),   # parameter groups beside custom picks: no group drawn for those
     (4, 1, 1, (3, 2, 2), "dense", {}),                                # one chain: empty spans, no ladder
+    # 70 049 chains: 69 listing blocks, 417 slots in the last -- cj_gather_kernel's strided sums over the blocks (32 partial sums per
+    # function) take a second and a third step (tests/test_custom_jump_gpu.py test_listing_beyond_one_stride_of_blocks).  12 iterations
+    # with the epochs drawn in: swaps at 3, 6, 9, 12, covariance epochs at 4, 8, 12, DE joins at 8.  The case is bound by the host: measured on
+    # one core, the oracle's start 1.8 s and its 12 iterations 0.6 s, and the oracle's likelihood handed back row by row to the callback
+    # engine 0.45 - 0.5 s per pass, 13 passes: 8 - 9 s in all on such a host, 1.9 s (pytest --durations) on the faster host of an MI355X.
+    (6, 7, 10007, (3, 2, 2), "iso", dict(cov_mode="pooled", cov_update=4, burn=8, tskip=3, segments=(5, 1, 6), blocks=69)),
 ]
+LB, STRIDE = 1024, 32                                                 # chain slots per listing block, partial sums per function (csrc/ptmi_cj.hip)
 
 
 @pytest.mark.parametrize("d,nt,W,weights,like,extra", CASES)
 def test_custom_jump_stage_equals_the_oracle(mods, d, nt, W, weights, like, extra, monkeypatch):
     """Four device engines -- row kernels with one launch per iteration, with two, the shape kernels, and the callback path with the
     oracle's likelihood handed back -- against ONE oracle run, after uneven pieces across covariance epochs (20), DE activation (40)
-    and swaps (7)."""
+    and swaps (7); the 70 049-chain case sets its own, shorter ones (``extra``: epochs at 4, 8 and 3, pieces of 5, 1 and 6)."""
     import torch
     orc, _lib, PTEngine = mods
+    extra = dict(extra)
+    segments = extra.pop("segments", (25, 3, 1, 46, 30))
+    blocks = extra.pop("blocks", None)                                # a case that is there for its number of listing blocks says so
+    if blocks is not None:
+        assert blocks == -(-W * nt // LB) > 2 * STRIDE
     o, kw, p0, cov0, lo, hi, seen = _oracle_side(orc, d, nt, W, weights, like, extra)
     lo_t, hi_t = torch.as_tensor(lo, device="cuda"), torch.as_tensor(hi, device="cuda")
 
@@ -145,7 +158,7 @@ def test_custom_jump_stage_equals_the_oracle(mods, d, nt, W, weights, like, extr
         v = C.c_int32(0)
         _lib.check(engines[0][1].lib.ptmi_split_am_piece(engines[0][1].h, C.byref(v)))
         assert v.value > 0                                            # the row kernels serve the handle
-    for n in (25, 3, 1, 46, 30):
+    for n in segments:
         o.run(n)
         for mode, g, cbs in engines:
             if mode == "shape kernels":
@@ -155,7 +168,9 @@ def test_custom_jump_stage_equals_the_oracle(mods, d, nt, W, weights, like, extr
             g.run_callback(n, *cbs, fused=(mode != "rows two launches"))
             monkeypatch.delenv("PTMI_SPLIT_ROWS", raising=False)
             _compare(g, o, "%s at iteration %d" % (mode, g.iter))
-    _reached(o, seen, W, nt)
+    _reached(o, seen, W, nt, sum(segments))
+    if blocks is not None:
+        assert not np.array_equal(o.slot_of, np.tile(np.arange(nt, dtype=o.slot_of.dtype), (W, 1)))   # the ladders have moved
 
 
 @pytest.mark.parametrize("name", ["traj_custom_d4", "traj_custom_groups_d5"])

@@ -188,6 +188,86 @@ def test_hmc_through_callbacks_equals_the_fused_device_hmc(mods):
     assert torch.is_tensor(s._gj_rows)
 
 
+LB = 1024                                                             # chain slots per block of the stage's listing (GJ_LB, csrc/ptmi_gjcb.h)
+BUFFERS = ("X", "lnL", "lp", "temp_of", "slot_of", "nacc", "jstat", "nswap", "AM", "gj", "cov", "Ut", "S", "DE")
+
+
+def _listing_blocks(_lib, g, want):
+    """The listing's block count from W x T -- and, for an HMC-only handle, from the library's own work area, which holds one int32
+    per block (work_layout of csrc/ptmi_gjcb.h): another LB fails here and does not quietly make the case a small one.  A handle with
+    NUTS has no such check: its work area also holds the trees' stacks, whose sizes are the library's own, so there ``want`` is held
+    to this file's LB alone."""
+    n = g.W * g.nt
+    nblk = -(-n // LB)
+    assert nblk == want
+    if g.grad_weights[0] == 0 and not g.split_nuts:
+        al16 = lambda v: (v + 15) & ~15                               # noqa: E731
+        nb = C.c_size_t(0)
+        _lib.check(g.lib.ptmi_gj_work_bytes(g.h, C.byref(nb)))
+        assert nb.value == 3 * al16(8 * n * g.d) + al16(8 * n) + al16(16 * n) + al16(4 * n) + al16(4 * nblk) + 16   # q, p, xs, joint0, ist, list, bcnt, n
+    return nblk
+
+
+def _split_equals_fused(mods, d, nt, W, kw, segments, nblk, beyond, absent=(), **split_kw):
+    """Two engines from one start, the fused kernels' own gradient jumps and the callback path with the built-in likelihood's bits as
+    callbacks (ptmi_rows_logl, gradient -X): every buffer bit for bit after every segment; ``absent`` names the buffers neither
+    engine has in this configuration.  ``nblk``: the listing's block count, ``beyond``: the count it must exceed for the case's term to be live.  Returns the callback engine and the
+    number of rows of every gradient round."""
+    orc, _lib, PTEngine = mods
+    rs = np.random.RandomState(W + d)
+    A = rs.randn(d, d)
+    cov0 = (A @ A.T / d + 0.5 * np.eye(d)) * 0.05
+    p0 = rs.randn(W, nt, d) * 0.5
+    f = PTEngine(d, nt, W, cov0, **kw)
+    s = PTEngine(d, nt, W, cov0, split=True, **split_kw, **kw)
+    assert _listing_blocks(_lib, s, nblk) > beyond
+    f.init_state(p0)
+    s.init_state(p0)
+    bl, rounds = s.builtin_logl(), []
+
+    def logl_grad(X):
+        rounds.append(X.shape[0])
+        return bl(X), -X
+
+    for n in segments:
+        f.run(n)
+        s.run_callback(n, bl, None, logl_grad=logl_grad)
+        f.sync()
+        s.sync()
+        for name in BUFFERS:
+            if name in absent:
+                assert s.t.get(name) is None and f.t.get(name) is None, name
+            else:
+                assert_same(s.get(name), f.get(name), "split vs fused, %d chains, it=%d: %s" % (W * nt, s.iter, name))
+    assert s.get("nswap").sum() > 0 and not np.array_equal(s.get("slot_of"), np.tile(np.arange(nt, dtype=np.int32), (W, 1)))
+    return s, rounds
+
+
+def test_hmc_listing_beyond_one_wave_of_blocks(mods):
+    """7 x 10 007 = 70 049 chains, 4-d, SCAM + DE + HMC with 2 leapfrogs: 69 listing blocks.  gj_fill_kernel's start of block b is the
+    sum of bcnt[0 .. b) over a block's 16 waves, wave k holding part[k] = the counts of blocks 64 k .. 64 k + 63: for the blocks
+    65 .. 68 part[1] is non-zero -- up to 64 x 1024 chains (test_full_size_invariants) every part[k], k >= 1, is zero.  A wrong start
+    hands the gradients of one chain to another: against the fused kernels' HMC, every buffer.  Swaps (3), covariance epochs (4) and the
+    DE activation (8) inside."""
+    kw = dict(weights=(20, 0, 20), grad_weights=(0, 20), hmc=(0.2, 2, 3), cov_update=4, burn=8, tskip=3, seed=99, cov_mode="pooled", am_mode="rows")
+    s, rounds = _split_equals_fused(mods, 4, 7, 10007, kw, (5, 6), nblk=69, beyond=65)
+    js = s.get("jstat").astype(np.int64)
+    assert js[..., 4, 0].sum() > 0 and 0 < js[..., 4, 1].sum() < js[..., 4, 0].sum() and js[..., 2, 0].sum() > 0
+    assert len(rounds) >= 2 * s.iter and min(rounds) > 0              # a round per leapfrog at the least
+
+
+def test_hmc_listing_beyond_1024_blocks(mods):
+    """16 x 65 601 = 1 049 616 chains, 2-d, SCAM + HMC at equal weights: 1026 listing blocks.  In gj_fill_kernel thread tid sums
+    bcnt[tid], bcnt[tid + 1024], ... below its block: for block 1025 thread 0 takes a second step (bcnt[1024]), and every part[k] is
+    non-zero from block 960 on.  Four iterations with swaps at 2 and 4; no covariance epoch (cov_update = 8: an AM ring of 8 MB)."""
+    kw = dict(weights=(20, 0, 0), grad_weights=(0, 20), hmc=(0.2, 2, 3), cov_update=8, burn=8, tskip=2, seed=7, cov_mode="pooled", am_mode="rows")
+    s, rounds = _split_equals_fused(mods, 2, 16, 65601, kw, (3, 1), nblk=1026, beyond=1025, absent=("DE",))
+    js = s.get("jstat").astype(np.int64)
+    assert js[..., 4, 0].sum() > 0 and 0 < js[..., 4, 1].sum() < js[..., 4, 0].sum()
+    assert len(rounds) >= 2 * s.iter and min(rounds) > 0
+    assert 0.45 < js[..., 4, 0].sum() / (16 * 65601.0 * s.iter) < 0.55   # half the chains pick HMC (4.2 million picks: a standard error of 0.00024)
+
+
 def test_accept_refuses_an_unfinished_gradient_stage_and_shapes_are_checked(mods):
     import torch
     orc, _lib, PTEngine = mods

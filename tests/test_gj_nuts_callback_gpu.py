@@ -16,7 +16,7 @@ import os
 import numpy as np
 import pytest
 
-from test_gj_callback_gpu import ORACLE_CASES, _case, _compare_all, _halfnormal_start, _interval_torch, _oracle_callbacks
+from test_gj_callback_gpu import LB, ORACLE_CASES, _case, _compare_all, _halfnormal_start, _interval_torch, _oracle_callbacks, _split_equals_fused
 from test_gpu_parity import assert_same, mods  # noqa: F401  (mods is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -195,6 +195,22 @@ def test_nuts_through_callbacks_equals_the_fused_device_nuts(mods, d, diag):
             assert_same(s.get(name), f.get(name), "split vs fused %dd it=%d %s" % (d, s.iter, name))
     js = s.get("jstat").astype(np.int64)
     assert js[..., _lib.J_NUTS, 1].sum() > 0 and js[..., _lib.J_HMC, 1].sum() > 0 and js[..., 1, 1].sum() > 0 and js[..., 2, 0].sum() > 0
+
+
+def test_nuts_listing_beyond_one_wave_of_blocks(mods):
+    """7 x 10 007 = 70 049 chains, 4-d, SCAM + DE + NUTS with trees of height <= 3: 69 listing blocks, so gj_fill_kernel's part[1] (the
+    counts of blocks 64 .. 127, held by wave 1) is non-zero for the blocks 65 .. 68 -- test_hmc_listing_beyond_one_wave_of_blocks.
+    Unlike HMC's fixed trajectory, a tree ends when it turns or is full, and the first call of every chain searches its step: the set
+    of listed chains thins out from round to round, down to a few, so the blocks' counts are sparse and uneven (many of them zero).
+    Against the fused kernels' NUTS, every buffer; swaps (3), covariance epochs (4), DE activation and the end of the step-size
+    adaptation (8) inside."""
+    _lib = mods[1]
+    kw = dict(weights=(20, 0, 20), grad_weights=(20, 0), nuts_maxdepth=3, cov_update=4, burn=8, tskip=3, seed=77, cov_mode="pooled", am_mode="rows")
+    s, rounds = _split_equals_fused(mods, 4, 7, 10007, kw, (5, 6), nblk=69, beyond=65, split_nuts=True)
+    js = s.get("jstat").astype(np.int64)
+    assert js[..., _lib.J_NUTS, 0].sum() > 0 and js[..., _lib.J_NUTS, 1].sum() > 0 and js[..., 2, 0].sum() > 0
+    # the chains whose search and tree took longest are alone in an iteration's last rounds: fewer rows than blocks, so empty blocks
+    assert 0 < min(rounds) < -(-7 * 10007 // LB) < LB < max(rounds) and len(rounds) > s.iter
 
 
 def test_accept_refuses_an_open_nuts_stage_and_the_flag_alone_changes_nothing(mods):

@@ -82,6 +82,15 @@ class _Stage(object):
         self.g.sync()
         return self.work[:4 * self.n_in].view(self.torch.int32).cpu().numpy().copy()
 
+    FILL32 = np.frombuffer(b"\xa5" * 4, dtype=np.int32)[0]           # what the work area holds where the stage wrote nothing
+
+    def tables(self):
+        """pos [n_in] and list [n_in] (entries beyond the count: never written)."""
+        self.g.sync()
+        n, off = self.n_in, (4 * self.n_in + 15) & ~15
+        w = self.work.cpu().numpy()
+        return w[:4 * n].view(np.int32).copy(), w[off:off + 4 * n].view(np.int32).copy()
+
     def rows(self, rows_in, rows):
         self._lib.check(self.g.lib.ptmi_sup_rows(self.g.h, self.work.data_ptr(), rows_in.data_ptr(), rows.data_ptr()))
 
@@ -89,22 +98,19 @@ class _Stage(object):
         self._lib.check(self.g.lib.ptmi_sup_end(self.g.h, self.work.data_ptr(), vals.data_ptr() if vals is not None else None, out.data_ptr()))
 
 
-@pytest.mark.parametrize("n_in", [1, 63, 64, 65, 1024, 1025, 2100, 3073])
-@pytest.mark.parametrize("d", [1, 5, 6])
-def test_listing_rows_and_values_against_numpy(mods, handles, d, n_in):
-    """Waves and blocks that are full, one short and one over; one, two, three and four listing blocks; odd and even ndim."""
+def _check_listing(_lib, g, d, n_in, rs, patterns):
+    """ptmi_sup_begin / _rows / _end on every pattern of ``patterns(n_in, rs)`` (drawn behind the rows) against
+    np.flatnonzero(lp != -inf) and its inverse, exact, every call twice."""
     import torch
-    orc, _lib, PTEngine = mods
-    g = handles(d)
-    rs = np.random.RandomState(1000 * d + n_in)
     SENT, PAD = -77.25, 8
     rows_np = rs.randn(n_in, d)
     rows_in = torch.from_numpy(rows_np).to(g.device)
-    for what, lp_np in _patterns(n_in, rs):
+    for what, lp_np in patterns(n_in, rs):
         what = "%s, n_in=%d, d=%d" % (what, n_in, d)
         mask = ~np.isneginf(lp_np)
         rank = np.cumsum(mask) - 1
         n_want = int(mask.sum())
+        want_list = np.flatnonzero(mask)
         vals_np = rs.randn(max(n_want, 1))
         lp, vals = torch.from_numpy(lp_np).to(g.device), torch.from_numpy(vals_np).to(g.device)
         want_out = np.where(mask, vals_np[np.maximum(rank, 0)], NINF)
@@ -113,7 +119,10 @@ def test_listing_rows_and_values_against_numpy(mods, handles, d, n_in):
             st = _Stage(_lib, g, n_in)
             n = st.begin(lp)
             assert n == n_want, what
-            assert np.array_equal(st.pos(), np.where(mask, rank, -1)), what
+            pos, lst = st.tables()
+            assert np.array_equal(pos, np.where(mask, rank, -1)), what + ": pos"
+            assert np.array_equal(lst[:n], want_list), what + ": list"
+            assert (lst[n:] == _Stage.FILL32).all(), what + ": list beyond n is not touched"
             rows = torch.full((n_in + PAD, d), SENT, dtype=torch.float64, device=g.device)
             if 0 < n:                                                 # (n == n_in too: the caller may skip the copy, the kernel may not get it wrong)
                 st.rows(rows_in, rows)
@@ -135,6 +144,69 @@ def test_listing_rows_and_values_against_numpy(mods, handles, d, n_in):
         g.sync()
         o = out.cpu().numpy()
         assert np.isneginf(o[:n_in]).all() and (o[n_in:] == SENT).all(), what
+
+
+@pytest.mark.parametrize("n_in", [1, 63, 64, 65, 1024, 1025, 2100, 3073])
+@pytest.mark.parametrize("d", [1, 5, 6])
+def test_listing_rows_and_values_against_numpy(mods, handles, d, n_in):
+    """Waves and blocks that are full, one short and one over; one, two, three and four listing blocks; odd and even ndim.  (At most
+    four blocks: sup_scan_kernel's cross-wave sums and its carry stay zero here -- test_listing_beyond_one_wave_of_blocks.)"""
+    orc, _lib, PTEngine = mods
+    rs = np.random.RandomState(1000 * d + n_in)
+    _check_listing(_lib, handles(d), d, n_in, rs, _patterns)
+
+
+LB = 1024                                                             # rows per block of the listing kernels (csrc/ptmi_sup.hip)
+
+
+def _block_patterns(n_in, rs):
+    """Patterns chosen from the BLOCK index: with the same count in every block a wrong start offset of a block can cancel; here the
+    counts differ from block to block, and whole blocks, wave-ends of the scan included, are empty."""
+    b = np.arange(n_in) // LB
+    nblk = int(b[-1]) + 1
+    half = np.where(rs.rand(n_in) < 0.5, rs.randn(n_in), NINF)
+    one = np.full(n_in, NINF)
+    one[np.minimum((np.arange(nblk) + 1) * LB, n_in) - 1] = rs.randn(nblk)
+    tail = np.where(b == nblk - 1, half, NINF)
+    tail[-1] = 0.5
+    dense = np.where(rs.rand(n_in) < (b % 7) / 6.0, rs.randn(n_in), NINF)
+    assert np.isneginf(dense[:min(LB, n_in)]).all() and (nblk < 7 or np.isfinite(dense[6 * LB:min(7 * LB, n_in)]).all())
+    return [("one row per block, the block's last", one),
+            ("rows in the last block only", tail),
+            ("every block but block 0", np.where(b == 0, NINF, half)),
+            ("every block but those = 63 (mod 64)", np.where(b % 64 == 63, NINF, half)),
+            ("a density per block, (b % 7) / 6", dense)]
+
+
+BIG = [
+    # n_in, blocks, chunks of 1024 block counts
+    (65536, 64, 1),                                                   # the last size one wave of sup_scan_kernel serves: wtot[1..] = 0
+    (65537, 65, 1),                                                   # one block in wave 1: wtot[0] is added for the first time
+    (66561, 66, 1),                                                   # ... a second block behind it, ragged
+    (1048576, 1024, 1),                                               # exactly one chunk: every wtot[k], no carry yet
+    (1048577, 1025, 2),                                               # the carry with a single block behind it
+    (2098177, 2050, 3),                                               # three chunks, a ragged last block
+]
+
+
+@pytest.mark.parametrize("n_in,nblk,nchunk", BIG)
+@pytest.mark.parametrize("d", [1, 2])
+def test_listing_beyond_one_wave_of_blocks(mods, handles, d, n_in, nblk, nchunk):
+    """sup_scan_kernel (ONE block of 1024 threads over the block counts) beyond the sizes an engine of a few thousand chains gives it:
+    from 65 blocks on its cross-wave sums wtot[k], k >= 1, are non-zero -- a block's start is carry + wtot[0 .. wv) + the wave's own
+    scan --, from 1025 blocks on the running ``carry`` from one chunk of 1024 block counts to the next.  Sizes on both sides of each
+    threshold, 8-byte and 16-byte pieces (d = 1, 2), the patterns of the small test and five more that depend on the block index.  The
+    block count is checked against the library's own (the work area holds two int32 per block), so another LB fails here first."""
+    orc, _lib, PTEngine = mods
+    g = handles(d)
+    assert nblk == -(-n_in // LB) and nchunk == -(-nblk // LB)
+    assert (nblk > 64) == (n_in > 65536) and (nchunk > 1) == (n_in > 1048576)
+    al16 = lambda v: (v + 15) & ~15                                   # noqa: E731
+    nb = C.c_size_t(0)
+    _lib.check(g.lib.ptmi_sup_work_bytes(g.h, n_in, C.byref(nb)))
+    assert nb.value == 2 * al16(4 * n_in) + 2 * al16(4 * nblk) + 16   # pos, list, bcnt, boff, n
+    rs = np.random.RandomState(7 * n_in + d)
+    _check_listing(_lib, g, d, n_in, rs, lambda n, r: _patterns(n, r) + _block_patterns(n, r))
 
 
 def test_the_stage_refuses_calls_out_of_sequence(mods, handles):
