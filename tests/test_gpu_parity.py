@@ -222,8 +222,11 @@ def test_curved_likelihood(mods):
 
 @pytest.mark.parametrize("d,W,n", [(12, 9, 250), (100, 70, 130), (300, 5, 130)])
 def test_pooled_covariance_mode(mods, d, W, n):
-    """One covariance from all walkers: fused Welford (matrix cores up to d = 112, tiles beyond), two-level pooling,
-    symmetric eigen-decomposition on the host (8 BLAS threads beyond 256 parameters)."""
+    """One covariance from all walkers (orc_pool_update_rle: am_mode "auto" keeps the AM row flags): pool_rle_kernel lists every slab's
+    stored rows and run lengths, pool_syrk_kernel sums the shifted outer products slab by slab on the matrix cores (one macro tile of
+    112 columns at d = 12 and 100, three per side at d = 300), pool_reduce_kernel adds the slabs in order, pool_finish_kernel
+    combines the chunk with the running statistics by Chan's formula; symmetric eigen-decomposition on the host (8 BLAS threads
+    beyond 256 parameters).  The kernels' own edges: tests/test_cov_epoch_edges_gpu.py."""
     g, o = _pair(mods, d, 3, W, cov_mode="pooled", weights=(20, 20, 20), cov_update=40, burn=80, tskip=10, seed=21)
     g.run(n)
     o.run(n)
