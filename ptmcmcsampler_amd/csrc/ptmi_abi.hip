@@ -2134,4 +2134,28 @@ int ptmi_timer_stop_ms(ptmi_handle h, double *ms)
     return PTMI_OK;
 }
 
+#ifdef PTMI_UNIT_STAMPS
+// diagnostic build (tools/unit_stamps.py): the stamps of the last persistent SCAM launch, copied to the host
+int ptmi_unit_stamps(void *dst, size_t bytes)
+{
+    const size_t all = sizeof(u64) * (size_t)PTMI_STAMP_WAVE * PTMI_STAMP_WAVES;
+    if (!dst || bytes > all) return fail(PTMI_EINVAL, "at most %zu bytes of stamps", all);
+    u64 *buf = ptmi_stamp_buffer();
+    if (!buf) return fail(PTMI_EHIP, "no stamp buffer");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(dst, buf, bytes, hipMemcpyDeviceToHost));
+    return PTMI_OK;
+}
+#endif
+
 }  // extern "C"
+
+#ifdef PTMI_UNIT_STAMPS
+u64 *ptmi_stamp_buffer()
+{
+    static u64 *buf = nullptr;
+    const size_t all = sizeof(u64) * (size_t)PTMI_STAMP_WAVE * PTMI_STAMP_WAVES;
+    if (!buf && (hipMalloc((void **)&buf, all) != hipSuccess || hipMemset(buf, 0, all) != hipSuccess)) buf = nullptr;
+    return buf;
+}
+#endif

@@ -19,7 +19,8 @@ int ptmi_fail(int code, const char *fmt, ...);
 // call, so that a test may switch them between calls.  Unset: the default in brackets.
 //   PTMI_NO_PC               nonzero: AM cycles keep the one-wave staged kernel with its AM queue, not mh_pc_kernel [0]
 //   PTMI_SWAP_FUSED          0: the swap as swap_prepare_kernel + swap_sweep_kernel, not swap_fused_kernel [1]
-//   PTMI_ULDS_PERS           0: SCAM-only cycles with one table take a table copy per block, not the persistent kernel [1]
+//   PTMI_ULDS_PERS           0: SCAM-only cycles with one table take a table copy per block, not the persistent kernel [1];
+//                            n > 1: the persistent kernel on at most n blocks, so that a small case gives a wave several units to walk
 //   PTMI_SPLIT_ROWS          0: the split path through the shape kernels' propose / accept, not the row kernels [1]
 //   PTMI_QL_SPLIT            1 / 0: ptmi_eig_ql as reduce -> chain -> apply / as one kernel per matrix [1 from 64 matrices on]; beyond
 //                            128 x 128, 0: chain and rows together in the redo kernel, not recorded rotations + apply [1]
@@ -129,7 +130,17 @@ struct KArgs {
     int gj_nslots;               // chain slots of the launch when gj_order is set (>= the chains: the longest trees' chains have a wave to themselves)
     const u64 *rp_draws;         // TEST HOOK (ptmi_test_replay): propose_kernel takes P0, Q0, Q1 and the SCAM normal's bits of every chain from here
     u64 *cjstat;                 // split path, batched custom jumps (ptmi_cj_attach): [W][T][w_host][2] proposed, accepted per pick index by RANK, or nullptr
+#ifdef PTMI_UNIT_STAMPS
+    u64 *stamps;                 // diagnostic build (tools/unit_stamps.py): the persistent SCAM kernel's clock stamps, nothing else reads them
+#endif
 };
+#ifdef PTMI_UNIT_STAMPS
+// Diagnostic build only: the persistent SCAM kernel stamps the clock around the table staging and at four places of every unit
+// into a buffer of its own (ptmi_abi.hip), PTMI_STAMP_WAVE words per wave of the launch: launch entry, behind the staging, then
+// per unit (at most PTMI_STAMP_UNITS) entry, behind the header, behind the last step, behind the exit stores, position in the walk.
+constexpr int PTMI_STAMP_UNITS = 16, PTMI_STAMP_WAVE = 2 + 5 * PTMI_STAMP_UNITS, PTMI_STAMP_WAVES = 8 * 1024;
+u64 *ptmi_stamp_buffer();
+#endif
 
 // gradient jumps (ptmi_gj.inc.h): per-rank state, Philox slots, layout of a chain's tree scratch
 enum { GJ_EPS = 0, GJ_MU = 1, GJ_HBAR = 2, GJ_EPSBAR = 3, GJ_NITER = 4, GJ_HITER = 5, GJ_HAVE_EPS = 6, GJ_NLEAP = 7 /* leapfrogs so far */, GJ_NSTATE = 8 };

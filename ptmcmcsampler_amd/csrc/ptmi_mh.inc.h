@@ -1152,6 +1152,21 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
     const int cib = STR ? wave * 16 + (lane & 15) : (int)(threadIdx.x / G);       // chain in block
     const int gl = STR ? lane >> 4 : (int)(threadIdx.x % G);
     extern __shared__ __attribute__((aligned(16))) double smem[];
+#ifdef PTMI_UNIT_STAMPS
+    // Diagnostic build (tools/unit_stamps.py): the persistent kernel's waves stamp the clock around the staging and four times per unit
+    // (ptmi_common.h PTMI_STAMP_WAVE).  A stamp is fenced against the scheduler; the _W form first waits for the wave's vector memory.
+    // Lane 0 stores a stamp directly behind it, so none is carried through the pass loop.
+#define PTMI_USTAMP(v) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define PTMI_USTAMP_W(v) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+    [[maybe_unused]] int stamp_w = -1, stamp_u = 0;          // this wave's place in the stamp buffer (words), the units it has stamped
+    if constexpr (PERS != 0) {
+        const int gw = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (PERS / 64) + wave);
+        if (a.stamps != nullptr && gw < PTMI_STAMP_WAVES) stamp_w = gw * PTMI_STAMP_WAVE;
+        u64 ts;
+        PTMI_USTAMP(ts);
+        if (stamp_w >= 0 && lane == 0) a.stamps[stamp_w] = ts;
+    }
+#endif
     // SCAM-only cycle, one parameter group: the chain-scalar half of the proposal moves into the draw pass (ScamBatch)
     constexpr bool SCAMFAST = !FULL && !GRP;
     // Box prior, SCAM cycle, one table for the launch: a SCAM jump moves no element further than |amp| max|U|, so while that REACH
@@ -1257,6 +1272,12 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
     if constexpr (BOXFAST && PERS != 0) {
         if (threadIdx.x == 0) reinterpret_cast<unsigned long long *>(smem)[a.umax_off] = 0ull;
     }
+    // PERS: the block's claim counter (see "the chains" below), in the spare word behind the box prior's maximum: every wave starts with
+    // the claim of its own number
+#define PTMI_CLAIM (reinterpret_cast<int *>(smem + a.umax_off + 1))
+    if constexpr (PERS != 0) {
+        if (threadIdx.x == 0) *PTMI_CLAIM = PERS / 64;
+    }
     if (ULDS || (a.logp_kind == PTMI_LOGP_BOX && a.box_off >= 0)) __syncthreads();
     double box_umax = 0.0;                       // BOXFAST: max |U| over the launch's table
     if constexpr (BOXFAST) {
@@ -1273,9 +1294,21 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
         }
         box_umax *= 1.0 + 0x1.0p-30;            // covers the rounding of amp * u
     }
+#ifdef PTMI_UNIT_STAMPS
+    if constexpr (PERS != 0) {
+        u64 ts;
+        PTMI_USTAMP_W(ts);
+        if (stamp_w >= 0 && lane == 0) a.stamps[stamp_w + 1] = ts;
+    }
+#endif
 
     // ---- the chains.  A block of 256 threads serves its 64 chains; a persistent block's waves walk over units of 16 chains on
     // their own (no barrier from here on)
+    // The two waves of a SIMD do not run at one pace: the vector pipe serves the older wave (0-3) first, and waves 4-7 get what it
+    // leaves (profiles/r14_unit_stamps.txt: 106 k cycles per hot unit against 224 k).  With a fixed share of eight units each, waves
+    // 0-3 were done at 70 % of the launch and the SIMDs ran their last 30 % with one wave, which alone fills the pipe less well.  So the
+    // block's positions p = 8 block + c % 8 + (c / 8) stride are CLAIMED: a wave that has finished a unit takes the block's next c from a
+    // counter in LDS, and the waves of a block end within one unit of each other.  Which wave serves a unit changes no result.
     const long long nunits = (nch + 15) / 16, ustride = PERS ? (long long)gridDim.x * (BLK / 64) : nunits;
     // The unit that holds a walker's rank-0 chain stores an AM row per step and takes ~13 % longer; which of the walker's units
     // that is changes with every swap.  The waves therefore walk over the units in an order that lists the W cold units first
@@ -1283,8 +1316,18 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
     // number of cold units for every wave (two of eight at 64 x 4096), where the plain order gave it a binomial draw.
     const int upw = nt / 16, upw1 = upw > 1 ? upw - 1 : 1;               // units per walker
     const bool cold_first = PERS && a.AM != nullptr && a.temp0 == 0 && nt % 16 == 0;
-    for (long long upos = PERS ? (long long)blockIdx.x * (BLK / 64) + wave : 0; upos < nunits; upos += ustride) {
+    for (long long upos = PERS ? (long long)blockIdx.x * (BLK / 64) + __builtin_amdgcn_readfirstlane(wave) : 0; upos < nunits;) {
     long long unit = upos;
+#ifdef PTMI_UNIT_STAMPS
+    [[maybe_unused]] int stamp_p = -1;                       // this unit's place in the stamp buffer
+    if constexpr (PERS != 0) {
+        if (stamp_w >= 0 && stamp_u < PTMI_STAMP_UNITS) stamp_p = stamp_w + 2 + 5 * stamp_u;
+        ++stamp_u;
+        u64 ts;
+        PTMI_USTAMP(ts);
+        if (stamp_p >= 0 && lane == 0) { a.stamps[stamp_p] = ts; a.stamps[stamp_p + 4] = (u64)upos; }
+    }
+#endif
     if (cold_first) {
         const long long r = upos - a.W;
         const int wq = upos < a.W ? (int)upos : (int)(r / upw1);
@@ -1341,6 +1384,17 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
 #pragma unroll
     for (int e = 0; e < EPL; ++e) PTMI_ROW_LOAD(x[e], xrow, e);
     double lnL = a.lnL[ch], lp = a.lp[ch];
+#ifdef PTMI_UNIT_STAMPS
+    if constexpr (PERS != 0) {
+        // the header ends where the state has arrived and the chain's constants are computed
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) asm volatile("" :: "v"(x[e]));
+        asm volatile("" :: "v"(lnL), "v"(lp), "v"(cc.cd0), "v"(cc.cd1), "v"(cc.cd2), "v"(cc.sc0), "v"(cc.sc1), "v"(cc.sc2));
+        u64 ts;
+        PTMI_USTAMP_W(ts);
+        if (stamp_p >= 0 && lane == 0) a.stamps[stamp_p + 1] = ts;
+    }
+#endif
     u32 nacc = 0, jp[PTMI_J_FUSED] = {0, 0, 0}, ja[PTMI_J_FUSED] = {0, 0, 0};
     long long am_next = (FULL && a.am_base != nullptr) ? a.am_base[ch] : 0;      // the chain's next precomputed AM increment
     const bool cold = live && tg == 0 && a.AM != nullptr;
@@ -1433,6 +1487,13 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
 #undef PTMI_STEP_S
     }
     }       // passes of a wide draw batch (one trip otherwise)
+#ifdef PTMI_UNIT_STAMPS
+    if constexpr (PERS != 0) {
+        u64 ts;
+        PTMI_USTAMP(ts);                          // (a cold unit's last AM rows may still be on their way: they count as exit)
+        if (stamp_p >= 0 && lane == 0) a.stamps[stamp_p + 2] = ts;
+    }
+#endif
     if (live) {
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
@@ -1451,6 +1512,21 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
                 a.jstat[(r * PTMI_J_NTYPES + j) * 2 + 1] += ja[j];
             }
         }
+    }
+#ifdef PTMI_UNIT_STAMPS
+    if constexpr (PERS != 0) {
+        u64 ts;
+        PTMI_USTAMP_W(ts);
+        if (stamp_p >= 0 && lane == 0) a.stamps[stamp_p + 3] = ts;
+    }
+#endif
+    if constexpr (PERS != 0) {
+        int c = 0;
+        if (lane == 0) c = __hip_atomic_fetch_add(PTMI_CLAIM, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        c = __builtin_amdgcn_readfirstlane(c);
+        upos = (long long)blockIdx.x * (BLK / 64) + (c % (BLK / 64)) + (long long)(c / (BLK / 64)) * ustride;       // (ascending in c: the first one past the end ends the walk)
+    } else {
+        upos += ustride;
     }
     }       // units of a persistent block (one trip otherwise)
 }
@@ -2226,8 +2302,15 @@ static int launch_mh_k(ptmi_engine *h, KArgs &a, int grid)
                         if (e != hipSuccess) return fail(PTMI_EHIP, "hipFuncSetAttribute(%zu B of LDS): %s", tp, hipGetErrorString(e));
                     }
                     const long long nunits = ((long long)c.nwalkers * c.ntemps + 15) / 16, wpb = BLKv / 64;
-                    const long long nb = (nunits + wpb - 1) / wpb;
-                    hipLaunchKernelGGL(kernp, dim3((unsigned)(nb < ncu ? nb : ncu)), dim3(BLKv), tp, h->stream, a);
+                    long long nb = (nunits + wpb - 1) / wpb;
+                    if (nb > ncu) nb = ncu;
+                    // test hook: PTMI_ULDS_PERS = n > 1 caps the grid, so that a few walkers already give every wave several units
+                    const long long cap = (long long)ptmi_env("PTMI_ULDS_PERS", 1);
+                    if (cap > 1 && nb > cap) nb = cap;
+#ifdef PTMI_UNIT_STAMPS
+                    a.stamps = ptmi_stamp_buffer();
+#endif
+                    hipLaunchKernelGGL(kernp, dim3((unsigned)nb), dim3(BLKv), tp, h->stream, a);
                     h->last_variant = PTMI_VAR_LDS_UT | PTMI_VAR_PERSISTENT | (a.box_off >= 0 ? PTMI_VAR_LDS_BOX : 0) | PTMI_VAR_LDS_DRAWT;
                     return PTMI_OK;
                 };
