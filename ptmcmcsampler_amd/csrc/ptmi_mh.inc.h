@@ -1272,11 +1272,11 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
     if constexpr (BOXFAST && PERS != 0) {
         if (threadIdx.x == 0) reinterpret_cast<unsigned long long *>(smem)[a.umax_off] = 0ull;
     }
-    // PERS: the block's claim counter (see "the chains" below), in the spare word behind the box prior's maximum: every wave starts with
-    // the claim of its own number
+    // PERS: the block's two claim counters (see "the chains" below), in the spare word behind the box prior's maximum: [0] counts the
+    // block's cold claims handed out, [1] its hot ones.  The waves take their first claims from them too, behind the barrier
 #define PTMI_CLAIM (reinterpret_cast<int *>(smem + a.umax_off + 1))
     if constexpr (PERS != 0) {
-        if (threadIdx.x == 0) *PTMI_CLAIM = PERS / 64;
+        if (threadIdx.x == 0) { PTMI_CLAIM[0] = 0; PTMI_CLAIM[1] = 0; }
     }
     if (ULDS || (a.logp_kind == PTMI_LOGP_BOX && a.box_off >= 0)) __syncthreads();
     double box_umax = 0.0;                       // BOXFAST: max |U| over the launch's table
@@ -1307,16 +1307,59 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
     // The two waves of a SIMD do not run at one pace: the vector pipe serves the older wave (0-3) first, and waves 4-7 get what it
     // leaves (profiles/r14_unit_stamps.txt: 106 k cycles per hot unit against 224 k).  With a fixed share of eight units each, waves
     // 0-3 were done at 70 % of the launch and the SIMDs ran their last 30 % with one wave, which alone fills the pipe less well.  So the
-    // block's positions p = 8 block + c % 8 + (c / 8) stride are CLAIMED: a wave that has finished a unit takes the block's next c from a
-    // counter in LDS, and the waves of a block end within one unit of each other.  Which wave serves a unit changes no result.
+    // block's positions p = 8 block + c % 8 + (c / 8) stride are CLAIMED: a wave that has finished a unit takes one of the block's next c
+    // from a counter in LDS, and the waves of a block end within one unit of each other.  Which wave serves a unit changes no result.
     const long long nunits = (nch + 15) / 16, ustride = PERS ? (long long)gridDim.x * (BLK / 64) : nunits;
-    // The unit that holds a walker's rank-0 chain stores an AM row per step and takes ~13 % longer; which of the walker's units
-    // that is changes with every swap.  The waves therefore walk over the units in an order that lists the W cold units first
-    // (position p < W: walker p's cold unit), then the others walker by walker: a wave's positions p, p + stride, ... hold the same
-    // number of cold units for every wave (two of eight at 64 x 4096), where the plain order gave it a binomial draw.
+    // The unit that holds a walker's rank-0 chain (its COLD unit) stores an AM row and a flag per step, and a wave in it waits on those
+    // stores for a third of the unit's life (155 k cycles against 105 k, same instructions); which of the walker's units that is changes
+    // with every swap.  The walk therefore lists the W cold units first (position p < W: walker p's cold unit), then the others walker
+    // by walker, so that a block knows its cold claims without looking: p ascends in c, the cold claims are the prefix c < ncold.
+    // What the order is for: a wave that waits on stores leaves the vector pipe to its SIMD's partner, which can only use it from a unit
+    // that does not wait as well.  So a block hands out its cold and its hot claims from TWO counters, and of a SIMD's two waves the older
+    // one (0-3) prefers the cold list and the younger one the hot list: the stalls of the wave that has the pipe's priority go to a partner
+    // that always has work (the other way round measured half the gain: profiles/r15_scam_ab.txt).  A wave takes from the other list only
+    // when its own is exhausted and leaves when both are.  While the block has hot units left, at most one wave of a SIMD is in a cold
+    // unit.  Without the cold-first order (no AM buffer, a hot block of a sharded ladder, ranks that do not fill whole units) ncold = 0
+    // and the claims come out as 0, 1, 2, ...
     const int upw = nt / 16, upw1 = upw > 1 ? upw - 1 : 1;               // units per walker
     const bool cold_first = PERS && a.AM != nullptr && a.temp0 == 0 && nt % 16 == 0;
-    for (long long upos = PERS ? (long long)blockIdx.x * (BLK / 64) + __builtin_amdgcn_readfirstlane(wave) : 0; upos < nunits;) {
+    [[maybe_unused]] int ncold = 0, ntot = 0;                            // the block's claims: cold c < ncold, hot ncold <= c < ntot
+    [[maybe_unused]] bool pref_cold = false;
+    if constexpr (PERS != 0) {
+        // the block's claims whose position lies below lim: whole rows of BLK / 64, then what the last row holds of it
+        auto below = [&](long long lim) -> int {
+            const long long m = lim - (long long)blockIdx.x * (BLK / 64);
+            if (m <= 0) return 0;
+            const long long q = (m - 1) / ustride, rest = m - q * ustride;
+            return (int)(q * (BLK / 64) + (rest < BLK / 64 ? rest : BLK / 64));
+        };
+        ntot = below(nunits);
+        ncold = cold_first ? below(a.W < nunits ? (long long)a.W : nunits) : 0;
+        pref_cold = __builtin_amdgcn_readfirstlane(wave) < BLK / 128;
+    }
+    // the wave's next position: a claim of its preferred list, else of the other one, else the first position past the end
+    [[maybe_unused]] auto claim = [&]() __attribute__((always_inline)) -> long long {
+        if constexpr (PERS != 0) {
+            int c = 0;
+            if (lane == 0) {
+                if (pref_cold) {
+                    c = __hip_atomic_fetch_add(PTMI_CLAIM, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (c >= ncold) c = ncold + __hip_atomic_fetch_add(PTMI_CLAIM + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                } else {
+                    c = ncold + __hip_atomic_fetch_add(PTMI_CLAIM + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (c >= ntot) {
+                        c = __hip_atomic_fetch_add(PTMI_CLAIM, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (c >= ncold) c = ntot;
+                    }
+                }
+            }
+            c = __builtin_amdgcn_readfirstlane(c);
+            return (long long)blockIdx.x * (BLK / 64) + (c % (BLK / 64)) + (long long)(c / (BLK / 64)) * ustride;       // (ascending in c)
+        } else {
+            return 0;
+        }
+    };
+    for (long long upos = PERS ? claim() : 0; upos < nunits;) {
     long long unit = upos;
 #ifdef PTMI_UNIT_STAMPS
     [[maybe_unused]] int stamp_p = -1;                       // this unit's place in the stamp buffer
@@ -1521,10 +1564,7 @@ __global__ __launch_bounds__(PERS ? PERS : 256, mh_min_blocks(G, EPL, LOGL, FULL
     }
 #endif
     if constexpr (PERS != 0) {
-        int c = 0;
-        if (lane == 0) c = __hip_atomic_fetch_add(PTMI_CLAIM, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        c = __builtin_amdgcn_readfirstlane(c);
-        upos = (long long)blockIdx.x * (BLK / 64) + (c % (BLK / 64)) + (long long)(c / (BLK / 64)) * ustride;       // (ascending in c: the first one past the end ends the walk)
+        upos = claim();
     } else {
         upos += ustride;
     }

@@ -10,7 +10,8 @@ have arrived and the chain's constants are computed; behind the last step; behin
 (csrc/ptmi_common.h PTMI_STAMP_WAVE).  The stamps are fenced, so the build's run time is not the shipped kernel's: read the SHARES.
 Reported, in clock ticks, over all waves of the last launch: the medians of header, steps and exit for cold and for hot units, the
 staging, the share of header + exit + staging in a wave's life, the skew between the two waves of a SIMD (waves j and j + 4 of a
-block) at every unit entry and at their ends, the blocks' lives and the units each half of a block served."""
+block) at every unit entry and at their ends, the blocks' lives, the units (cold, hot) each half of a block served, and the steps of a
+unit by wave class and by what the SIMD's partner wave was in meanwhile: a cold unit, a hot unit, or gone."""
 import argparse
 import ctypes as C
 import os
@@ -39,8 +40,12 @@ def report(st, W, cold_first, out):
     st = st[:nw]
     t_in, t_staged = st[:, 0], st[:, 1]
     u = st[:, 2:].reshape(nw, UNITS, 5)
-    # the buffer is not cleared between launches: a wave's units of the last launch are the leading ones stamped after its entry
-    n_units = np.cumprod(u[:, :, 0] >= t_in[:, None], axis=1).sum(1)
+    # the buffer is not cleared between launches, and a wave serves another number of units in every launch: a wave's units of the last
+    # launch are the leading ones that follow each other directly (entry within GAP ticks behind the staging or the exit before it; a
+    # stamp left by an earlier launch is older, or from another XCD's clock)
+    GAP = 50000
+    prev = np.concatenate([t_staged[:, None], u[:, :-1, 3]], axis=1)
+    n_units = np.cumprod((u[:, :, 0] >= prev) & (u[:, :, 0] - prev < GAP), axis=1).sum(1)
     on = np.arange(UNITS)[None, :] < n_units[:, None]
     header, steps, exit_ = u[:, :, 1] - u[:, :, 0], u[:, :, 2] - u[:, :, 1], u[:, :, 3] - u[:, :, 2]
     cold = on & (u[:, :, 4] < W) & cold_first
@@ -82,6 +87,29 @@ def report(st, W, cold_first, out):
     p("a block's life (first entry -> last end)                  %s   max %d" % (med(bl), bl.max()))
     p("units served per wave: waves 0-3 %s" % med(n_units[:blk].reshape(-1, 2, 4)[:, 0].reshape(-1)))
     p("units served per wave: waves 4-7 %s" % med(n_units[:blk].reshape(-1, 2, 4)[:, 1].reshape(-1)))
+    # cold and hot units by wave class, and the steps of a unit by what the SIMD's partner wave did meanwhile: the state (in a cold
+    # unit, in a hot unit, gone: behind its last exit) that covers most of the unit's steps
+    cls = ("waves 0-3", "waves 4-7")
+    cu, hu = cold[:blk].reshape(-1, 2, 4, UNITS), hot[:blk].reshape(-1, 2, 4, UNITS)
+    for h in (0, 1):
+        p("cold units served per wave: %s %s" % (cls[h], med(cu[:, h].sum(-1).reshape(-1))))
+        p("hot  units served per wave: %s %s" % (cls[h], med(hu[:, h].sum(-1).reshape(-1))))
+    t0, t1 = u[:blk, :, 1].reshape(-1, 2, 4, UNITS), u[:blk, :, 2].reshape(-1, 2, 4, UNITS)          # a unit's steps
+    p0, p3 = u[:blk, :, 0].reshape(-1, 2, 4, UNITS), u[:blk, :, 3].reshape(-1, 2, 4, UNITS)          # a unit from entry to exit
+    pend = end[:blk].reshape(-1, 2, 4)
+    st_ = steps[:blk].reshape(-1, 2, 4, UNITS)
+    for h in (0, 1):
+        q = 1 - h                                                          # the partner's half of the block
+        ov = np.zeros((3,) + t0[:, h].shape, dtype=np.int64)               # overlap with the partner cold / hot / gone
+        for k in range(UNITS):
+            lap = np.maximum(np.minimum(t1[:, h], p3[:, q, :, k, None]) - np.maximum(t0[:, h], p0[:, q, :, k, None]), 0)
+            ov[0] += np.where(cu[:, q, :, k, None], lap, 0)
+            ov[1] += np.where(hu[:, q, :, k, None], lap, 0)
+        ov[2] = np.maximum(t1[:, h] - np.maximum(t0[:, h], pend[:, q, :, None]), 0)
+        state = ov.argmax(0)
+        for kind, mine in (("cold", cu[:, h]), ("hot", hu[:, h])):
+            for si, sname in enumerate(("cold", "hot", "gone")):
+                p("%s, %-4s unit, partner %-4s: steps  %s" % (cls[h], kind, sname, med(st_[:, h], mine & (state == si))))
 
 
 def main():
