@@ -621,6 +621,42 @@ int ptmi_ev_attach(ptmi_handle h, double *acc /* dev [5][W][T] */, uint64_t *cnt
                    const double *dbeta /* host [T] */);
 int ptmi_ev_update(ptmi_handle h);
 
+/* Convergence diagnostics of EVERY cold chain, accumulated on the device (csrc/ptmi_diag.hip): the streaming sums from which the host
+ * computes Gelman-Rubin R-hat and a batch-means autocorrelation time / effective sample size over all nwalkers replicas
+ * (ptmcmcsampler_amd/diagnostics.py).  The reference's one convergence check is the neff stop rule, PTMCMCSampler.py:510-521: acor on
+ * the host over one kept chain read back from its file; these calls serve the same rule from every walker's cold chain, which the AM
+ * ring holds for the current covariance period (as ptmi_hist_update reads it).  One independent stream per (walker w, parameter j) over
+ * the cold row x of every counted iteration, in iteration order; n (samples folded so far) is the same for all streams:
+ *
+ *     if n == 0: c = x                         the stream's shift: its first counted sample
+ *     y = x - c
+ *     S1 += y;  S2 += y * y;  A += y;  n += 1
+ *     if n % batch0 == 0:
+ *         k = n / batch0;  t = A;  A = 0.0
+ *         for l = 0 .. nlevels - 1:
+ *             Q[l] += t * t                    sum of squared batch sums at level l, batch length batch0 << l
+ *             if l == nlevels - 1: break
+ *             if (k >> l) & 1: H[l] = t; break        first half of a pair: wait for its partner
+ *             t = H[l] + t                     the pair is a level l + 1 batch
+ *
+ * every operation rounded on its own, in this order (no fma); non-finite samples are not special-cased (they poison their stream's
+ * sums and no other's).  With AMflag a row without NEW / KEY repeats the last stored row before it (ptmi_am_expand's rule) and is added
+ * once per iteration: the sums do not depend on the ring mode, on how a period is cut into calls or on the launch geometry.
+ * acc: DEVICE double [2 * nlevels + 3][W][ndim], plane-major, in PARAMETER order whatever the ring's row format (ptmi_am_row_format):
+ * plane 0 c, 1 S1, 2 S2, 3 A, planes 4 .. 4 + nlevels - 1 Q, planes 4 + nlevels .. 2 nlevels + 2 H[0 .. nlevels - 2]; caller-owned,
+ * zeroed by the caller, 8-byte aligned.  ptmi_diag_attach (once per handle): 1 <= nlevels <= 16, batch0 >= 1; anything else
+ * PTMI_EINVAL.  State lives in the handle: ptmi_config and ptmi_buffers are unchanged, and a handle that never attaches launches what
+ * it launched before.  The library keeps no count: n_done, the samples folded before iter_lo, comes in with every call (a
+ * checkpoint is acc plus one integer).
+ * ptmi_diag_update folds iterations iter_lo .. iter_hi of every walker from the handle's CURRENT ring (ptmi_set_am_buffers), with the
+ * contract of ptmi_hist_update: both in one covariance period (PTMI_EINVAL for a range that crosses one, for n_done < 0, before
+ * ptmi_diag_attach and on a cold handle without an AM buffer); iter_hi < iter_lo: nothing to do; temp0 != 0: PTMI_OK, nothing done.
+ * The caller folds every iteration once, in order, and calls before the ring wraps; the ring is only read.  One thread per stream,
+ * asynchronous on the handle's stream, no host synchronisation, no atomics. */
+int ptmi_diag_attach(ptmi_handle h, double *acc /* dev [2*nlevels+3][W][ndim], caller-owned, caller-zeroed */, int32_t nlevels,
+                     int32_t batch0);
+int ptmi_diag_update(ptmi_handle h, int64_t iter_lo, int64_t iter_hi, int64_t n_done);
+
 /* Self-test hooks used by the parity tests: evaluate the device's deterministic math on
  * n inputs (op: 0 log, 1 exp, 2 cos2pi, 3 sqrt, 4 reciprocal-free divide a/b with b=in2). */
 int ptmi_selftest_math(int device, int op, const double *in, const double *in2, double *out, int64_t n);

@@ -242,6 +242,14 @@ class PTEngine(object):
     against one per iteration.  ``evidence_moments()`` returns the accumulators, ``evidence()`` the estimates (thermodynamic integration,
     its second-order correction, stepping stones; per walker and with standard errors from the walkers' scatter).  lnL is only read:
     the chains are the same bits with and without.  ``t["ev_acc"]``, ``t["ev_cnt"]`` and ``ev_epochs`` are part of ``checkpoint()``.
+    ``with_stages(..., diag=True, diag_from=None, diag_batch=1, diag_levels=16)``: convergence diagnostics from EVERY walker's cold chain
+    (include/ptmi.h ``ptmi_diag_*``, diagnostics.py): per walker and parameter the shifted sums ``S1``, ``S2`` and, over a binary counter of
+    batches of ``diag_batch << l`` iterations, ``l < diag_levels``, the sums of squared batch sums -- streamed on the device from the AM ring
+    for iterations ``diag_from + 1`` on (default ``diag_from = burn``), bit-defined whatever the ring mode.  ``update_cov`` folds the period
+    that ends before it touches anything else; ``diag_sync(it)`` folds up to an iteration inside a period, ``diag_moments(it=None)``
+    returns the planes, ``diagnostics(it=None)`` the estimates: Gelman-Rubin ``rhat``, ``tau`` (batch means pooled over the walkers),
+    ``tau_walkers``, ``ess``.  The ring is only read: the chains are the same bits with and without.  ``t["diag"]`` and ``diag_iter`` are
+    part of ``checkpoint()``.  Refused on an engine that owns no cold ring (``temp0 != 0``).
     ``stats_async`` (pooled covariance with ``eig_lag >= 1``): the statistics of a covariance period that is over need nothing the next
     launches touch once those write ANOTHER ring -- so the engine keeps two rings (``t["AM"]`` is always the one in use), switches at
     every covariance epoch, and runs the period's statistics (``ptmi_update_cov_on``) and the factorization behind them on a side
@@ -259,15 +267,22 @@ class PTEngine(object):
     _ev = False
     _ev_from = None
     _ev_every = 1
+    _diag = False
+    _diag_from = None
+    _diag_batch = None
+    _diag_levels = None
 
     @classmethod
     def with_stages(cls, *args, jumps_with_grad=False, aux=None, logl_in_support=False, hist=None, hist_from=None,
-                    evidence=False, evidence_from=None, evidence_every=1, **kw):
+                    evidence=False, evidence_from=None, evidence_every=1, diag=False, diag_from=None, diag_batch=None, diag_levels=None,
+                    **kw):
         """``PTEngine(*args, **kw)`` with the stages of the composed ``_jump`` on the callback path (see the class docstring):
         ``jumps_with_grad=True`` lets ``jumps=`` stand beside ``grad_weights`` in one cycle, ``aux=[func, ...]`` are the auxiliary jumps,
         ``logl_in_support=True`` hands the likelihood callback only the rows whose prior is not -inf (``eval_callback``),
         ``hist=(lo, hi, nbins)`` with ``hist_from`` accumulates the marginal histograms of every cold chain (``hist_counts``),
-        ``evidence=True`` with ``evidence_from`` / ``evidence_every`` (default 1) the ladder's lnL summaries for ln Z (``evidence``).
+        ``evidence=True`` with ``evidence_from`` / ``evidence_every`` (default 1) the ladder's lnL summaries for ln Z (``evidence``),
+        ``diag=True`` with ``diag_from`` / ``diag_batch`` (default 1) / ``diag_levels`` (default 16) the streaming sums of every cold chain
+        for R-hat and ESS (``diagnostics``).
         The plain constructor keeps the parameters it had (tests/test_gj_groups.py holds them to the letter) and its refusals."""
         self = cls.__new__(cls)
         self.jumps_with_grad = bool(jumps_with_grad)
@@ -275,6 +290,7 @@ class PTEngine(object):
         self.logl_in_support = bool(logl_in_support)
         self._hist, self._hist_from = hist, hist_from
         self._ev, self._ev_from, self._ev_every = bool(evidence), evidence_from, evidence_every
+        self._diag, self._diag_from, self._diag_batch, self._diag_levels = bool(diag), diag_from, diag_batch, diag_levels
         self.__init__(*args, **kw)
         return self
 
@@ -334,6 +350,26 @@ class PTEngine(object):
             self.hist_iter = self.hist_from
         elif self._hist_from is not None:
             raise ValueError("hist_from= goes with hist=(lo, hi, nbins)")
+        # convergence diagnostics of the cold chains (with_stages(diag=True, diag_from=..., diag_batch=..., diag_levels=...); see the class docstring)
+        self.diag_on = bool(self._diag)
+        if self.diag_on:
+            from .diagnostics import MAX_LEVELS
+            b0 = 1 if self._diag_batch is None else self._diag_batch
+            L = MAX_LEVELS if self._diag_levels is None else self._diag_levels
+            if not isinstance(b0, (int, np.integer)) or not 1 <= int(b0) < 2 ** 31:
+                raise ValueError("diag_batch = %r: the level-0 batch length, an integer >= 1" % (b0,))
+            if not isinstance(L, (int, np.integer)) or not 1 <= int(L) <= MAX_LEVELS:
+                raise ValueError("diag_levels = %r: 1 <= diag_levels <= %d" % (L, MAX_LEVELS))
+            if int(temp0) != 0:
+                raise ValueError("diag=True reads the cold chains' ring: this engine (temp0 = %d) holds no rank 0 and owns no cold ring at "
+                                 "all; the stage belongs on the block with temp0 = 0" % int(temp0))
+            self.diag_batch, self.diag_levels = int(b0), int(L)
+            self.diag_from = int(burn) if self._diag_from is None else int(self._diag_from)
+            if self.diag_from < 0:
+                raise ValueError("diag_from = %d: the first iteration folded is diag_from + 1 >= 1" % self.diag_from)
+            self.diag_iter = self.diag_from
+        elif self._diag_from is not None or self._diag_batch is not None or self._diag_levels is not None:
+            raise ValueError("diag_from= / diag_batch= / diag_levels= go with diag=True")
         # the ladder's summaries for the log-evidence (with_stages(evidence=True, evidence_from=..., evidence_every=...); see the class docstring)
         self.evidence_on = bool(self._ev)
         if self.evidence_on:
@@ -546,6 +582,11 @@ class PTEngine(object):
             self.ev_dbeta = np.ascontiguousarray(dbeta_of(self.temps_mh))
             _lib.check(self.lib.ptmi_ev_attach(self.h, C.c_void_p(self.t["ev_acc"].data_ptr()), C.c_void_p(self.t["ev_cnt"].data_ptr()),
                                                self.ev_dbeta.ctypes.data_as(_lib._dp)))
+        if self.diag_on:
+            # double [2 L + 3][W][d] (c, S1, S2, A, Q[0 .. L - 1], H[0 .. L - 2]), plane-major, in parameter order; in self.t: checkpoints
+            # carry it by itself
+            self.t["diag"] = z((2 * self.diag_levels + 3, W, d))
+            _lib.check(self.lib.ptmi_diag_attach(self.h, C.c_void_p(self.t["diag"].data_ptr()), self.diag_levels, self.diag_batch))
         self.de_on = False
         self.de_head = 0
         self.iter = 0
@@ -883,6 +924,8 @@ class PTEngine(object):
             return
         if self.hist_spec is not None:
             self._hist_sync(it_done)                                  # before the statistics, and before stats_async switches rings
+        if self.diag_on:
+            self._diag_sync(it_done)                                  # the same
         # A factorization still pending from the epoch before (eig_lag >= the launches of a period) is finished here at the latest.
         # On the side stream (device factorizations) it goes on BESIDE this epoch's statistics, which do not read the table: they are
         # queued first, the wait for the old table comes behind them -- the same table in force for the same launches either way.
@@ -994,6 +1037,50 @@ class PTEngine(object):
                     edges=hist_edges(lo, hi, nbins), first_iter=np.int64(self.hist_from + 1), last_iter=np.int64(self.hist_iter),
                     nwalkers=np.int64(self.W))
 
+    # ------------------------------------------------------------------ convergence diagnostics
+    def diag_sync(self, it):
+        """Fold iterations ``(diag_iter, it]`` of every walker's cold chain into ``t["diag"]`` (``ptmi_diag_update``: asynchronous, the ring
+        is only read).  ``it`` lies in the covariance period the ring holds; ``update_cov`` calls this at every period's end, so a
+        caller only needs it for sums up to an iteration inside a period.  Nothing to do up to ``diag_from``."""
+        if not self.diag_on:
+            raise ValueError("no diagnostics: PTEngine.with_stages(..., diag=True)")
+        if int(it) > self.iter:
+            raise ValueError("diag_sync(%d): the engine has reached iteration %d; the ring's rows beyond it are the period before's" % (int(it), self.iter))
+        self._diag_sync(it)
+
+    def _diag_sync(self, it):
+        it = int(it)
+        if it <= self.diag_iter:
+            return
+        base = ((it - 1) // self.cov_update) * self.cov_update
+        if self.diag_iter < base:
+            raise ValueError("diag_sync(%d): iterations %d..%d are no longer in the ring (it holds the period after %d); every period "
+                             "must end through update_cov" % (it, self.diag_iter + 1, base, base))
+        _lib.check(self.lib.ptmi_diag_update(self.h, self.diag_iter + 1, it, self.diag_iter - self.diag_from))
+        self.diag_iter = it
+
+    def diag_moments(self, it=None):
+        """The streaming sums up to iteration ``it`` (default: the current one): a dict of the planes ``c``, ``S1``, ``S2``, ``A`` [W][d],
+        ``Q`` [levels][W][d], ``H`` [levels - 1][W][d] (parameter order; include/ptmi.h ``ptmi_diag_attach``), ``n`` (samples per stream),
+        ``k = n // batch0``, ``batch0``, ``levels``, ``first_iter`` / ``last_iter`` (the iterations folded, of every one of ``nwalkers``
+        cold chains)."""
+        from .diagnostics import planes
+        self.diag_sync(self.iter if it is None else it)
+        out = {k: np.ascontiguousarray(v) for k, v in planes(self.t["diag"].cpu().numpy(), self.diag_levels).items()}
+        n = self.diag_iter - self.diag_from
+        out.update(n=np.int64(n), k=np.int64(n // self.diag_batch), batch0=np.int64(self.diag_batch), levels=np.int64(self.diag_levels),
+                   first_iter=np.int64(self.diag_from + 1), last_iter=np.int64(self.diag_iter), nwalkers=np.int64(self.W))
+        return out
+
+    def diagnostics(self, it=None):
+        """R-hat, the autocorrelation times and the effective sample size of every parameter from ALL cold chains up to iteration ``it``
+        (default: the current one): ``diagnostics.estimates(diag_moments(it))`` with ``first_iter`` / ``last_iter``."""
+        from .diagnostics import estimates
+        mom = self.diag_moments(it)
+        out = estimates(mom)
+        out.update(first_iter=mom["first_iter"], last_iter=mom["last_iter"])
+        return out
+
     def update_de(self, it_done=None):
         if self.owns_cold and self.t["DE"] is not None:
             if it_done is not None:
@@ -1023,6 +1110,8 @@ class PTEngine(object):
             st["hist_iter"] = self.hist_iter
         if self.evidence_on:
             st["ev_epochs"] = self.ev_epochs
+        if self.diag_on:
+            st["diag_iter"] = self.diag_iter
         if self.stats_async:
             st.update({"alt_" + k: v.cpu().numpy() for k, v in self._alt.items() if v is not None})
         return st
@@ -1033,6 +1122,10 @@ class PTEngine(object):
             raise ValueError("the checkpoint carries no histogram: it was written by a run without hist=")
         if self.evidence_on and any(k not in st for k in ("ev_epochs", "t_ev_acc", "t_ev_cnt")):
             raise ValueError("the checkpoint carries no evidence accumulators: it was written by a run without evidence=True")
+        if self.diag_on and ("diag_iter" not in st or "t_diag" not in st
+                             or tuple(np.shape(st["t_diag"])) != tuple(self.t["diag"].shape)):
+            raise ValueError("the checkpoint carries no diagnostics sums of this shape: it was written by a run without diag=True (or "
+                             "with other diag_levels)")
         # whatever this engine has under way is void -- and is brought to an end FIRST: a factorization on the side stream (its thread
         # joined, its result dropped), statistics still running beside the launches (stats_async: they write cov / mu / M2)
         if self._eig_pending:
@@ -1060,6 +1153,8 @@ class PTEngine(object):
             self.hist_iter = int(st["hist_iter"])
         if self.evidence_on:
             self.ev_epochs = int(st["ev_epochs"])
+        if self.diag_on:
+            self.diag_iter = int(st["diag_iter"])
         if self.t["DE"] is not None:
             self.set_de_head(int(st["de_head"]))
             if int(st["de_on"]):

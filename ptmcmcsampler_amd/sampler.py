@@ -35,6 +35,15 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
   from the AM ring (``PTEngine.with_stages(hist=...)``): ``<outDir>/hist.npz`` (``counts``, ``under``, ``over``, ``edges``, ``first_iter``,
   ``last_iter``, ``nwalkers``) at every save, ``sampler.hist`` after the run; ``checkpoint=True`` runs resume the counts, a replay of
   chain files cannot;
+* ``sampler.chain_diagnostics = True`` or ``{"batch": b0, "levels": L, "stop_ess": N, "stop_rhat": r}`` (before ``sample()``; any likelihood,
+  any path): Gelman-Rubin R-hat, the integrated autocorrelation time and the effective sample size of every parameter from EVERY
+  walker's cold chain after ``burn`` -- where the ``neff`` rule (PTMCMCSampler.py:510-521) looks at one kept chain.  The device streams the
+  ring into per-walker sums (``PTEngine.with_stages(diag=True)``, csrc/ptmi_diag.hip), ``diagnostics.py`` turns them into ``rhat``,
+  ``tau`` (batch means pooled over the walkers), ``tau_walkers``, ``ess``, ``reliable``: ``<outDir>/diagnostics.npz`` at every save,
+  ``sampler.diagnostics`` after the run.  With ``stop_ess`` / ``stop_rhat`` the run ends at the first save where every parameter is
+  reliable, ``min ess >= N`` and ``max rhat <= r``.  ``rhat`` and ``tau_walkers`` take the walkers as independent replicas (exact with
+  per-walker covariances, weakly coupled under ``cov_mode="pooled"``).  ``checkpoint=True`` runs resume the sums, a replay of chain
+  files cannot; ``neff`` itself is untouched;
 * ``sampler.log_evidence = True`` or ``{"every": k}`` (before ``sample()``; any likelihood, any path; a ladder of at least two
   temperatures): the log-evidence ln Z from the whole ladder of EVERY walker.  Behind every swap after ``burn`` (every k-th with
   ``every``) the device folds the post-swap lnL of every (walker, rank) into per-temperature moments (``PTEngine.with_stages(evidence=True)``,
@@ -157,6 +166,12 @@ class PTSampler(object):
     # after the run.  An attribute for the same reason as batched_aux
     log_evidence = False
     evidence = None
+    # s.chain_diagnostics = True, or {"batch": b0, "levels": L, "stop_ess": N, "stop_rhat": r} (before sample()): R-hat, autocorrelation time
+    # and ESS from EVERY walker's cold chain after burn -- streaming sums on the device (PTEngine.with_stages(diag=True)), estimates in
+    # diagnostics.py: <outDir>/diagnostics.npz at every save, s.diagnostics after the run; with stop_ess / stop_rhat the run ends at the
+    # first save that meets them.  An attribute for the same reason as batched_aux
+    chain_diagnostics = False
+    diagnostics = None
 
     def __init__(self, ndim, logl, logp, cov, groups=None, loglargs=[], loglkwargs={}, logpargs=[], logpkwargs={},
                  logl_grad=None, logp_grad=None, comm=None, outDir="./chains", verbose=True, resume=False, seed=None,
@@ -398,6 +413,11 @@ class PTSampler(object):
             raise NotImplementedError("log_evidence sums the lnL of every walker's whole ladder on the device; chain files hold the kept "
                                       "walkers' thinned rows only, so a replayed run cannot continue the sums: resume from a device checkpoint "
                                       "(PTSampler(..., checkpoint=True) from the first run on)")
+        self._diag_kw()                                               # a bad chain_diagnostics is refused before anything is built
+        if self._replaying and self.chain_diagnostics:
+            raise NotImplementedError("chain_diagnostics sums every walker's cold chain on the device; chain files hold the kept walkers' "
+                                      "thinned rows only, so a replayed run cannot continue the sums: resume from a device checkpoint "
+                                      "(PTSampler(..., checkpoint=True) from the first run on)")
         if self._replaying:
             # PTMCMCSampler.py:290-313: the text rows are all there is (chains the reference wrote, or a run of ours without
             # checkpoints).  In the reference every MPI rank replays its own chain_<T>.txt; here the one process replays
@@ -497,7 +517,7 @@ class PTSampler(object):
             split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
             jumps=[(f, n) for f, n in stage_list] if stage_list else None,
             jumps_with_grad=bool(stage_list) and sum(self._grad_weights) > 0, aux=list(self._batched_aux) or None,
-            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **self._evidence_kw(),
+            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **self._evidence_kw(), **self._diag_kw(),
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     def _evidence_kw(self):
@@ -510,6 +530,27 @@ class PTSampler(object):
         if isinstance(le, dict) and set(le) <= {"every"}:
             return dict(evidence=True, evidence_every=le.get("every", 1))
         raise ValueError('log_evidence is True or {"every": k} (got %r)' % (le,))
+
+    _DIAG_KEYS = ("batch", "levels", "stop_ess", "stop_rhat")
+
+    def _diag_kw(self):
+        """``chain_diagnostics`` -> the keywords of ``PTEngine.with_stages`` (none where it is off; ``diag_from`` is the engine's default,
+        burn), checked; the stop rule's thresholds go to ``self._diag_stop``."""
+        cd = self.chain_diagnostics
+        self._diag_stop = (None, None)
+        if cd is None or cd is False:
+            return {}
+        if cd is True:
+            return dict(diag=True)
+        if not isinstance(cd, dict) or not set(cd) <= set(self._DIAG_KEYS):
+            raise ValueError('chain_diagnostics is True or a dict with keys among %s (got %r)' % (", ".join(self._DIAG_KEYS), cd))
+        ess, rhat = cd.get("stop_ess"), cd.get("stop_rhat")
+        if ess is not None and not float(ess) > 0:
+            raise ValueError("chain_diagnostics: stop_ess = %r is a number of effective samples > 0" % (ess,))
+        if rhat is not None and not float(rhat) > 1.0:
+            raise ValueError("chain_diagnostics: stop_rhat = %r lies above 1 (R-hat tends to 1 from above)" % (rhat,))
+        self._diag_stop = (ess, rhat)
+        return dict(diag=True, diag_batch=cd.get("batch"), diag_levels=cd.get("levels"))
 
     # ------------------------------------------------------------------ sample (:374-528)
     def sample(self, p0, Niter, ladder=None, Tmin=1, Tmax=None, Tskip=100, isave=1000, covUpdate=1000, SCAMweight=20,
@@ -584,6 +625,13 @@ class PTSampler(object):
                 self._harvest_hot(end)
             if end % self.isave == 0:
                 self.writeOutput(end)
+            if eng.diag_on and end % self.isave == 0 and end < self.Niter and self.diagnostics is not None:
+                # the stop rule of chain_diagnostics, from every walker's cold chain (the sums this save has just written)
+                from .diagnostics import converged
+                if converged(self.diagnostics, *self._diag_stop):
+                    message = "\nRun Complete with {0} effective samples and R-hat {1:.4f} over {2} cold chains".format(
+                        int(np.min(self.diagnostics["ess"])), float(np.max(self.diagnostics["rhat"])), self.nwalkers)
+                    self.Niter = end
             if self.neff and end % 1000 == 0 and end > 2 * self.burn:                               # :510-521
                 # acor.acor(chain[burn:iter-1, ii])[0] per dimension, Neff = iter / max(1, nanmax(tau)): with thin = 1 exactly the
                 # reference's expression (ess.acor restates the un-vendored package's published algorithm).  With thin > 1 the
@@ -665,7 +713,9 @@ class PTSampler(object):
                                   + ((("hist", eng.hist_from, eng.hist_spec[2]),) if eng.hist_spec is not None else ()), *groups,
                                   *(eng.hist_spec[:2] if eng.hist_spec is not None else ()),
                                   # (the evidence stage's sampling, only where it is on)
-                                  *((("evidence", eng.evidence_from, eng.evidence_every),) if eng.evidence_on else ())),
+                                  *((("evidence", eng.evidence_from, eng.evidence_every),) if eng.evidence_on else ()),
+                                  # (the diagnostics stage's batches, only where it is on)
+                                  *((("diag", eng.diag_from, eng.diag_batch, eng.diag_levels),) if eng.diag_on else ())),
                            digest(*(spec(self.logl_spec) + spec(self.logp_spec)))], dtype=np.int64)
 
     def _load_checkpoint(self):
@@ -989,7 +1039,24 @@ class PTSampler(object):
         np.savez(tmp, **ev)
         os.replace(tmp, os.path.join(self.outDir, "evidence.npz"))
 
+    def _write_diagnostics(self, iter):
+        """The estimates up to iteration ``iter`` (of the current covariance period), with the sums they come from -> self.diagnostics and
+        <outDir>/diagnostics.npz."""
+        self.engine.iter = max(self.engine.iter, int(iter))          # (the sampler's loops step the engine themselves)
+        mom = self.engine.diag_moments(iter)
+        from .diagnostics import estimates
+        est = estimates(mom)
+        est.update(mom)
+        self.diagnostics = est
+        tmp = os.path.join(self.outDir, "diagnostics.tmp.npz")
+        np.savez(tmp, **est)
+        os.replace(tmp, os.path.join(self.outDir, "diagnostics.npz"))
+
     def writeOutput(self, iter):
+        if self.chain_diagnostics and not self.engine.diag_on:
+            raise ValueError("chain_diagnostics was set after the engine was built: set it before the first sample()")
+        if self.engine.diag_on and iter > self.engine.diag_from:
+            self._write_diagnostics(iter)                             # ahead of the checkpoint: it carries the sums up to here
         if self.log_evidence and not self.engine.evidence_on:
             raise ValueError("log_evidence was set after the engine was built: set it before the first sample()")
         if self.engine.evidence_on and iter > 0:
