@@ -657,6 +657,49 @@ int ptmi_diag_attach(ptmi_handle h, double *acc /* dev [2*nlevels+3][W][ndim], c
                      int32_t batch0);
 int ptmi_diag_update(ptmi_handle h, int64_t iter_lo, int64_t iter_hi, int64_t n_done);
 
+/* The temperature ladder adapted on the device from EVERY walker's accepted swaps (csrc/ptmi_ladder.hip).  The reference's ladder is
+ * fixed (temperatureLadder, :699-720); nswap [W][n] (n = ntemps_global; column k = pair (k, k + 1), credited to the lower rank, :681)
+ * holds what every pair accepted.  State of the whole ladder, with n1 = n - 1 pairs: g[k] = ln T[k + 1] - ln T[k], the log gaps; T[k],
+ * the ladder; seen[k], the accepted swaps of pair k already consumed.  One ptmi_ladder_update(h, kappa, tries_even, tries_odd):
+ *
+ *     acc[k] = sum_w nswap[w][k]                                 uint64, exact
+ *     A[k]   = (double)(acc[k] - seen[k]) / ((double)W * (double)(k even ? tries_even : tries_odd))     k = 0 .. n1 - 1
+ *                                                                (the difference in integers; one product, one division)
+ *     h[k]   = g[k] * exp(kappa * A[k])
+ *     s = 0.0; for k ascending: s = s + h[k]
+ *     G = 0.0; for k ascending: G = G + g[k]
+ *     g'[k]  = G * (h[k] / s)
+ *     c = 0.0; for k = 1 .. n - 2:  c = c + g'[k - 1];  T[k] = T[0] * exp(c)
+ *     seen[k] = acc[k]; g = g'                                   T[0] and T[n - 1] are never rewritten
+ *
+ * every operation rounded on its own, in this order (no fma), exp the library's deterministic exponential (ptmi_selftest_math op 1),
+ * the division IEEE's (op 4).  A pair that accepted more than the others gets a wider gap, the sum of the gaps and both ends of the
+ * ladder stay; only differences of A matter; the fixed point is equal acceptance on every pair.  tries_even / tries_odd: how often
+ * the window tried the pairs with even / odd k (PTMI_SWAP_SWEEP: every swap epoch counts for both; PTMI_SWAP_ODDEVEN: epoch e tries
+ * k = e mod 2).  With two temperatures there is no interior rank: the update writes A and seen only.
+ * The publish step -- ptmi_ladder_publish, and the end of every update -- makes the handle's tables those of plane T:
+ * d_ladder[k] = T[k] (what ptmi_swap reads); for every local rank r that sampled at its ladder entry when ptmi_ladder_attach was
+ * called (temps_mh[r] == ladder[temp0 + r]: not a hot chain at 1e80) temps_mh[r] = T[temp0 + r] and beta[r] = 1.0 / temps_mh[r] (what
+ * every step, split, gradient and callback kernel reads); with ptmi_ev_attach done, dbeta[r] = beta[r - 1] - beta[r] for r >= 1
+ * (dbeta[0] stays).  lnL and lp are stored apart and no tempered value is cached: nothing is re-evaluated, and captured graphs stay valid.
+ * lad: DEVICE double [3][n], planes g, A (of the last window), T; seen: DEVICE uint64 [n]; caller-owned, 8-byte aligned; the caller
+ * fills g and T from its ladder and zeroes A and seen (entry n - 1 of g, A and seen is not used).  A caller that overwrites plane T
+ * (a restored checkpoint, a ladder of its own -- with g to match) calls ptmi_ladder_publish.  ptmi_ladder_attach: once per handle
+ * (it waits for the stream once, to read the tables); a second attach, NULL or misaligned buffers, ntemps_global < 2: PTMI_EINVAL, the
+ * message says which; ntemps != ntemps_global (a sharded ladder: the sums would need a reduction across blocks): PTMI_EUNSUPPORTED.
+ * ptmi_ladder_update refuses (PTMI_EINVAL, nothing launched) before an attach, kappa not finite or outside [0, 8], tries_even < 1, and
+ * tries_odd < 1 with three temperatures or more; ptmi_ladder_publish and ptmi_ladder_read refuse before an attach.  State lives in the
+ * handle: ptmi_config and ptmi_buffers are unchanged, and a handle that never attaches launches what it launched before.
+ * Update (two launches: column sums of the walkers' slabs, read rank-fastest; one finishing block) and publish (one launch) run
+ * asynchronously on the handle's stream: no host synchronisation, no atomics, graph-capturable.  The walker sums are integer sums and
+ * the floating-point part is one sequential pass in ascending k: the result does not depend on the launch geometry.
+ * ptmi_ladder_read copies the handle's tables to HOST memory; it is the one entry point that waits (for the handle's stream). */
+int ptmi_ladder_attach(ptmi_handle h, double *lad /* dev [3][ntemps_global]: planes g, A (last window), T */,
+                       uint64_t *seen /* dev [ntemps_global] */);
+int ptmi_ladder_update(ptmi_handle h, double kappa, int64_t tries_even, int64_t tries_odd);
+int ptmi_ladder_publish(ptmi_handle h);
+int ptmi_ladder_read(ptmi_handle h, double *ladder /* host [ntemps_global] */, double *temps_mh /* host [T] */, double *beta /* host [T] */);
+
 /* Self-test hooks used by the parity tests: evaluate the device's deterministic math on
  * n inputs (op: 0 log, 1 exp, 2 cos2pi, 3 sqrt, 4 reciprocal-free divide a/b with b=in2). */
 int ptmi_selftest_math(int device, int op, const double *in, const double *in2, double *out, int64_t n);

@@ -57,6 +57,7 @@ SYMBOLS = (
     "ptmi_hist_attach", "ptmi_hist_update",
     "ptmi_ev_attach", "ptmi_ev_update",
     "ptmi_diag_attach", "ptmi_diag_update",
+    "ptmi_ladder_attach", "ptmi_ladder_update", "ptmi_ladder_publish", "ptmi_ladder_read",
     "ptmi_am_flags_ok", "ptmi_am_expand", "ptmi_test_replay",
     "ptmi_selftest_math", "ptmi_selftest_philox", "ptmi_malloc", "ptmi_free", "ptmi_memcpy_h2d", "ptmi_memcpy_d2h",
     "ptmi_memset", "ptmi_timer_start", "ptmi_timer_stop_ms",
@@ -146,10 +147,12 @@ def load():
               ptmi_sup_rows=[H, C.c_void_p, C.c_void_p, C.c_void_p], ptmi_sup_end=[H, C.c_void_p, C.c_void_p, C.c_void_p],
               ptmi_hist_attach=[H, C.c_void_p, _dp, _dp, C.c_int32], ptmi_hist_update=[H, C.c_int64, C.c_int64],
               ptmi_ev_attach=[H, C.c_void_p, C.c_void_p, _dp], ptmi_ev_update=[H],
-              ptmi_diag_attach=[H, C.c_void_p, C.c_int32, C.c_int32], ptmi_diag_update=[H, C.c_int64, C.c_int64, C.c_int64])
+              ptmi_diag_attach=[H, C.c_void_p, C.c_int32, C.c_int32], ptmi_diag_update=[H, C.c_int64, C.c_int64, C.c_int64],
+              ptmi_ladder_attach=[H, C.c_void_p, C.c_void_p], ptmi_ladder_update=[H, C.c_double, C.c_int64, C.c_int64],
+              ptmi_ladder_publish=[H], ptmi_ladder_read=[H, _dp, _dp, _dp])
     for n, at in cj.items():
         if SO == os.environ.get("PTMI_LIB") and not hasattr(L, n):
-            continue                                  # an older build for an A/B measurement: no custom-jump, auxiliary, support, histogram, evidence or diagnostics stage (using it raises)
+            continue                                  # an older build for an A/B measurement: no custom-jump, auxiliary, support, histogram, evidence, diagnostics or ladder stage (using it raises)
         getattr(L, n).argtypes = at
     L.ptmi_selftest_math.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     L.ptmi_selftest_philox.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64]

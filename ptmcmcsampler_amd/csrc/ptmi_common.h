@@ -250,6 +250,8 @@ struct ptmi_engine {
     struct ptmi_ev_state *ev;
     // the streaming sums behind R-hat / ESS of the cold chains (ptmi_diag.hip): the state of ptmi_diag_attach, or nullptr
     struct ptmi_diag_state *diag;
+    // the ladder adapted from the walkers' swaps (ptmi_ladder.hip): the state of ptmi_ladder_attach, or nullptr
+    struct ptmi_ladder_state *ladder;
 };
 enum { PTMI_GJ_NONE = 0, PTMI_GJ_PENDING = 1 /* proposals made, ptmi_gj_begin not yet called */, PTMI_GJ_ROUNDS = 2, PTMI_GJ_DONE = 3 };
 // the split path's refusals for gradient jumps (0: served; else the code, with the message set)
@@ -263,8 +265,12 @@ void ptmi_dc_plan_free(ptmi_engine *h);
 void ptmi_hist_free(ptmi_engine *h);
 // log-evidence summaries (ptmi_ev.hip): frees h->ev, for ptmi_destroy
 void ptmi_ev_free(ptmi_engine *h);
+// ... and its device copy of dbeta [T], or nullptr without the stage (ptmi_ladder.hip rewrites it with the ladder)
+double *ptmi_ev_dbeta(ptmi_engine *h);
 // convergence diagnostics (ptmi_diag.hip): frees h->diag, for ptmi_destroy
 void ptmi_diag_free(ptmi_engine *h);
+// ladder adaptation (ptmi_ladder.hip): frees h->ladder, for ptmi_destroy
+void ptmi_ladder_free(ptmi_engine *h);
 // swap (ptmi_swap.hip): bytes of a record of d_pre (SwapPre), for ptmi_create
 constexpr size_t PTMI_SWAP_PRE_BYTES = 48;
 

@@ -76,6 +76,8 @@ void ptmi_ev_free(ptmi_engine *h)
     h->ev = nullptr;
 }
 
+double *ptmi_ev_dbeta(ptmi_engine *h) { return h->ev ? h->ev->d_dbeta : nullptr; }
+
 extern "C" {
 
 int ptmi_ev_attach(ptmi_handle h, double *acc, uint64_t *cnt, const double *dbeta)

@@ -250,6 +250,17 @@ class PTEngine(object):
     returns the planes, ``diagnostics(it=None)`` the estimates: Gelman-Rubin ``rhat``, ``tau`` (batch means pooled over the walkers),
     ``tau_walkers``, ``ess``.  The ring is only read: the chains are the same bits with and without.  ``t["diag"]`` and ``diag_iter`` are
     part of ``checkpoint()``.  Refused on an engine that owns no cold ring (``temp0 != 0``).
+    ``with_stages(..., adapt_ladder=True | dict(every=10, kappa=2.0, t0=10.0, until=None))``: the temperature ladder adapts during burn-in
+    from EVERY walker's accepted swaps (include/ptmi.h ``ptmi_ladder_*``).  ``swap(it)`` counts the swap epochs of a window by the parity
+    of the pairs they try (``swap_mode="oddeven"``: epoch ``it // tskip`` tries the pairs of its parity, so ``every`` is even; the sweep
+    tries all); behind the ``every``-th, while ``it <= until`` (default ``burn``), the device turns the window's acceptance per pair into
+    new log gaps with the gain ``kappa * t0 / (updates so far + t0)`` -- a pair that accepts more than the others gets a wider gap -- and
+    rewrites its temperature tables in place: no host round trip, nothing re-evaluated, captured graphs stay valid.  Both ends of the
+    ladder stay (``Tmax`` keeps its meaning, the evidence integral its range; a ``hot_chain`` rank keeps 1e80).  After ``until`` the
+    ladder is frozen and the run is ordinary parallel tempering: adaptation belongs to burn-in, and with ``evidence=True``
+    ``until <= evidence_from``.  ``ladder`` / ``temps_mh`` / ``ev_dbeta`` show what the device holds (read back on first use after an
+    update), ``ladder0`` / ``temps_mh0`` stay the constructor's; ``ladder_history()`` returns every update.  ``t["lad"]``,
+    ``t["lad_seen"]``, the open window's counts and the history are part of ``checkpoint()``.  One GPU, a whole ladder.
     ``stats_async`` (pooled covariance with ``eig_lag >= 1``): the statistics of a covariance period that is over need nothing the next
     launches touch once those write ANOTHER ring -- so the engine keeps two rings (``t["AM"]`` is always the one in use), switches at
     every covariance epoch, and runs the period's statistics (``ptmi_update_cov_on``) and the factorization behind them on a side
@@ -271,18 +282,40 @@ class PTEngine(object):
     _diag_from = None
     _diag_batch = None
     _diag_levels = None
+    _adapt = None
+    adapt_on = False
+    _lad_stale = False
+
+    # the host's mirrors of the device's temperature tables.  With adapt_ladder the device rewrites them (ptmi_ladder_update): the
+    # mirrors are then read back on their first use after an update (ptmi_ladder_read: one wait for the stream), never per update
+    def _lad_refresh(self):
+        if self._lad_stale:
+            self._lad_stale = False
+            lad, tm, be = np.empty(self.ntg), np.empty(self.nt), np.empty(self.nt)
+            dp = _lib._dp
+            _lib.check(self.lib.ptmi_ladder_read(self.h, lad.ctypes.data_as(dp), tm.ctypes.data_as(dp), be.ctypes.data_as(dp)))
+            self._ladder, self._temps_mh = lad, tm
+            if self.evidence_on:
+                db = self._ev_dbeta.copy()
+                db[1:] = be[:-1] - be[1:]                             # as the publish step writes it; dbeta[0] stays
+                self._ev_dbeta = db
+
+    ladder = property(lambda self: (self._lad_refresh(), self._ladder)[1], lambda self, v: setattr(self, "_ladder", v))
+    temps_mh = property(lambda self: (self._lad_refresh(), self._temps_mh)[1], lambda self, v: setattr(self, "_temps_mh", v))
+    ev_dbeta = property(lambda self: (self._lad_refresh(), self._ev_dbeta)[1], lambda self, v: setattr(self, "_ev_dbeta", v))
 
     @classmethod
     def with_stages(cls, *args, jumps_with_grad=False, aux=None, logl_in_support=False, hist=None, hist_from=None,
                     evidence=False, evidence_from=None, evidence_every=1, diag=False, diag_from=None, diag_batch=None, diag_levels=None,
-                    **kw):
+                    adapt_ladder=None, **kw):
         """``PTEngine(*args, **kw)`` with the stages of the composed ``_jump`` on the callback path (see the class docstring):
         ``jumps_with_grad=True`` lets ``jumps=`` stand beside ``grad_weights`` in one cycle, ``aux=[func, ...]`` are the auxiliary jumps,
         ``logl_in_support=True`` hands the likelihood callback only the rows whose prior is not -inf (``eval_callback``),
         ``hist=(lo, hi, nbins)`` with ``hist_from`` accumulates the marginal histograms of every cold chain (``hist_counts``),
         ``evidence=True`` with ``evidence_from`` / ``evidence_every`` (default 1) the ladder's lnL summaries for ln Z (``evidence``),
         ``diag=True`` with ``diag_from`` / ``diag_batch`` (default 1) / ``diag_levels`` (default 16) the streaming sums of every cold chain
-        for R-hat and ESS (``diagnostics``).
+        for R-hat and ESS (``diagnostics``), ``adapt_ladder=True`` or ``dict(every=10, kappa=2.0, t0=10.0, until=None)`` adapts the
+        temperature ladder during burn-in from every walker's accepted swaps (``ladder_history``).
         The plain constructor keeps the parameters it had (tests/test_gj_groups.py holds them to the letter) and its refusals."""
         self = cls.__new__(cls)
         self.jumps_with_grad = bool(jumps_with_grad)
@@ -291,6 +324,7 @@ class PTEngine(object):
         self._hist, self._hist_from = hist, hist_from
         self._ev, self._ev_from, self._ev_every = bool(evidence), evidence_from, evidence_every
         self._diag, self._diag_from, self._diag_batch, self._diag_levels = bool(diag), diag_from, diag_batch, diag_levels
+        self._adapt = adapt_ladder
         self.__init__(*args, **kw)
         return self
 
@@ -390,6 +424,40 @@ class PTEngine(object):
             self.ev_epochs = 0
         elif self._ev_from is not None or self._ev_every != 1:
             raise ValueError("evidence_from= and evidence_every= go with evidence=True")
+        # the ladder adapted from every walker's swaps (with_stages(adapt_ladder=True | dict(...)); see the class docstring)
+        self.adapt_on = self._adapt is not None and self._adapt is not False
+        if self.adapt_on:
+            ad = {} if self._adapt is True else self._adapt
+            if not isinstance(ad, dict) or not set(ad) <= {"every", "kappa", "t0", "until"}:
+                raise ValueError("adapt_ladder is True or a dict with keys among every, kappa, t0, until (got %r)" % (self._adapt,))
+            every, kappa, t0, until = ad.get("every", 10), ad.get("kappa", 2.0), ad.get("t0", 10.0), ad.get("until")
+            if int(ntemps) < 2:
+                raise ValueError("adapt_ladder needs a ladder: ntemps = %d is one temperature, there is no gap to move" % int(ntemps))
+            if (ntemps_global is not None and int(ntemps_global) != int(ntemps)) or int(temp0) != 0:
+                raise ValueError("adapt_ladder serves a whole ladder on one GPU: on a sharded ladder (ntemps_global / temp0) the pairs' "
+                                 "acceptance would need a reduction across blocks (ShardedPTEngine has no such stage)")
+            if int(tskip) <= 0:
+                raise ValueError("adapt_ladder reads the swaps' acceptance: tskip = %d proposes none" % int(tskip))
+            if not isinstance(every, (int, np.integer)) or int(every) < 1:
+                raise ValueError("adapt_ladder: every = %r swap epochs per window, an integer >= 1" % (every,))
+            if swap_mode == "oddeven" and int(every) % 2:
+                raise ValueError("adapt_ladder: every = %d with swap_mode='oddeven': a window needs as many even as odd swap epochs, "
+                                 "an even number" % int(every))
+            if not isinstance(kappa, (int, float, np.integer, np.floating)) or not np.isfinite(kappa) or not 0.0 <= float(kappa) <= 8.0:
+                raise ValueError("adapt_ladder: kappa = %r, the gain of the first update, lies in [0, 8]" % (kappa,))
+            if not isinstance(t0, (int, float, np.integer, np.floating)) or not np.isfinite(t0) or not float(t0) > 0.0:
+                raise ValueError("adapt_ladder: t0 = %r, the updates after which the gain has halved, is finite and > 0" % (t0,))
+            if until is None:
+                until = int(burn)
+            if not isinstance(until, (int, np.integer)) or int(until) < 0:
+                raise ValueError("adapt_ladder: until = %r, the last iteration at which the ladder may move, an integer >= 0" % (until,))
+            if self.evidence_on and int(until) > self.evidence_from:
+                raise ValueError("adapt_ladder: until = %d lies behind evidence_from = %d: the evidence stage's sums are per temperature, "
+                                 "the ladder must be frozen before the first sample" % (int(until), self.evidence_from))
+            self.adapt_every, self.adapt_kappa, self.adapt_t0, self.adapt_until = int(every), float(kappa), float(t0), int(until)
+            self.lad_calls, self.lad_epochs, self.lad_tries = 0, 0, [0, 0]
+            self._lad_sweep = swap_mode != "oddeven"
+            self._lad_hist = []                                       # per update: (iteration, kappa, the planes [3][n]: device, or host once asked for)
         # rows_logl: the built-in likelihood as a row kernel on the split path (see the class docstring); refused before anything is built
         self.rows_logl = bool(rows_logl)
         if self.rows_logl:
@@ -416,6 +484,7 @@ class PTEngine(object):
         self.temps_mh = self.ladder[self.temp0:self.temp0 + self.nt].copy()
         if hot_chain and self.temp0 + self.nt == self.ntg:
             self.temps_mh[-1] = 1e80                                  # PTMCMCSampler.py:281-282
+        self.ladder0, self.temps_mh0 = self.ladder.copy(), self.temps_mh.copy()      # the constructor's ladder (adapt_ladder moves self.ladder)
         self.cov_update, self.burn, self.tskip, self.seed = int(cov_update), int(burn), int(tskip), int(seed)
         self.weights = tuple(int(w) for w in weights)
         self.per_walker = cov_mode == "per_walker"
@@ -582,6 +651,15 @@ class PTEngine(object):
             self.ev_dbeta = np.ascontiguousarray(dbeta_of(self.temps_mh))
             _lib.check(self.lib.ptmi_ev_attach(self.h, C.c_void_p(self.t["ev_acc"].data_ptr()), C.c_void_p(self.t["ev_cnt"].data_ptr()),
                                                self.ev_dbeta.ctypes.data_as(_lib._dp)))
+        if self.adapt_on:
+            # double [3][n] (log gaps, the last window's acceptance, the ladder) and uint64 [n] (accepted swaps already consumed); in
+            # self.t: checkpoints carry them by themselves
+            lad = np.zeros((3, self.ntg))
+            lad[0, :-1] = np.log(self.ladder0[1:]) - np.log(self.ladder0[:-1])
+            lad[2] = self.ladder0
+            self.t["lad"] = torch.from_numpy(lad).to(self.device)
+            self.t["lad_seen"] = z((self.ntg,), i64)
+            _lib.check(self.lib.ptmi_ladder_attach(self.h, C.c_void_p(self.t["lad"].data_ptr()), C.c_void_p(self.t["lad_seen"].data_ptr())))
         if self.diag_on:
             # double [2 L + 3][W][d] (c, S1, S2, A, Q[0 .. L - 1], H[0 .. L - 2]), plane-major, in parameter order; in self.t: checkpoints
             # carry it by itself
@@ -1112,6 +1190,10 @@ class PTEngine(object):
             st["ev_epochs"] = self.ev_epochs
         if self.diag_on:
             st["diag_iter"] = self.diag_iter
+        if self.adapt_on:
+            hist = self.ladder_history()
+            st.update(lad_calls=self.lad_calls, lad_epochs=self.lad_epochs, lad_tries=np.asarray(self.lad_tries, dtype=np.int64),
+                      lad_hist_iter=hist["iter"], lad_hist_kappa=hist["kappa"], lad_hist_planes=self._lad_planes())
         if self.stats_async:
             st.update({"alt_" + k: v.cpu().numpy() for k, v in self._alt.items() if v is not None})
         return st
@@ -1126,6 +1208,9 @@ class PTEngine(object):
                              or tuple(np.shape(st["t_diag"])) != tuple(self.t["diag"].shape)):
             raise ValueError("the checkpoint carries no diagnostics sums of this shape: it was written by a run without diag=True (or "
                              "with other diag_levels)")
+        if self.adapt_on and any(k not in st for k in ("t_lad", "t_lad_seen", "lad_calls", "lad_epochs", "lad_tries", "lad_hist_iter",
+                                                       "lad_hist_kappa", "lad_hist_planes")):
+            raise ValueError("the checkpoint carries no ladder state: it was written by a run without adapt_ladder")
         # whatever this engine has under way is void -- and is brought to an end FIRST: a factorization on the side stream (its thread
         # joined, its result dropped), statistics still running beside the launches (stats_async: they write cov / mu / M2)
         if self._eig_pending:
@@ -1155,6 +1240,13 @@ class PTEngine(object):
             self.ev_epochs = int(st["ev_epochs"])
         if self.diag_on:
             self.diag_iter = int(st["diag_iter"])
+        if self.adapt_on:
+            self.lad_calls, self.lad_epochs = int(st["lad_calls"]), int(st["lad_epochs"])
+            self.lad_tries = [int(v) for v in st["lad_tries"]]
+            planes = np.asarray(st["lad_hist_planes"], dtype=np.float64).reshape(-1, 3, self.ntg)
+            self._lad_hist = [(int(i), float(k), p.copy()) for i, k, p in zip(st["lad_hist_iter"], st["lad_hist_kappa"], planes)]
+            _lib.check(self.lib.ptmi_ladder_publish(self.h))          # the handle's tables are those of the restored plane T
+            self._lad_stale = True
         if self.t["DE"] is not None:
             self.set_de_head(int(st["de_head"]))
             if int(st["de_on"]):
@@ -1249,6 +1341,37 @@ class PTEngine(object):
         if self.evidence_on and it > self.evidence_from and (it // self.tskip) % self.evidence_every == 0:
             _lib.check(self.lib.ptmi_ev_update(self.h))               # the post-swap lnL of every (walker, rank): one sample
             self.ev_epochs += 1
+        if self.adapt_on and it <= self.adapt_until:
+            # the window counts this epoch by the parity of the pairs it tried (the sweep tries both); `every` epochs in: one update
+            if self._lad_sweep:
+                self.lad_tries[0] += 1
+                self.lad_tries[1] += 1
+            else:
+                self.lad_tries[(it // self.tskip) & 1] += 1
+            self.lad_epochs += 1
+            if self.lad_epochs >= self.adapt_every:
+                kappa = self.adapt_kappa * self.adapt_t0 / (self.lad_calls + self.adapt_t0)
+                _lib.check(self.lib.ptmi_ladder_update(self.h, kappa, self.lad_tries[0], self.lad_tries[1]))
+                self._lad_hist.append((int(it), kappa, self.t["lad"].clone()))      # a device copy: it goes to the host only when asked for
+                self.lad_calls += 1
+                self.lad_epochs, self.lad_tries = 0, [0, 0]
+                self._lad_stale = True
+
+    # ------------------------------------------------------------------ ladder adaptation
+    def _lad_planes(self):
+        """The planes behind every update so far, ``[m][3][n]`` on the host (device copies are brought down once)."""
+        self._lad_hist = [(i, k, p if isinstance(p, np.ndarray) else p.cpu().numpy()) for i, k, p in self._lad_hist]
+        return np.stack([p for _, _, p in self._lad_hist]) if self._lad_hist else np.zeros((0, 3, self.ntg))
+
+    def ladder_history(self):
+        """The updates of ``adapt_ladder`` so far: ``iter [m]`` (the swap iteration each ran behind), ``kappa [m]`` (its gain), ``A [m][n - 1]``
+        (the acceptance of every pair over its window) and ``ladder [m][n]`` (the ladder it left)."""
+        if not self.adapt_on:
+            raise ValueError("no ladder adaptation: PTEngine.with_stages(..., adapt_ladder=True)")
+        planes = self._lad_planes()
+        return dict(iter=np.asarray([i for i, _, _ in self._lad_hist], dtype=np.int64),
+                    kappa=np.asarray([k for _, k, _ in self._lad_hist], dtype=np.float64),
+                    A=planes[:, 1, :-1].copy(), ladder=planes[:, 2, :].copy())
 
     # ------------------------------------------------------------------ log-evidence
     def evidence_moments(self):

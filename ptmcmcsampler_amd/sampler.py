@@ -53,6 +53,17 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
   ``*_sem`` from the walkers' scatter, ``mean`` / ``var`` of lnL per rank, ``beta_min`` (the range below the hottest beta is not
   integrated: run with ``hotChain=True`` to reach the prior), and the moments themselves (``evidence.py``); ``checkpoint=True`` runs
   resume the accumulators, a replay of chain files cannot;
+* ``sampler.adapt_ladder = True`` or ``{"every": 10, "kappa": 2.0, "t0": 10.0, "until": None}`` (before ``sample()``; any likelihood, any
+  path; a ladder of at least two temperatures): the temperature ladder adapts during burn-in from EVERY walker's accepted swaps
+  (``PTEngine.with_stages(adapt_ladder=...)``, csrc/ptmi_ladder.hip) -- where the reference keeps the geometric guess of
+  ``temperatureLadder`` (:699-720).  Every ``every`` swap epochs up to iteration ``until`` (default ``burn``) a pair that accepts more
+  than the others gets a wider gap; both ends of the ladder stay; afterwards the ladder is frozen and the run is ordinary parallel
+  tempering.  ``sampler.ladder_adapted`` after the run and ``<outDir>/ladder.npz`` at every save: ``ladder``, ``ladder0``, ``until`` and
+  the history of the updates (``iter``, ``kappa``, ``A``, ``history``).  Chain file names (``chain_<T>.txt``), ``sampler.ladder`` and the
+  checkpoint's fingerprint keep the INITIAL ladder's temperatures -- a file stays the file of its rank, and a resumed run is recognised
+  by the ladder it was started with; the ``lnprob`` column of the hot-chain files uses the temperatures in force.  With
+  ``log_evidence`` the ladder must be frozen before the first sample (``until <= burn``); ``checkpoint=True`` runs resume the ladder and
+  its open window, a replay of chain files cannot;
 * engine options: ``cov_mode="pooled"`` (one covariance adapted from all walkers instead of one per walker),
   ``swap_mode="oddeven"`` (disjoint swap pairs instead of the reference's hot -> cold sweep), ``pick_mode="walker"`` (one
   proposal-type draw per walker and iteration), ``eig_mode="ql"`` / ``"jacobi"`` / ``"sytrd"`` / ``"hipsolver"`` (covariance epochs factorized on the device: per-walker matrices by
@@ -172,6 +183,11 @@ class PTSampler(object):
     # first save that meets them.  An attribute for the same reason as batched_aux
     chain_diagnostics = False
     diagnostics = None
+    # s.adapt_ladder = True, or {"every": e, "kappa": k, "t0": t, "until": it} (before sample()): the ladder adapts during burn-in from every
+    # walker's accepted swaps, on the device (PTEngine.with_stages(adapt_ladder=...)): <outDir>/ladder.npz at every save, s.ladder_adapted
+    # after the run.  An attribute for the same reason as batched_aux
+    adapt_ladder = False
+    ladder_adapted = None
 
     def __init__(self, ndim, logl, logp, cov, groups=None, loglargs=[], loglkwargs={}, logpargs=[], logpkwargs={},
                  logl_grad=None, logp_grad=None, comm=None, outDir="./chains", verbose=True, resume=False, seed=None,
@@ -413,6 +429,10 @@ class PTSampler(object):
             raise NotImplementedError("log_evidence sums the lnL of every walker's whole ladder on the device; chain files hold the kept "
                                       "walkers' thinned rows only, so a replayed run cannot continue the sums: resume from a device checkpoint "
                                       "(PTSampler(..., checkpoint=True) from the first run on)")
+        if self._replaying and self._adapt_kw():
+            raise NotImplementedError("adapt_ladder keeps the ladder and its open window on the device; chain files hold neither, so a "
+                                      "replayed run cannot continue them: resume from a device checkpoint (PTSampler(..., checkpoint=True) "
+                                      "from the first run on)")
         self._diag_kw()                                               # a bad chain_diagnostics is refused before anything is built
         if self._replaying and self.chain_diagnostics:
             raise NotImplementedError("chain_diagnostics sums every walker's cold chain on the device; chain files hold the kept walkers' "
@@ -517,7 +537,7 @@ class PTSampler(object):
             split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
             jumps=[(f, n) for f, n in stage_list] if stage_list else None,
             jumps_with_grad=bool(stage_list) and sum(self._grad_weights) > 0, aux=list(self._batched_aux) or None,
-            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **self._evidence_kw(), **self._diag_kw(),
+            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **self._evidence_kw(), **self._diag_kw(), **self._adapt_kw(),
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     def _evidence_kw(self):
@@ -530,6 +550,15 @@ class PTSampler(object):
         if isinstance(le, dict) and set(le) <= {"every"}:
             return dict(evidence=True, evidence_every=le.get("every", 1))
         raise ValueError('log_evidence is True or {"every": k} (got %r)' % (le,))
+
+    def _adapt_kw(self):
+        """``adapt_ladder`` -> the keyword of ``PTEngine.with_stages`` (none where it is off; the engine checks the values)."""
+        al = self.adapt_ladder
+        if al is None or al is False:
+            return {}
+        if al is True or (isinstance(al, dict) and set(al) <= {"every", "kappa", "t0", "until"}):
+            return dict(adapt_ladder=True if al is True else dict(al))
+        raise ValueError('adapt_ladder is True or a dict with keys among every, kappa, t0, until (got %r)' % (al,))
 
     _DIAG_KEYS = ("batch", "levels", "stop_ess", "stop_rhat")
 
@@ -702,7 +731,7 @@ class PTSampler(object):
         groups = [np.asarray(g, dtype=np.int64) for g in self.groups]
         return np.asarray([self.seed & 0x7FFFFFFFFFFFFFFF, self.ndim, self.nchain, self.nwalkers, self.thin, self.covUpdate, self.burn,
                            eng.de_ld, eng.de_epl, self.keep_walkers, eng.am_epl,
-                           digest(np.asarray(eng.ladder, dtype=np.float64), np.asarray(eng.temps_mh, dtype=np.float64)), self.Tskip,
+                           digest(np.asarray(eng.ladder0, dtype=np.float64), np.asarray(eng.temps_mh0, dtype=np.float64)), self.Tskip,      # (the ladder the run STARTED with: adapt_ladder moves eng.ladder)
                            digest((self.SCAMweight, self.AMweight, self.DEweight) + tuple(self._grad_weights) + (len(self.host_jumps),)
                                   + ((tuple(f.__name__ for f in self.host_jumps),) if getattr(self, "_stage_jumps", False) else ())
                                   # (batched auxiliary jumps by name, only where there are some: the other runs' fingerprints stay what they were)
@@ -715,7 +744,9 @@ class PTSampler(object):
                                   # (the evidence stage's sampling, only where it is on)
                                   *((("evidence", eng.evidence_from, eng.evidence_every),) if eng.evidence_on else ()),
                                   # (the diagnostics stage's batches, only where it is on)
-                                  *((("diag", eng.diag_from, eng.diag_batch, eng.diag_levels),) if eng.diag_on else ())),
+                                  *((("diag", eng.diag_from, eng.diag_batch, eng.diag_levels),) if eng.diag_on else ()),
+                                  # (the ladder's adaptation, only where it is on)
+                                  *((("adapt", eng.adapt_every, eng.adapt_kappa, eng.adapt_t0, eng.adapt_until),) if eng.adapt_on else ())),
                            digest(*(spec(self.logl_spec) + spec(self.logp_spec)))], dtype=np.int64)
 
     def _load_checkpoint(self):
@@ -1039,6 +1070,17 @@ class PTSampler(object):
         np.savez(tmp, **ev)
         os.replace(tmp, os.path.join(self.outDir, "evidence.npz"))
 
+    def _write_ladder(self):
+        """The ladder in force, the one the run started with and every update so far -> self.ladder_adapted and <outDir>/ladder.npz."""
+        eng = self.engine
+        hist = eng.ladder_history()
+        la = dict(ladder=np.array(eng.ladder), ladder0=np.array(eng.ladder0), until=np.int64(eng.adapt_until), iter=hist["iter"],
+                  kappa=hist["kappa"], A=hist["A"], history=hist["ladder"])
+        self.ladder_adapted = la
+        tmp = os.path.join(self.outDir, "ladder.tmp.npz")
+        np.savez(tmp, **la)
+        os.replace(tmp, os.path.join(self.outDir, "ladder.npz"))
+
     def _write_diagnostics(self, iter):
         """The estimates up to iteration ``iter`` (of the current covariance period), with the sums they come from -> self.diagnostics and
         <outDir>/diagnostics.npz."""
@@ -1061,6 +1103,10 @@ class PTSampler(object):
             raise ValueError("log_evidence was set after the engine was built: set it before the first sample()")
         if self.engine.evidence_on and iter > 0:
             self._write_evidence()                                    # ahead of the checkpoint: it carries the sums up to here
+        if self.adapt_ladder and not self.engine.adapt_on:
+            raise ValueError("adapt_ladder was set after the engine was built: set it before the first sample()")
+        if self.engine.adapt_on:
+            self._write_ladder()
         if self.posterior_hist is not None and self.engine.hist_spec is None:
             raise ValueError("posterior_hist was set after the engine was built: set it before the first sample()")
         if self.engine.hist_spec is not None and iter > 0:

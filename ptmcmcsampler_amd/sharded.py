@@ -138,6 +138,10 @@ class ShardedPTEngine(object):
     """One ladder of ``ntemps_global`` ranks sharded over ``group``; same interface as PTEngine."""
 
     def __init__(self, ndim, ntemps_global, nwalkers, cov0, group=None, local_factory=None, comm=None, **kw):
+        if kw.get("adapt_ladder") not in (None, False):
+            # (PTEngine.with_stages(adapt_ladder=...): the pairs' acceptance is summed on one GPU -- refused before anything is set up)
+            raise ValueError("adapt_ladder serves a whole ladder on one GPU: a sharded ladder would need the pairs' acceptance reduced "
+                             "across blocks (ShardedPTEngine has no such stage)")
         torch = _torch()
         self.comm = comm if comm is not None else DistComm(group)
         self.rank, self.world = self.comm.rank, self.comm.world
