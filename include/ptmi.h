@@ -233,6 +233,23 @@ enum { PTMI_VAR_STAGED = 1,    /* strided lane layout, tables in LDS, products o
                                  * draw), the direction read from the library's zero-padded copy of the table -- what bench.py --ndim 1000 times */ };
 int ptmi_last_mh_variant(ptmi_handle h, int32_t *variant);
 
+/* What the most recent gradient-jump launch of ptmi_mh_steps was (PTMI_VAR_GRADJUMP says no more than that there was one): all
+ * layouts of the kernel give the same results, so only this report tells a test which one it ran.  `layout` is one of
+ * PTMI_GJL_WAVE .. PTMI_GJL_CHAIN or-ed with the flags behind them, `lds_levels` the heights of the NUTS tree stack kept in LDS,
+ * `lds_bytes` the dynamic LDS of a block, `nslots` the chain slots of the launch (with the launch order: the chains, the empty
+ * slots beside the chains that have a wave of their own, and the last wave's padding).  All four are 0 before the first such launch. */
+enum { PTMI_GJL_WAVE = 1,      /* a jump takes the whole wave, one chain at a time: the 4-lane shapes */
+       PTMI_GJL_PAIR = 2,      /* 4-lane shapes, diagonal whitening, no dense likelihood: two jumps at a time, a half-wave each */
+       PTMI_GJL_W16 = 3,       /* the 16-lane shape at ndim <= 64: a jump takes the whole wave, one element per lane */
+       PTMI_GJL_CHAIN = 4,     /* a jump runs in the chain's own 16 or 64 lanes */
+       PTMI_GJL_LAYOUT_MASK = 15,
+       PTMI_GJL_DIAG = 16,     /* the whitening tables are diagonal */
+       PTMI_GJL_GRP = 32,      /* the instantiation for parameter groups */
+       PTMI_GJL_BOX_LDS = 64,  /* box prior: the bounds table sits behind the layout's other tables in LDS */
+       PTMI_GJL_ORDERED = 128, /* chains dealt over the waves by NUTS step size (cycles with NUTS) */
+       PTMI_GJL_AM_AHEAD = 256 /* the launch was a piece behind the matrix product that computes its AM increments */ };
+int ptmi_last_gj_launch(ptmi_handle h, int32_t *layout, int32_t *lds_levels, int32_t *lds_bytes, int32_t *nslots);
+
 /* PTswap (:631-697) for iteration `iter` when the whole ladder is on this GPU. */
 int ptmi_swap(ptmi_handle h, int64_t iter);
 

@@ -1650,6 +1650,7 @@ int ptmi_mh_steps(ptmi_handle h, int64_t iter0, int32_t nsteps)
         }
         if (int rc = run_shape(h, PTMI_OP_MH_GJ, a, chains_grid(h), true)) return rc;
         h->last_variant = PTMI_VAR_GRADJUMP | PTMI_VAR_FULL;
+        if (a.gj_order) h->gj_last[0] |= PTMI_GJL_ORDERED;
         return PTMI_OK;
     };
     if (gjc && h->am_piece <= 0) {
@@ -1676,6 +1677,7 @@ int ptmi_mh_steps(ptmi_handle h, int64_t iter0, int32_t nsteps)
             ap.UtPad = a.UtPad; ap.ut_pad_ld = a.ut_pad_ld; ap.ut_absmax = a.ut_absmax;
             if (gjc) {                                                   // (the gradient-jump kernel reads its AM increments the same way)
                 if (int rc = launch_gj(ap)) return rc;
+                h->gj_last[0] |= PTMI_GJL_AM_AHEAD;
                 continue;
             }
             if (int rc = run_shape(h, PTMI_OP_MH, ap, grid, full)) return rc;
@@ -1693,6 +1695,13 @@ int ptmi_last_mh_variant(ptmi_handle h, int32_t *variant)
     if (!h || !variant) return fail(PTMI_EINVAL, "NULL argument");
     *variant = h->last_variant | ((h->cfg.pick_mode == PTMI_PICK_WALKER && (h->last_variant & PTMI_VAR_FULL)) ? PTMI_VAR_UNIFORM : 0) |
                (h->G << 12) | (h->EPL << 20);
+    return PTMI_OK;
+}
+
+int ptmi_last_gj_launch(ptmi_handle h, int32_t *layout, int32_t *lds_levels, int32_t *lds_bytes, int32_t *nslots)
+{
+    if (!h || !layout || !lds_levels || !lds_bytes || !nslots) return fail(PTMI_EINVAL, "NULL argument");
+    *layout = h->gj_last[0]; *lds_levels = h->gj_last[1]; *lds_bytes = h->gj_last[2]; *nslots = h->gj_last[3];
     return PTMI_OK;
 }
 

@@ -197,6 +197,7 @@ struct ptmi_engine {
     int G, EPL;
     int de_on, de_head;
     int last_variant;   // PTMI_VAR_* flags of the most recent fused-MH launch (ptmi_last_mh_variant)
+    int gj_last[4];     // PTMI_GJL_* layout | flags, LDS levels, LDS bytes, chain slots of the most recent gradient-jump launch (ptmi_last_gj_launch)
     hipEvent_t ev0, ev1;
     hipStream_t side;            // pooled statistics at ndim > 111: the diagonal macro tiles run beside the off-diagonal ones
     hipEvent_t side_go, side_done;

@@ -78,6 +78,11 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
             off = (off + 1) & ~(size_t)1;
             a.box_off = box ? (int)off : -1;
             off += box;
+            // what ptmi_last_gj_launch reports: the layout launched below, its tables, the stack levels and bytes of LDS, the chain slots
+            auto note = [&](int layout) {
+                h->gj_last[0] = layout | (a.gj_diag ? PTMI_GJL_DIAG : 0) | (a.box_off >= 0 ? PTMI_GJL_BOX_LDS : 0);
+                h->gj_last[1] = a.gj_lds_levels; h->gj_last[2] = (int)(sizeof(double) * off); h->gj_last[3] = (int)nch;
+            };
             if constexpr (G == 4 && L != PTMI_LOGL_DENSE) {
                 if (pair) {
                     if (sizeof(double) * off > 64 * 1024) {
@@ -85,6 +90,7 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
                         if (e != hipSuccess) return fail(PTMI_EHIP, "hipFuncSetAttribute(%zu B of LDS): %s", sizeof(double) * off, hipGetErrorString(e));
                     }
                     hipLaunchKernelGGL((mh_steps_gj_kernel<G, E, L, true>), dim3((unsigned)((nch + cpb - 1) / cpb)), dim3(GJ_BLOCK), sizeof(double) * off, h->stream, a);
+                    note(PTMI_GJL_PAIR);
                     return PTMI_OK;
                 }
             }
@@ -92,6 +98,7 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
                 if (w16) {
                     if (a.gj_diag) hipLaunchKernelGGL((mh_steps_gj_kernel<G, E, L, false, 1>), dim3((unsigned)((nch + cpb - 1) / cpb)), dim3(GJ_BLOCK), sizeof(double) * off, h->stream, a);
                     else hipLaunchKernelGGL((mh_steps_gj_kernel<G, E, L, false, 2>), dim3((unsigned)((nch + cpb - 1) / cpb)), dim3(GJ_BLOCK), sizeof(double) * off, h->stream, a);
+                    note(PTMI_GJL_W16);
                     return PTMI_OK;
                 }
             }
@@ -103,6 +110,7 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
                         if (e != hipSuccess) return fail(PTMI_EHIP, "hipFuncSetAttribute(%zu B of LDS): %s", sizeof(double) * off, hipGetErrorString(e));
                     }
                     hipLaunchKernelGGL(kern, dim3((unsigned)((nch + cpb - 1) / cpb)), dim3(GJ_BLOCK), sizeof(double) * off, h->stream, a);
+                    note((G == 4 ? PTMI_GJL_WAVE : PTMI_GJL_CHAIN) | PTMI_GJL_GRP);
                     return PTMI_OK;
                 }
             }
@@ -113,6 +121,7 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
             }
             hipLaunchKernelGGL((mh_steps_gj_kernel<G, E, L>), dim3((unsigned)((nch + cpb - 1) / cpb)), dim3(GJ_BLOCK),
                                sizeof(double) * off, h->stream, a);
+            note(G == 4 ? PTMI_GJL_WAVE : PTMI_GJL_CHAIN);
             return PTMI_OK;
         } else {
             return fail(PTMI_EUNSUPPORTED, "gradient jumps are built for kernel shapes with at most 8 register slots per lane");

@@ -1334,6 +1334,13 @@ class PTEngine(object):
         _lib.check(self.lib.ptmi_last_mh_variant(self.h, C.byref(v)))
         return (v.value & 0xFFF) | (v.value & _lib.VAR_UTPAD), (v.value >> 12) & 0xFF, (v.value >> 20) & 0xFF
 
+    def last_gj_launch(self):
+        """(layout | flags, LDS levels of the tree stack, dynamic LDS bytes, chain slots) of the last gradient-jump launch of ``mh_steps``
+        (``_lib.GJL_*``; ``ptmi_last_gj_launch``): all zero before the first one."""
+        v = [C.c_int32(0) for _ in range(4)]
+        _lib.check(self.lib.ptmi_last_gj_launch(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def swap(self, it):
         """PT swap of iteration ``it`` with the whole ladder on this GPU (:631-697)."""
         _lib.check(self.lib.ptmi_swap(self.h, it))

@@ -65,6 +65,33 @@ def test_variant_flags_match_the_header(lib):
         assert getattr(lib, n) == v, n
 
 
+def test_gj_launch_report_matches_the_header(lib):
+    """ptmi_last_gj_launch: the PTMI_GJL_* layouts and flags the gradient-jump matrix asserts on are the header's, the layouts fit
+    under the mask, the flags are distinct bits above it; the symbol is declared with four int32 outputs, bound with them, and
+    refuses NULL arguments without touching a device."""
+    import ctypes as C
+    hdr = open(os.path.join(ROOT, "include", "ptmi.h")).read()
+    vals = {n: int(v) for n, v in re.findall(r"\bPTMI_(GJL_[A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    assert vals == dict(GJL_WAVE=1, GJL_PAIR=2, GJL_W16=3, GJL_CHAIN=4, GJL_LAYOUT_MASK=15, GJL_DIAG=16, GJL_GRP=32, GJL_BOX_LDS=64,
+                        GJL_ORDERED=128, GJL_AM_AHEAD=256)
+    for n, v in vals.items():
+        assert getattr(lib, n) == v, n
+    flags = sorted(v for n, v in vals.items() if v > vals["GJL_LAYOUT_MASK"])
+    assert flags == [16 << k for k in range(len(flags))]
+    assert all(v & ~vals["GJL_LAYOUT_MASK"] == 0 for n, v in vals.items() if v < 16)
+    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert re.search(r"\bint\s+ptmi_last_gj_launch\s*\(\s*ptmi_handle\s+h\s*,\s*int32_t\s*\*\s*layout\s*,\s*int32_t\s*\*\s*lds_levels\s*,"
+                     r"\s*int32_t\s*\*\s*lds_bytes\s*,\s*int32_t\s*\*\s*nslots\s*\)\s*;", plain)
+    L = lib.load()
+    assert "ptmi_last_gj_launch" in lib.SYMBOLS
+    assert L.ptmi_last_gj_launch.argtypes == [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
+    # ptmi_last_mh_variant keeps its bits: no gradient-jump layout went into its twelve low bits or the shape bits
+    assert not re.search(r"PTMI_VAR_GJ|PTMI_VAR_[A-Z_]*LAYOUT", hdr)
+    out = [C.c_int32(7) for _ in range(4)]
+    assert L.ptmi_last_gj_launch(None, *[C.byref(v) for v in out]) != 0 and "NULL" in L.ptmi_last_error().decode()
+    assert [v.value for v in out] == [7] * 4
+
+
 def test_no_cpu_fallback(lib):
     """Without a device the product path refuses to run instead of computing on the host."""
     import numpy as np

@@ -118,6 +118,16 @@ def test_fused_kernels_equal_the_oracle(mods, name):
         _compare_all(g, snap, "%s fused it=%d " % (name, g.iter))
     flags, lanes, _ = g.last_variant()
     assert flags & _lib.VAR_GRADJUMP and lanes == _lib.lanes_for(d, grad=True)
+    # the GRP instantiation ran, in the one layout of its lane width -- also for the handles that would take the pair layout
+    # (curved20_box_diag) or the wide-16 one (dense40_diag) without groups; with an AM entry behind am_prepare's pieces
+    layout, levels, nbytes, nslots = g.last_gj_launch()
+    diag = not np.count_nonzero(cov0 - np.diag(np.diag(cov0)))        # (curved20_box starts from the identity: diagonal tables too)
+    want = ((_lib.GJL_WAVE if lanes == 4 else _lib.GJL_CHAIN) | _lib.GJL_GRP | (_lib.GJL_DIAG if diag else 0) |
+            (_lib.GJL_BOX_LDS if kw.get("logp", ("flat",))[0] == "box" else 0) | (_lib.GJL_ORDERED if kw["grad_weights"][0] else 0) |
+            (_lib.GJL_AM_AHEAD if kw["weights"][1] else 0))
+    assert layout == want, "%s launched 0x%x, the case means 0x%x" % (name, layout, want)
+    cpw = 64 // lanes
+    assert nslots == (-(-(nt * W) // cpw) * cpw if kw["grad_weights"][0] else nt * W) and levels >= 1 and nbytes > 0
 
 
 @pytest.mark.parametrize("name", CALLBACK_CASES)

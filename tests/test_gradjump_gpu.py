@@ -84,6 +84,31 @@ def _case_id(c):
                              "-diag" if c.get("diag") else "", ("" if sum(c["grad_weights"]) else "-nogj") + ("-nowide16" if c.get("nowide16") else "") + ("-solo%d" % c["solo"] if "solo" in c else "") + ("-" + c["cov_mode"] if "cov_mode" in c else "") + ("-pieces" if "am_budget" in c else ""))
 
 
+def _expected_layout(case):
+    """PTMI_GJL_* layout | flags of a case's launches (csrc/ptmi_shape.hip, PTMI_OP_MH_GJ): what the comments of CASES claim."""
+    from ptmcmcsampler_amd import _lib
+    d, diag, dense = case["d"], bool(case.get("diag")), case["logl"][0] == "dense"
+    G = _lib.lanes_for(d, grad=True)
+    if G == 4:
+        layout = _lib.GJL_PAIR if (diag and not dense and d != 7) else _lib.GJL_WAVE      # (d = 7: PTMI_GJ_NOPAIR)
+    else:
+        layout = _lib.GJL_W16 if (G == 16 and d <= 64 and not case.get("nowide16")) else _lib.GJL_CHAIN
+    return (layout | (_lib.GJL_DIAG if diag else 0) | (_lib.GJL_BOX_LDS if case["logp"][0] == "box" else 0) |
+            (_lib.GJL_ORDERED if case["grad_weights"][0] else 0) | (_lib.GJL_AM_AHEAD if (case["weights"][1] and G > 4) else 0))
+
+
+def test_the_cases_name_the_layouts_their_comments_claim():
+    """The layouts by case id, spelled out once (no GPU needed to read it; the run asserts them through last_gj_launch)."""
+    from ptmcmcsampler_amd import _lib
+    by = {_case_id(c): _expected_layout(c) & _lib.GJL_LAYOUT_MASK for c in CASES if sum(c["grad_weights"])}
+    assert len(by) == sum(1 for c in CASES if sum(c["grad_weights"]))
+    assert by["d20-curved-diag"] == by["d8-interval-diag"] == by["d20-curved-diag-solo5"] == by["d8-interval-diag-solo0"] == _lib.GJL_PAIR
+    assert by["d7-iso-diag"] == by["d5-iso"] == by["d32-iso"] == by["d5-iso-solo9"] == by["d20-interval"] == _lib.GJL_WAVE
+    assert by["d40-interval-diag"] == by["d33-iso-diag"] == by["d64-iso-diag"] == by["d34-curved-diag"] == by["d50-iso-cap2-diag"] == _lib.GJL_W16
+    assert by["d40-dense"] == by["d40-dense-solo6"] == by["d40-interval-diag-pooled-pieces"] == _lib.GJL_W16
+    assert by["d40-interval-diag-nowide16"] == by["d100-iso"] == by["d150-iso"] == by["d130-interval-diag"] == by["d100-iso-pooled-pieces"] == _lib.GJL_CHAIN
+
+
 @pytest.mark.parametrize("case", CASES, ids=_case_id)
 def test_device_gradient_jumps_bit_exact(case, monkeypatch):
     c = dict(case)
@@ -124,6 +149,23 @@ def test_device_gradient_jumps_bit_exact(case, monkeypatch):
         _same(g.get(name), getattr(o, name), name)
     if sum(c["grad_weights"]):
         _same(g.get("gj"), o.gj, "gradient-jump state")
+    # the layout the case's comment names is the one that launched (all layouts give the same bits), with the chain slots its launch
+    # order makes and the tree-stack levels the hook leaves in LDS
+    import os
+    from ptmcmcsampler_amd import _lib
+    layout, levels, nbytes, nslots = g.last_gj_launch()
+    if sum(c["grad_weights"]):
+        assert layout == _expected_layout(case), "launched 0x%x, the case means 0x%x" % (layout, _expected_layout(case))
+        cpw, nch = 64 // _lib.lanes_for(d, grad=True), nt * W
+        solo = min(case.get("solo", nch // 32), nch) if cpw > 1 else 0
+        assert nslots == (solo * cpw + -(-(nch - solo) // cpw) * cpw if c["grad_weights"][0] else nch)
+        assert nbytes > 0 and levels >= 1
+        if os.environ.get("PTMI_GJ_LDS_LEVELS") == "1":
+            assert levels == 1
+        elif layout & _lib.GJL_LAYOUT_MASK != _lib.GJL_CHAIN:
+            assert levels == min(c.get("nuts_maxdepth", 24) + 1, 11)
+    else:
+        assert (layout, levels, nbytes, nslots) == (0, 0, 0, 0)
     js = o.jstat.sum(axis=(0, 1))
     if c["grad_weights"][0]:
         assert js[3, 0] > 0 and js[3, 0] == js[3, 1], "NUTS proposals are always accepted (NJ:838)"

@@ -8,7 +8,9 @@ the oracle; this file holds the table both share, the flags ``ptmi_last_mh_varia
 cases.  To add a shape: put its ndim into ``NDIM`` (even, and with the last slot of lanes 2 and 3 empty where the shape allows
 it); the table grows by itself, ``test_every_cell_has_exactly_one_case`` then passes again, and the GPU file runs the new cells.
 
-Families: family 3 (interval) and the gradient-jump kernels are tests/test_gradjump_gpu.py's."""
+Families: family 3 (interval) and the gradient-jump kernels have a matrix and a ledger of their own, tests/test_gj_variants.py with
+tests/test_gj_variants_gpu.py (every shape of PTMI_GJ_SHAPE_LIST x family x layout x tables x prior, the layout asserted through
+ptmi_last_gj_launch); tests/test_gradjump_gpu.py and tests/test_gj_groups_gpu.py hold the single cases that grew before it."""
 import collections
 import os
 import re
