@@ -219,7 +219,7 @@ def welford(AM, mu, M2, it, fused=False):
 
 
 def pool_slab(nwalkers, ndim):
-    """Walkers per slab of the pooled statistics (the engine's rule, ptmi_abi.hip pool_slab): up to 512 slabs for the
+    """Walkers per slab of the pooled statistics (the engine's rule, ptmi_cov.hip pool_slab): up to 512 slabs for the
     one-macro-tile shapes (ndim <= 111), up to 32 beyond (a slab's partial matrix is ndim x (ndim + 1) doubles)."""
     target = 512 if ndim + 1 <= 112 else 32
     return max(1, -(-nwalkers // target))

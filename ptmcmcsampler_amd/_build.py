@@ -85,6 +85,8 @@ def build(force=False, verbose=False, jobs=None):
             (os.path.join(CSRC, "ptmi_eig.hip"), os.path.join(OBJ, "eig.o"), []),             # the device eigensolvers ("jacobi", "ql", "sytrd")
             (os.path.join(CSRC, "ptmi_eig_wide.hip"), os.path.join(OBJ, "eig_wide.o"), []),   # ... "ql" beyond 128 x 128: the matrix in a global scratch
             (os.path.join(CSRC, "ptmi_swap.hip"), os.path.join(OBJ, "swap.o"), []),           # the PT swap and the block-edge exchange
+            (os.path.join(CSRC, "ptmi_cov.hip"), os.path.join(OBJ, "cov.o"), []),             # the covariance epoch: Welford / pooled statistics, AM and DE rings
+            (os.path.join(CSRC, "ptmi_am_ahead.hip"), os.path.join(OBJ, "am_ahead.o"), []),   # the AM increments computed on the matrix cores ahead of a launch
             (os.path.join(CSRC, "ptmi_split.hip"), os.path.join(OBJ, "split.o"), []),         # the split path's row kernels (shape-independent)
             (os.path.join(CSRC, "ptmi_gjcb.hip"), os.path.join(OBJ, "gjcb.o"), []),           # ... and its HMC stage for gradient callbacks
             (os.path.join(CSRC, "ptmi_gjcb_wide.hip"), os.path.join(OBJ, "gjcb_wide.o"), []),   # ... the same stage beyond 512-d: whitening on the matrix cores

@@ -60,6 +60,8 @@ __host__ __device__ inline int am_inv(int p, int epl)
     return p < h ? ((p & 7) >> 1) + 4 * (2 * (p >> 3) + (p & 1)) : (p - h) + 4 * (epl - 1);
 }
 constexpr int am_row_epl(int G, int EPL) { return (G == 4 && EPL == 25) ? EPL : 0; }      // = ptmi_shape_exact (declared below)
+// doubles per row of the DE buffer (host code): the 16-byte pieces of the 4-lane shapes (de_update_kernel, ptmi_cov.hip), else ndim
+constexpr int de_row_ld(int G, int EPL, int ndim) { return G == 4 ? 8 * ((EPL + 1) / 2) : ndim; }
 
 // AM row flags (ptmi_buffers.AMflag, include/ptmi.h): one 8-byte word beside every row of the AM buffer.  A rejected proposal
 // leaves the rank-0 chain where it was -- its row repeats the row before it (43 % of the rows at the stationary acceptance of a
@@ -107,7 +109,7 @@ struct KArgs {
     int amq_on;                  // ... and whether this launch takes its AM increments from the queue (launch_mh_k)
     int box_off;                 // box prior: offset (doubles, even) of the bounds table in the block's LDS, or -1: bounds read from global
     int tab_off;                 // step kernels: offset (doubles, even) of the block's LDS copy of the draw tables (ptmi_tables.h), or -1: read from global
-    // AM increments computed ahead of the launch by am_gemm_kernel (ptmi_abi.hip; the 16- and 64-lane shapes): increment j of the
+    // AM increments computed ahead of the launch by am_gemm_kernel (ptmi_am_ahead.hip; the 16- and 64-lane shapes): increment j of the
     // chain's AM picks of this launch is am_inc[(am_base[chain] + j) * d ...]; nullptr: the kernel computes its own
     const double *am_inc;
     const long long *am_base;
@@ -211,7 +213,7 @@ struct ptmi_engine {
     void *d_qlw_scr;             // ... beyond 128 x 128 (ptmi_eig_wide.hip): the same for one batch of matrices, and its size
     size_t qlw_scr_bytes;
     void *d_rle_ent;             // pooled statistics over run-length-compacted rows: the stored rows of each slab, 16 bytes each [nrows]
-                                 // (PoolEnt, ptmi_abi.hip: the row inside its slab, the square root of its run length) ...
+                                 // (PoolEnt, ptmi_cov.hip: the row inside its slab, the square root of its run length) ...
     int32_t *d_rle_cnt;          // ... and how many each slab has [nslab]
     const double *rp_swap_u;     // TEST HOOK (ptmi_test_replay): the swap's uniforms [W][ntemps_global - 1] instead of the Philox ones
     const u64 *rp_draws;         // TEST HOOK: see KArgs
@@ -257,9 +259,13 @@ struct ptmi_engine {
 enum { PTMI_GJ_NONE = 0, PTMI_GJ_PENDING = 1 /* proposals made, ptmi_gj_begin not yet called */, PTMI_GJ_ROUNDS = 2, PTMI_GJ_DONE = 3 };
 // the split path's refusals for gradient jumps (0: served; else the code, with the message set)
 int ptmi_gj_split_check(const ptmi_engine *h);
-// the split path's scratch for AM increments made ahead of a launch (ptmi_abi.hip; ptmi_create for cycles without host-served entries,
+// the split path's scratch for AM increments made ahead of a launch (ptmi_am_ahead.hip; ptmi_create for cycles without host-served entries,
 // ptmi_cj_attach for cycles whose host-served entries are batched device callbacks); main: the fused kernels read it too
 hipError_t ptmi_am_scratch_alloc(ptmi_engine *h, bool am_main);
+// ... and the increments of iterations iter0 .. iter0 + ns - 1 computed into it, for ptmi_mh_steps
+int ptmi_am_prepare(ptmi_engine *h, long long iter0, int ns);
+// the pooled statistics' scratch (ptmi_cov.hip), for ptmi_create: d_pool_part, d_pool_T, d_rle_ent, d_rle_cnt
+hipError_t ptmi_pool_scratch_alloc(ptmi_engine *h);
 // eigensolvers (ptmi_eig.hip): frees h->dc_plan, for ptmi_destroy
 void ptmi_dc_plan_free(ptmi_engine *h);
 // posterior histograms (ptmi_hist.hip): frees h->hist, for ptmi_destroy

@@ -28,7 +28,7 @@
 // acceptance of the first thousand iterations from p0 = 0 that is 8 % of the rows instead of 91 %.  With one buffer (Q2 NULL) the
 // same rule makes every accepted row go to X at once: the single-buffer case is the one where the target IS the current buffer.
 //
-// AM picks (PT:879-933, 2 d^2 flop each) get their increments from the matrix cores AHEAD of the launch (am_gemm_kernel of ptmi_abi.hip:
+// AM picks (PT:879-933, 2 d^2 flop each) get their increments from the matrix cores AHEAD of the launch (am_gemm_kernel of ptmi_am_ahead.hip:
 // ptmi_split_am_prepare lists the picks of a piece of iterations and multiplies; an increment depends on the chain's stream, the
 // iteration and the scale branch, not on its state) and the row kernel adds the chain's next one as it adds a SCAM direction.
 // Not here: host-served cycle entries together with AM entries (unless they are batched device callbacks: ptmi_cj_attach makes the

@@ -1,4 +1,4 @@
-"""The covariance epoch's definition at the shapes where its kernels change path (csrc/ptmi_abi.hip: pool_rle_kernel, pool_syrk_kernel,
+"""The covariance epoch's definition at the shapes where its kernels change path (csrc/ptmi_cov.hip: pool_rle_kernel, pool_syrk_kernel,
 pool_reduce_kernel, pool_finish_kernel, welford_rows_kernel, welford_kernel, welford_mean_kernel): macro tiles of 112 columns with
 the ones column at position d, staged chunks of 32 and 16 rows, slabs (up to 512 of them, 32 beyond d = 111) reduced in batches of
 32 / 8 / 1, trips of 2048 flags and of 2048 stored rows, the per-walker kernels' switches at d = 100 and d = 112.

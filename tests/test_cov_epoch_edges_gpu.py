@@ -1,4 +1,4 @@
-"""The covariance epoch's kernels (csrc/ptmi_abi.hip), driven directly at their tile, chunk, slab and trip edges: pool_rle_kernel,
+"""The covariance epoch's kernels (csrc/ptmi_cov.hip), driven directly at their tile, chunk, slab and trip edges: pool_rle_kernel,
 pool_syrk_kernel in its eight forms, pool_reduce_kernel, pool_finish_kernel, welford_rows_kernel, welford_kernel, welford_mean_kernel,
 am_expand_kernel and de_update_kernel.  No chain is stepped: a synthetic ring is written into an engine of one temperature, the epoch
 is called through the C ABI, and mu / M2 / cov are compared with the oracle BIT FOR BIT (orc.pool_update, orc.pool_update_rle,

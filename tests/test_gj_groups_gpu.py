@@ -119,7 +119,7 @@ def test_fused_kernels_equal_the_oracle(mods, name):
     flags, lanes, _ = g.last_variant()
     assert flags & _lib.VAR_GRADJUMP and lanes == _lib.lanes_for(d, grad=True)
     # the GRP instantiation ran, in the one layout of its lane width -- also for the handles that would take the pair layout
-    # (curved20_box_diag) or the wide-16 one (dense40_diag) without groups; with an AM entry behind am_prepare's pieces
+    # (curved20_box_diag) or the wide-16 one (dense40_diag) without groups; with an AM entry behind ptmi_am_prepare's pieces
     layout, levels, nbytes, nslots = g.last_gj_launch()
     diag = not np.count_nonzero(cov0 - np.diag(np.diag(cov0)))        # (curved20_box starts from the identity: diagonal tables too)
     want = ((_lib.GJL_WAVE if lanes == 4 else _lib.GJL_CHAIN) | _lib.GJL_GRP | (_lib.GJL_DIAG if diag else 0) |

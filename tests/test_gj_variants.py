@@ -286,7 +286,7 @@ def expected_launch(c, nuts_maxdepth=24):
     ordered = c.cycle != "hmc"                      # the launch order serves the cycles with NUTS
     nch, solo = nt * W, min(solo_of(c) if cpw > 1 else 0, nt * W)
     nslots = solo * cpw + -(-(nch - solo) // cpw) * cpw if ordered else nch
-    am_ahead = c.cycle != "nuts" and (grp or G > 4)     # w_am > 0 and (parameter groups or a 16- / 64-lane shape): am_prepare's pieces
+    am_ahead = c.cycle != "nuts" and (grp or G > 4)     # w_am > 0 and (parameter groups or a 16- / 64-lane shape): ptmi_am_prepare's pieces
     flags = ((L.GJL_DIAG if diag else 0) | (L.GJL_GRP if grp else 0) | (L.GJL_BOX_LDS if box else 0) |
              (L.GJL_ORDERED if ordered else 0) | (L.GJL_AM_AHEAD if am_ahead else 0))
     return layout | flags, levels, 8 * off, nslots

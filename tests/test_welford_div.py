@@ -1,4 +1,4 @@
-"""The running mean's division in welford_rows_kernel (ptmi_abi.hip div_by_count) against the reference's plain `diff / n`
+"""The running mean's division in welford_rows_kernel (ptmi_cov.hip div_by_count) against the reference's plain `diff / n`
 (PTMCMCSampler.py:787): reciprocal times dividend, corrected twice through the exact remainder, is the correctly rounded quotient
 for every integer count -- random dividends, dividends next to rounding ties of the quotient, and tiny / huge magnitudes."""
 import numpy as np

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Did moving code between translation units change a kernel?  Compares the compiler's output, kernel by kernel.
 
-    tools/kernel_diff.py --rev HEAD~1 --old ptmi_abi.hip --new ptmi_abi.hip ptmi_eig.hip ptmi_swap.hip
+    tools/kernel_diff.py --rev HEAD~1 --old ptmi_abi.hip --new ptmi_abi.hip ptmi_cov.hip ptmi_am_ahead.hip
 
 compiles the --old units of csrc/ as they are at the git revision --rev and the --new units of the working tree, each with the
 library's own flags (_build.FLAGS) plus --cuda-device-only -S, and compares for every kernel
