@@ -717,6 +717,32 @@ int ptmi_ladder_update(ptmi_handle h, double kappa, int64_t tries_even, int64_t 
 int ptmi_ladder_publish(ptmi_handle h);
 int ptmi_ladder_read(ptmi_handle h, double *ladder /* host [ntemps_global] */, double *temps_mh /* host [T] */, double *beta /* host [T] */);
 
+/* Joint posterior histograms of parameter PAIRS from EVERY cold chain, accumulated on the device (csrc/ptmi_pairs.hip): the
+ * off-diagonal panels of a corner plot, from the ring that ptmi_hist_update reads.  The caller fixes npairs pairs (i, j) of different
+ * parameters (order matters: (j, i) is the transpose), lo[k] < hi[k], nbins per axis and scale[k] = nbins / (hi[k] - lo[k]) in double
+ * precision.  A ring row x that stands for n iterations is counted once per pair p = (i, j):
+ *
+ *     ti = (x[i] - lo[i]) * scale[i];  tj = (x[j] - lo[j]) * scale[j]      ptmi_hist_update's rule per axis: no fma
+ *     inside(t) = (t >= 0.0) and not (t >= nbins)                          NaN, x < lo, x >= hi (as scale rounds), +-inf: outside
+ *     if inside(ti) and inside(tj):  counts[p][(int)ti * nbins + (int)tj] += n
+ *     else:                          counts[p][nbins * nbins] += n         one "outside" cell per pair
+ *
+ * counts: DEVICE uint64 [npairs][nbins * nbins + 1]; caller-owned, zeroed by the caller, 8-byte aligned.  ptmi_pairs_attach (once per
+ * handle) takes it with pairs (HOST int32 [npairs][2]), lo / scale (HOST [ndim]; the library keeps device copies of what it needs),
+ * 1 <= npairs <= 8192 and 2 <= nbins <= 128.  PTMI_EINVAL, the message says which: NULL or misaligned counts, npairs or nbins out of
+ * range, an index outside 0 .. ndim - 1, i == j, a lo that is not finite, a scale that is not finite and positive, a second attach.
+ * State lives in the handle and is freed with it: ptmi_config and ptmi_buffers are unchanged, a handle that never attaches launches
+ * what it launched before, and ptmi_hist_attach may stand beside it.
+ * ptmi_pairs_update adds iterations iter_lo .. iter_hi of every walker from the handle's CURRENT ring with the contract of
+ * ptmi_hist_update: both in one covariance period (PTMI_EINVAL for a range that crosses one, and before ptmi_pairs_attach);
+ * iter_hi < iter_lo: nothing to do; the run-length weights of rings with AMflag are ptmi_hist_update's, so every iteration of every
+ * walker counts once per pair and a pair's cells grow by nwalkers * (iter_hi - iter_lo + 1).  temp0 != 0: PTMI_OK, nothing done.  Rings
+ * of 2^32 rows or more: PTMI_EUNSUPPORTED.  Asynchronous on the handle's stream, no host synchronisation, the ring is only read; no
+ * global atomics per element (a block adds its private tile of pair tables to counts once). */
+int ptmi_pairs_attach(ptmi_handle h, uint64_t *counts, const int32_t *pairs, int32_t npairs, const double *lo, const double *scale,
+                      int32_t nbins);
+int ptmi_pairs_update(ptmi_handle h, int64_t iter_lo, int64_t iter_hi);
+
 /* Self-test hooks used by the parity tests: evaluate the device's deterministic math on
  * n inputs (op: 0 log, 1 exp, 2 cos2pi, 3 sqrt, 4 reciprocal-free divide a/b with b=in2). */
 int ptmi_selftest_math(int device, int op, const double *in, const double *in2, double *out, int64_t n);

@@ -35,6 +35,7 @@
 // A u32 cell cannot overflow: the weights of a call sum to W x (iter_hi - iter_lo + 1) <= W x cov_update per column over ALL blocks, and
 // the call refuses rings of 2^32 rows or more.
 #include "ptmi_common.h"
+#include "ptmi_ring_weight.h"      // stored_at, hist_weight_kernel
 #include <math.h>
 
 struct ptmi_hist_state {
@@ -51,28 +52,6 @@ constexpr int UNR = 8;                 // elements in flight per thread
 constexpr int LDS_BYTES = 65536;       // weights + bounds + histogram of a block
 constexpr int TC_MAX = 512;            // columns per tile at most
 constexpr int NBLOCKS = 1024;          // blocks of a launch, about (every block flushes its tile once)
-
-// iteration base + k, k in 1 .. cu, sits in ring row k % cu
-__device__ __forceinline__ bool stored_at(const AmFlag *fw, int k, int cu) { return (fw[k == cu ? 0 : k] & (AMROW_NEW | AMROW_KEY)) != 0; }
-
-__global__ __launch_bounds__(256) void hist_weight_kernel(const AmFlag *flag, u32 *wgt, int cu, int klo, int khi)
-{
-    const size_t w = blockIdx.x;
-    const AmFlag *fw = flag ? flag + w * cu : nullptr;
-    u32 *ww = wgt + w * cu;
-    for (int r = (int)threadIdx.x; r < cu; r += 256) ww[r] = 0u;
-    __syncthreads();
-    for (int k = klo + (int)threadIdx.x; k <= khi; k += 256) {
-        int s = k;                                             // the stored row iteration k is counted with
-        if (fw && !stored_at(fw, k, cu)) {
-            if (k != klo) continue;                            // counted with its run's stored row
-            while (s > 1 && !stored_at(fw, s, cu)) --s;        // (ring row 1 of a period is a KEY row)
-        }
-        int n = k + 1;
-        if (fw) while (n <= khi && !stored_at(fw, n, cu)) ++n;
-        ww[s == cu ? 0 : s] = (u32)(n - k);
-    }
-}
 
 struct HistArgs {
     const double *AM;

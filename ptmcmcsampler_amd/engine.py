@@ -232,6 +232,12 @@ class PTEngine(object):
     (default ``hist_from = burn``).  ``update_cov`` counts the period that ends before it touches anything else, so every way of running
     the engine is served; ``hist_sync(it)`` counts up to an iteration inside a period, ``hist_counts(it=None)`` returns the result.  The
     ring is only read: the chains are the same bits with and without.  ``t["hist"]`` and ``hist_iter`` are part of ``checkpoint()``.
+    ``with_stages(..., pairs=(pairs, lo, hi, nbins), pairs_from=None)``: the joint posterior histograms of parameter PAIRS of every
+    walker's cold chain -- the off-diagonal panels of a corner plot -- from the same ring with the same rule per axis (include/ptmi.h
+    ``ptmi_pairs_*``, pairs.py ``pairs_rule``: both coordinates inside -> cell ``[int(ti)][int(tj)]``, else the pair's ``outside``).
+    ``pairs``: an integer ``[npairs][2]`` array ((j, i) is the transpose of (i, j)) or ``{"params": [indices]}`` = every pair ``(a, b)``
+    with ``a`` before ``b`` in the list; ``2 <= nbins <= 128``, ``npairs <= 8192``; ``pairs_from``, ``pairs_sync(it)``, ``pairs_counts(it=None)``
+    as the histogram's; both stages may run on one engine.  ``t["pairs"]`` and ``pairs_iter`` are part of ``checkpoint()``.
     ``with_stages(..., evidence=True, evidence_from=None, evidence_every=1)``: the ladder's summaries for the log-evidence ln Z (include/ptmi.h
     ``ptmi_ev_*``, evidence.py): per walker and rank the count, mean and variance of lnL (shifted sums) and the running log-sum-exp of
     ``dbeta_r * lnL``, ``dbeta_r = beta_{r-1} - beta_r`` from ``temps_mh`` (``hot_chain=True``: beta = 1e-80 at the last rank, the last
@@ -275,6 +281,8 @@ class PTEngine(object):
     logl_in_support = False
     _hist = None
     _hist_from = None
+    _pairs = None
+    _pairs_from = None
     _ev = False
     _ev_from = None
     _ev_every = 1
@@ -307,7 +315,7 @@ class PTEngine(object):
     @classmethod
     def with_stages(cls, *args, jumps_with_grad=False, aux=None, logl_in_support=False, hist=None, hist_from=None,
                     evidence=False, evidence_from=None, evidence_every=1, diag=False, diag_from=None, diag_batch=None, diag_levels=None,
-                    adapt_ladder=None, **kw):
+                    adapt_ladder=None, pairs=None, pairs_from=None, **kw):
         """``PTEngine(*args, **kw)`` with the stages of the composed ``_jump`` on the callback path (see the class docstring):
         ``jumps_with_grad=True`` lets ``jumps=`` stand beside ``grad_weights`` in one cycle, ``aux=[func, ...]`` are the auxiliary jumps,
         ``logl_in_support=True`` hands the likelihood callback only the rows whose prior is not -inf (``eval_callback``),
@@ -315,13 +323,16 @@ class PTEngine(object):
         ``evidence=True`` with ``evidence_from`` / ``evidence_every`` (default 1) the ladder's lnL summaries for ln Z (``evidence``),
         ``diag=True`` with ``diag_from`` / ``diag_batch`` (default 1) / ``diag_levels`` (default 16) the streaming sums of every cold chain
         for R-hat and ESS (``diagnostics``), ``adapt_ladder=True`` or ``dict(every=10, kappa=2.0, t0=10.0, until=None)`` adapts the
-        temperature ladder during burn-in from every walker's accepted swaps (``ladder_history``).
+        temperature ladder during burn-in from every walker's accepted swaps (``ladder_history``),
+        ``pairs=(pairs, lo, hi, nbins)`` with ``pairs_from`` accumulates the joint histograms of parameter pairs of every cold chain
+        (``pairs_counts``; ``pairs``: int ``[npairs][2]`` or ``{"params": [indices]}`` = every pair of the list).
         The plain constructor keeps the parameters it had (tests/test_gj_groups.py holds them to the letter) and its refusals."""
         self = cls.__new__(cls)
         self.jumps_with_grad = bool(jumps_with_grad)
         self._aux = list(aux) if aux is not None else []
         self.logl_in_support = bool(logl_in_support)
         self._hist, self._hist_from = hist, hist_from
+        self._pairs, self._pairs_from = pairs, pairs_from
         self._ev, self._ev_from, self._ev_every = bool(evidence), evidence_from, evidence_every
         self._diag, self._diag_from, self._diag_batch, self._diag_levels = bool(diag), diag_from, diag_batch, diag_levels
         self._adapt = adapt_ladder
@@ -384,6 +395,17 @@ class PTEngine(object):
             self.hist_iter = self.hist_from
         elif self._hist_from is not None:
             raise ValueError("hist_from= goes with hist=(lo, hi, nbins)")
+        # joint histograms of parameter pairs of the cold chains (with_stages(pairs=(pairs, lo, hi, nbins), pairs_from=...); see the class docstring)
+        self.pairs_spec = None
+        if self._pairs is not None:
+            from .pairs import pairs_spec
+            self.pairs_spec = pairs_spec(int(ndim), self._pairs)
+            self.pairs_from = int(burn) if self._pairs_from is None else int(self._pairs_from)
+            if self.pairs_from < 0:
+                raise ValueError("pairs_from = %d: the first iteration counted is pairs_from + 1 >= 1" % self.pairs_from)
+            self.pairs_iter = self.pairs_from
+        elif self._pairs_from is not None:
+            raise ValueError("pairs_from= goes with pairs=(pairs, lo, hi, nbins)")
         # convergence diagnostics of the cold chains (with_stages(diag=True, diag_from=..., diag_batch=..., diag_levels=...); see the class docstring)
         self.diag_on = bool(self._diag)
         if self.diag_on:
@@ -642,6 +664,13 @@ class PTEngine(object):
             self._hist_scale = nbins / (hi - lo)
             _lib.check(self.lib.ptmi_hist_attach(self.h, C.c_void_p(self.t["hist"].data_ptr()), lo.ctypes.data_as(_lib._dp),
                                                  self._hist_scale.ctypes.data_as(_lib._dp), nbins))
+        if self.pairs_spec is not None:
+            # uint64 [npairs][nbins * nbins + 1] (the table row-major, then "outside"); in self.t: checkpoints carry it by itself
+            pr, lo, hi, nbins = self.pairs_spec
+            self.t["pairs"] = z((len(pr), nbins * nbins + 1), i64)
+            self._pairs_scale = nbins / (hi - lo)
+            _lib.check(self.lib.ptmi_pairs_attach(self.h, C.c_void_p(self.t["pairs"].data_ptr()), pr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  len(pr), lo.ctypes.data_as(_lib._dp), self._pairs_scale.ctypes.data_as(_lib._dp), nbins))
         if self.evidence_on:
             # double [5][W][nt] (shift, s1, s2, m, es) and uint64 [2][W][nt] (taken, skipped), plane-major, by local rank; in self.t:
             # checkpoints carry them by themselves
@@ -1002,6 +1031,8 @@ class PTEngine(object):
             return
         if self.hist_spec is not None:
             self._hist_sync(it_done)                                  # before the statistics, and before stats_async switches rings
+        if self.pairs_spec is not None:
+            self._pairs_sync(it_done)                                 # the same
         if self.diag_on:
             self._diag_sync(it_done)                                  # the same
         # A factorization still pending from the epoch before (eig_lag >= the launches of a period) is finished here at the latest.
@@ -1115,6 +1146,40 @@ class PTEngine(object):
                     edges=hist_edges(lo, hi, nbins), first_iter=np.int64(self.hist_from + 1), last_iter=np.int64(self.hist_iter),
                     nwalkers=np.int64(self.W))
 
+    # ------------------------------------------------------------------ pair histograms
+    def pairs_sync(self, it):
+        """Count iterations ``(pairs_iter, it]`` of every walker's cold chain into ``t["pairs"]`` (``ptmi_pairs_update``: asynchronous,
+        the ring is only read).  ``it`` lies in the covariance period the ring holds; ``update_cov`` calls this at every period's end,
+        so a caller only needs it for counts up to an iteration inside a period.  Nothing to do up to ``pairs_from``."""
+        if self.pairs_spec is None:
+            raise ValueError("no pair histogram: PTEngine.with_stages(..., pairs=(pairs, lo, hi, nbins))")
+        if int(it) > self.iter:
+            raise ValueError("pairs_sync(%d): the engine has reached iteration %d; the ring's rows beyond it are the period before's" % (int(it), self.iter))
+        self._pairs_sync(it)
+
+    def _pairs_sync(self, it):
+        it = int(it)
+        if it <= self.pairs_iter:
+            return
+        base = ((it - 1) // self.cov_update) * self.cov_update
+        if self.pairs_iter < base and self.owns_cold:
+            raise ValueError("pairs_sync(%d): iterations %d..%d are no longer in the ring (it holds the period after %d); every period "
+                             "must end through update_cov" % (it, self.pairs_iter + 1, base, base))
+        _lib.check(self.lib.ptmi_pairs_update(self.h, self.pairs_iter + 1, it))
+        self.pairs_iter = it
+
+    def pairs_counts(self, it=None):
+        """The pair histograms up to iteration ``it`` (default: the current one): a dict of ``counts`` uint64 [npairs][nbins][nbins]
+        (``counts[p][a][b]``: parameter ``pairs[p][0]`` in bin ``a``, ``pairs[p][1]`` in bin ``b``), ``outside`` [npairs] (either coordinate
+        NaN, below ``lo`` or at or above ``hi``), ``pairs`` [npairs][2], ``edges`` [ndim][nbins + 1], ``first_iter`` / ``last_iter`` (the
+        iterations counted, of every one of ``nwalkers`` cold chains)."""
+        self.pairs_sync(self.iter if it is None else it)
+        pr, lo, hi, nbins = self.pairs_spec
+        a = self.t["pairs"].cpu().numpy().view(np.uint64)
+        return dict(counts=np.ascontiguousarray(a[:, :nbins * nbins]).reshape(len(pr), nbins, nbins), outside=a[:, nbins * nbins].copy(),
+                    pairs=pr.copy(), edges=hist_edges(lo, hi, nbins), first_iter=np.int64(self.pairs_from + 1),
+                    last_iter=np.int64(self.pairs_iter), nwalkers=np.int64(self.W))
+
     # ------------------------------------------------------------------ convergence diagnostics
     def diag_sync(self, it):
         """Fold iterations ``(diag_iter, it]`` of every walker's cold chain into ``t["diag"]`` (``ptmi_diag_update``: asynchronous, the ring
@@ -1186,6 +1251,8 @@ class PTEngine(object):
                   eig_pending=int(self._eig_pending), eig_wait=int(self._eig_wait))
         if self.hist_spec is not None:
             st["hist_iter"] = self.hist_iter
+        if self.pairs_spec is not None:
+            st["pairs_iter"] = self.pairs_iter
         if self.evidence_on:
             st["ev_epochs"] = self.ev_epochs
         if self.diag_on:
@@ -1202,6 +1269,10 @@ class PTEngine(object):
         torch = _torch()
         if self.hist_spec is not None and ("hist_iter" not in st or "t_hist" not in st):      # refused before anything is touched
             raise ValueError("the checkpoint carries no histogram: it was written by a run without hist=")
+        if self.pairs_spec is not None and ("pairs_iter" not in st or "t_pairs" not in st
+                                            or tuple(np.shape(st["t_pairs"])) != tuple(self.t["pairs"].shape)):
+            raise ValueError("the checkpoint carries no pair histograms of this shape: it was written by a run without pairs= (or with "
+                             "other pairs or bins)")
         if self.evidence_on and any(k not in st for k in ("ev_epochs", "t_ev_acc", "t_ev_cnt")):
             raise ValueError("the checkpoint carries no evidence accumulators: it was written by a run without evidence=True")
         if self.diag_on and ("diag_iter" not in st or "t_diag" not in st
@@ -1236,6 +1307,8 @@ class PTEngine(object):
         self.eig_epochs = int(st["eig_epochs"])                       # (behind _eig_finish, which counts the dropped table)
         if self.hist_spec is not None:
             self.hist_iter = int(st["hist_iter"])
+        if self.pairs_spec is not None:
+            self.pairs_iter = int(st["pairs_iter"])
         if self.evidence_on:
             self.ev_epochs = int(st["ev_epochs"])
         if self.diag_on:

@@ -35,6 +35,12 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
   from the AM ring (``PTEngine.with_stages(hist=...)``): ``<outDir>/hist.npz`` (``counts``, ``under``, ``over``, ``edges``, ``first_iter``,
   ``last_iter``, ``nwalkers``) at every save, ``sampler.hist`` after the run; ``checkpoint=True`` runs resume the counts, a replay of
   chain files cannot;
+* ``sampler.posterior_pairs = (pairs, lo, hi, nbins)`` (before ``sample()``; any likelihood, any path): the joint posterior histograms
+  of parameter pairs -- the off-diagonal panels of a corner plot -- of EVERY walker's cold chain after ``burn``, accumulated on the
+  device from the AM ring (``PTEngine.with_stages(pairs=...)``, pairs.py).  ``pairs``: an integer ``[npairs][2]`` array or
+  ``{"params": [indices]}`` = every pair of the list; ``<outDir>/pairs.npz`` (``counts`` [npairs][nbins][nbins], ``outside``, ``pairs``,
+  ``edges``, ``first_iter``, ``last_iter``, ``nwalkers``) at every save, ``sampler.pairs2d`` after the run (``pairs.credible_levels``
+  gives the contour thresholds); ``checkpoint=True`` runs resume the counts, a replay of chain files cannot;
 * ``sampler.chain_diagnostics = True`` or ``{"batch": b0, "levels": L, "stop_ess": N, "stop_rhat": r}`` (before ``sample()``; any likelihood,
   any path): Gelman-Rubin R-hat, the integrated autocorrelation time and the effective sample size of every parameter from EVERY
   walker's cold chain after ``burn`` -- where the ``neff`` rule (PTMCMCSampler.py:510-521) looks at one kept chain.  The device streams the
@@ -172,6 +178,11 @@ class PTSampler(object):
     # scalars or [ndim].  An attribute for the same reason as batched_aux
     posterior_hist = None
     hist = None
+    # s.posterior_pairs = (pairs, lo, hi, nbins) (before sample()): the joint posterior histograms of parameter pairs of EVERY walker's
+    # cold chain after burn, accumulated on the device (PTEngine.with_stages(pairs=...)): <outDir>/pairs.npz at every save, s.pairs2d
+    # after the run.  pairs: int [npairs][2] or {"params": [indices]}; lo / hi: scalars or [ndim].  An attribute for the same reason
+    posterior_pairs = None
+    pairs2d = None
     # s.log_evidence = True, or {"every": k} (before sample()): ln Z from the ladder of EVERY walker -- per-temperature lnL moments taken on
     # the device behind every (k-th) swap after burn (PTEngine.with_stages(evidence=True)): <outDir>/evidence.npz at every save, s.evidence
     # after the run.  An attribute for the same reason as batched_aux
@@ -425,6 +436,10 @@ class PTSampler(object):
             raise NotImplementedError("posterior_hist counts every walker's cold chain on the device; chain files hold the kept walkers' "
                                       "thinned rows only, so a replayed run cannot continue the counts: resume from a device checkpoint "
                                       "(PTSampler(..., checkpoint=True) from the first run on)")
+        if self._replaying and self.posterior_pairs is not None:
+            raise NotImplementedError("posterior_pairs counts every walker's cold chain on the device; chain files hold the kept walkers' "
+                                      "thinned rows only, so a replayed run cannot continue the counts: resume from a device checkpoint "
+                                      "(PTSampler(..., checkpoint=True) from the first run on)")
         if self._replaying and self.log_evidence:
             raise NotImplementedError("log_evidence sums the lnL of every walker's whole ladder on the device; chain files hold the kept "
                                       "walkers' thinned rows only, so a replayed run cannot continue the sums: resume from a device checkpoint "
@@ -537,7 +552,7 @@ class PTSampler(object):
             split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
             jumps=[(f, n) for f, n in stage_list] if stage_list else None,
             jumps_with_grad=bool(stage_list) and sum(self._grad_weights) > 0, aux=list(self._batched_aux) or None,
-            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **self._evidence_kw(), **self._diag_kw(), **self._adapt_kw(),
+            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **({"pairs": self.posterior_pairs} if self.posterior_pairs is not None else {}), **self._evidence_kw(), **self._diag_kw(), **self._adapt_kw(),
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     def _evidence_kw(self):
@@ -741,6 +756,9 @@ class PTSampler(object):
                                   # (the histogram's bins, only where there are some: the other runs' fingerprints stay what they were)
                                   + ((("hist", eng.hist_from, eng.hist_spec[2]),) if eng.hist_spec is not None else ()), *groups,
                                   *(eng.hist_spec[:2] if eng.hist_spec is not None else ()),
+                                  # (the pair histograms' pairs and bins, only where there are some)
+                                  *((("pairs", eng.pairs_from, eng.pairs_spec[3], eng.pairs_spec[0].tobytes()), *eng.pairs_spec[1:3])
+                                    if eng.pairs_spec is not None else ()),
                                   # (the evidence stage's sampling, only where it is on)
                                   *((("evidence", eng.evidence_from, eng.evidence_every),) if eng.evidence_on else ()),
                                   # (the diagnostics stage's batches, only where it is on)
@@ -1059,6 +1077,14 @@ class PTSampler(object):
         np.savez(tmp, **self.hist)
         os.replace(tmp, os.path.join(self.outDir, "hist.npz"))
 
+    def _write_pairs(self, iter):
+        """The pair histograms up to iteration ``iter`` (of the current covariance period) -> self.pairs2d and <outDir>/pairs.npz."""
+        self.engine.iter = max(self.engine.iter, int(iter))          # (the sampler's loops step the engine themselves)
+        self.pairs2d = self.engine.pairs_counts(iter)
+        tmp = os.path.join(self.outDir, "pairs.tmp.npz")
+        np.savez(tmp, **self.pairs2d)
+        os.replace(tmp, os.path.join(self.outDir, "pairs.npz"))
+
     def _write_evidence(self):
         """The estimates from the samples so far, with the moments they come from -> self.evidence and <outDir>/evidence.npz."""
         from .evidence import estimates
@@ -1111,6 +1137,10 @@ class PTSampler(object):
             raise ValueError("posterior_hist was set after the engine was built: set it before the first sample()")
         if self.engine.hist_spec is not None and iter > 0:
             self._write_hist(iter)                                    # ahead of the checkpoint: it carries the counts up to here
+        if self.posterior_pairs is not None and self.engine.pairs_spec is None:
+            raise ValueError("posterior_pairs was set after the engine was built: set it before the first sample()")
+        if self.engine.pairs_spec is not None and iter > 0:
+            self._write_pairs(iter)                                   # the same
         if iter // self.thin >= self.ind_next_write:
             self._counters()
             self._writeToFile(iter)
