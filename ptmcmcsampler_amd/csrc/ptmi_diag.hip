@@ -29,6 +29,8 @@
 // the cascade's branches are wave-uniform (scalar registers); Q / H stay in vector registers because the loop over l is unrolled with
 // uniform guards (an array indexed by a run-time l would go to scratch).
 #include "ptmi_common.h"
+#define PTMI_RING_RANGE_ONLY       // this reader weighs no rows: no copy of hist_weight_kernel
+#include "ptmi_ring_weight.h"      // ring_range
 
 struct ptmi_diag_state {
     double *acc;               // caller-owned [2 * nlevels + 3][W][ndim]
@@ -177,19 +179,14 @@ int ptmi_diag_update(ptmi_handle h, int64_t iter_lo, int64_t iter_hi, int64_t n_
     const ptmi_diag_state *s = h->diag;
     if (!s) return fail(PTMI_EINVAL, "ptmi_diag_update: no accumulators are attached (ptmi_diag_attach)");
     const ptmi_config &c = h->cfg;
-    if (c.temp0 != 0) return PTMI_OK;                   // only the GPU holding rank 0 has the cold chains (as ptmi_update_cov)
-    if (iter_hi < iter_lo) return PTMI_OK;
+    long long base;
+    if (int r = ring_range(h, "ptmi_diag_update", iter_lo, iter_hi, &base)) return r == RING_IDLE ? PTMI_OK : r;
     if (n_done < 0) return fail(PTMI_EINVAL, "ptmi_diag_update: n_done >= 0 (got %lld)", (long long)n_done);
-    const long long cu = c.cov_update, base = iter_hi > 0 ? ((long long)(iter_hi - 1) / cu) * cu : 0;
-    if (iter_lo <= base || iter_hi < 1)
-        return fail(PTMI_EINVAL, "ptmi_diag_update: iterations %lld..%lld cross a covariance period: the ring holds (%lld, %lld], the period of "
-                                 "the last one", (long long)iter_lo, (long long)iter_hi, base, base + cu);
-    if (!h->buf.AM) return fail(PTMI_EINVAL, "ptmi_diag_update: the handle has no AM buffer");
     DiagArgs a;
     a.AM = h->buf.AM; a.flag = (const AmFlag *)h->buf.AMflag; a.acc = s->acc;
     a.nstreams = (long long)c.nwalkers * c.ndim;
     a.k_done = (long long)n_done / s->batch0; a.rem = (int)((long long)n_done % s->batch0); a.first = n_done == 0;
-    a.d = c.ndim; a.epl = am_row_epl(h->G, h->EPL); a.cu = (int)cu;
+    a.d = c.ndim; a.epl = am_row_epl(h->G, h->EPL); a.cu = c.cov_update;
     a.klo = (int)(iter_lo - base); a.khi = (int)(iter_hi - base); a.L = s->nlevels; a.b0 = s->batch0;
     const long long nblocks = (a.nstreams + 255) / 256;
     if (nblocks >= (1ll << 31)) return fail(PTMI_EUNSUPPORTED, "ptmi_diag_update: %lld streams (a block per 256: below 2^31 blocks)", a.nstreams);

@@ -35,8 +35,7 @@
 // A u32 cell cannot overflow: the weights of a call sum to W x (iter_hi - iter_lo + 1) <= W x cov_update per column over ALL blocks, and
 // the call refuses rings of 2^32 rows or more.
 #include "ptmi_common.h"
-#include "ptmi_ring_weight.h"      // stored_at, hist_weight_kernel
-#include <math.h>
+#include "ptmi_ring_weight.h"      // hist_weight_kernel, ring_range, ring_weigh, ring_bounds
 
 struct ptmi_hist_state {
     u64 *counts;               // caller-owned [ndim][nbins + 2]
@@ -139,10 +138,7 @@ int ptmi_hist_attach(ptmi_handle h, uint64_t *counts, const double *lo, const do
     if (nbins < 2 || nbins > 1024) return fail(PTMI_EINVAL, "ptmi_hist_attach: 2 <= nbins <= 1024 (got %d)", (int)nbins);
     if (!counts || ((uintptr_t)counts & 7) != 0) return fail(PTMI_EINVAL, "ptmi_hist_attach: counts must be non-NULL and 8-byte aligned");
     const ptmi_config &c = h->cfg;
-    for (int j = 0; j < c.ndim; ++j)
-        if (!isfinite(lo[j]) || !isfinite(scale[j]) || !(scale[j] > 0.0))
-            return fail(PTMI_EINVAL, "ptmi_hist_attach: parameter %d: lo must be finite and scale = nbins / (hi - lo) finite and positive (got %g, %g)", j,
-                        lo[j], scale[j]);
+    if (int r = ring_bounds("ptmi_hist_attach", c.ndim, lo, scale)) return r;
     ptmi_hist_state *s = new ptmi_hist_state();
     s->counts = (u64 *)counts;
     s->nbins = (int)nbins;
@@ -166,17 +162,10 @@ int ptmi_hist_update(ptmi_handle h, int64_t iter_lo, int64_t iter_hi)
     const ptmi_hist_state *s = h->hist;
     if (!s) return fail(PTMI_EINVAL, "ptmi_hist_update: no histogram is attached (ptmi_hist_attach)");
     const ptmi_config &c = h->cfg;
-    if (c.temp0 != 0) return PTMI_OK;                   // only the GPU holding rank 0 has the cold chains (as ptmi_update_cov)
-    if (iter_hi < iter_lo) return PTMI_OK;
-    const long long cu = c.cov_update, base = iter_hi > 0 ? ((long long)(iter_hi - 1) / cu) * cu : 0;
-    if (iter_lo <= base || iter_hi < 1)
-        return fail(PTMI_EINVAL, "ptmi_hist_update: iterations %lld..%lld cross a covariance period: the ring holds (%lld, %lld], the period of "
-                                 "the last one", (long long)iter_lo, (long long)iter_hi, base, base + cu);
-    if (!h->buf.AM) return fail(PTMI_EINVAL, "ptmi_hist_update: the handle has no AM buffer");
-    const long long nrows = (long long)c.nwalkers * cu;
-    if (nrows >= (1ll << 32)) return fail(PTMI_EUNSUPPORTED, "ptmi_hist_update: a ring of %lld rows (32-bit counts per block: below 2^32)", nrows);
-    hipLaunchKernelGGL(hist_weight_kernel, dim3((unsigned)c.nwalkers), dim3(256), 0, h->stream, (const AmFlag *)h->buf.AMflag, s->d_wgt, (int)cu,
-                       (int)(iter_lo - base), (int)(iter_hi - base));
+    long long base;
+    if (int r = ring_range(h, "ptmi_hist_update", iter_lo, iter_hi, &base)) return r == RING_IDLE ? PTMI_OK : r;
+    if (int r = ring_weigh(h, "ptmi_hist_update", s->d_wgt, base, iter_lo, iter_hi)) return r;
+    const long long nrows = (long long)c.nwalkers * c.cov_update;
     HistArgs a;
     a.AM = h->buf.AM; a.wgt = s->d_wgt; a.lo = s->d_lo; a.scale = s->d_scale; a.counts = s->counts;
     a.nrows = nrows; a.d = c.ndim; a.epl = am_row_epl(h->G, h->EPL); a.nbins = s->nbins;

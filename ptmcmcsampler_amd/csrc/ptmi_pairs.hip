@@ -38,8 +38,7 @@
 // A u32 cell cannot overflow: the weights of a call sum to W x (iter_hi - iter_lo + 1) <= W x cov_update per pair over ALL blocks, and
 // the call refuses rings of 2^32 rows or more.
 #include "ptmi_common.h"
-#include "ptmi_ring_weight.h"      // stored_at, hist_weight_kernel
-#include <math.h>
+#include "ptmi_ring_weight.h"      // hist_weight_kernel, ring_range, ring_weigh, ring_bounds
 #include <algorithm>
 #include <vector>
 
@@ -182,10 +181,7 @@ int ptmi_pairs_attach(ptmi_handle h, uint64_t *counts, const int32_t *pairs, int
         if (i < 0 || i >= c.ndim || j < 0 || j >= c.ndim || i == j)
             return fail(PTMI_EINVAL, "ptmi_pairs_attach: pair %d: two different parameters in 0 .. %d (got %d, %d)", p, c.ndim - 1, i, j);
     }
-    for (int j = 0; j < c.ndim; ++j)
-        if (!isfinite(lo[j]) || !isfinite(scale[j]) || !(scale[j] > 0.0))
-            return fail(PTMI_EINVAL, "ptmi_pairs_attach: parameter %d: lo must be finite and scale = nbins / (hi - lo) finite and positive (got %g, %g)", j,
-                        lo[j], scale[j]);
+    if (int r = ring_bounds("ptmi_pairs_attach", c.ndim, lo, scale)) return r;
     // the tiles: the pair list in its order, a tile closed where the next pair (with the columns it adds) no longer fits
     const int epl = am_row_epl(h->G, h->EPL);
     std::vector<PairTile> tiles;
@@ -249,17 +245,10 @@ int ptmi_pairs_update(ptmi_handle h, int64_t iter_lo, int64_t iter_hi)
     const ptmi_pairs_state *s = h->pairs;
     if (!s) return fail(PTMI_EINVAL, "ptmi_pairs_update: no pair histogram is attached (ptmi_pairs_attach)");
     const ptmi_config &c = h->cfg;
-    if (c.temp0 != 0) return PTMI_OK;                   // only the GPU holding rank 0 has the cold chains (as ptmi_update_cov)
-    if (iter_hi < iter_lo) return PTMI_OK;
-    const long long cu = c.cov_update, base = iter_hi > 0 ? ((long long)(iter_hi - 1) / cu) * cu : 0;
-    if (iter_lo <= base || iter_hi < 1)
-        return fail(PTMI_EINVAL, "ptmi_pairs_update: iterations %lld..%lld cross a covariance period: the ring holds (%lld, %lld], the period of "
-                                 "the last one", (long long)iter_lo, (long long)iter_hi, base, base + cu);
-    if (!h->buf.AM) return fail(PTMI_EINVAL, "ptmi_pairs_update: the handle has no AM buffer");
-    const long long nrows = (long long)c.nwalkers * cu;
-    if (nrows >= (1ll << 32)) return fail(PTMI_EUNSUPPORTED, "ptmi_pairs_update: a ring of %lld rows (32-bit counts per block: below 2^32)", nrows);
-    hipLaunchKernelGGL(hist_weight_kernel, dim3((unsigned)c.nwalkers), dim3(256), 0, h->stream, (const AmFlag *)h->buf.AMflag, s->d_wgt, (int)cu,
-                       (int)(iter_lo - base), (int)(iter_hi - base));
+    long long base;
+    if (int r = ring_range(h, "ptmi_pairs_update", iter_lo, iter_hi, &base)) return r == RING_IDLE ? PTMI_OK : r;
+    if (int r = ring_weigh(h, "ptmi_pairs_update", s->d_wgt, base, iter_lo, iter_hi)) return r;
+    const long long nrows = (long long)c.nwalkers * c.cov_update;
     PairsArgs a;
     a.AM = h->buf.AM; a.wgt = s->d_wgt; a.tile = s->d_tile; a.cpos = s->d_cpos; a.clo = s->d_clo; a.csc = s->d_csc; a.pslot = s->d_pslot;
     a.counts = s->counts; a.nrows = nrows; a.d = c.ndim; a.nbins = s->nbins;

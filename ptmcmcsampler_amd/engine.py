@@ -98,6 +98,46 @@ def hist_edges(lo, hi, nbins):
     return e
 
 
+class _RingReader(object):
+    """A stage that reads the cold chains' AM ring a second time: iterations ``first + 1`` on, ``iter`` the last one taken.
+    ``update(eng, lo, hi, n_done)`` issues the stage's C call for iterations ``lo .. hi`` of the period the ring holds, ``n_done`` taken
+    before.  The engine comes in with every call: a reader that held it would keep it from being freed where its last name goes."""
+    # name: what the messages call it, how with_stages asks for it, what it does to an iteration, what restore() says without its state
+    WORDS = {"hist": ("histogram", "hist=(lo, hi, nbins)", "counted",
+                      "the checkpoint carries no histogram: it was written by a run without hist="),
+             "pairs": ("pair histogram", "pairs=(pairs, lo, hi, nbins)", "counted",
+                       "the checkpoint carries no pair histograms of this shape: it was written by a run without pairs= (or with other pairs or bins)"),
+             "diag": ("diagnostics", "diag=True", "folded",
+                      "the checkpoint carries no diagnostics sums of this shape: it was written by a run without diag=True (or with other diag_levels)")}
+
+    def __init__(self, name, first, update):
+        self.name, self.first, self.iter, self.update = name, first, first, update
+
+    def sync(self, eng, it):
+        """The engine's ``<name>_sync(it)``."""
+        if int(it) > eng.iter:
+            raise ValueError("%s_sync(%d): the engine has reached iteration %d; the ring's rows beyond it are the period before's"
+                             % (self.name, int(it), eng.iter))
+        self.advance(eng, it)
+
+    def advance(self, eng, it):
+        """Take iterations ``(iter, it]``; ``it`` is not held against the engine's iteration (``update_cov`` ends a period this way)."""
+        it = int(it)
+        if it <= self.iter:
+            return
+        base = ((it - 1) // eng.cov_update) * eng.cov_update
+        if self.iter < base and eng.owns_cold:
+            raise ValueError("%s_sync(%d): iterations %d..%d are no longer in the ring (it holds the period after %d); every period "
+                             "must end through update_cov" % (self.name, it, self.iter + 1, base, base))
+        self.update(eng, self.iter + 1, it, self.iter - self.first)
+        self.iter = it
+
+
+def _ring_attr(name, field):
+    """``PTEngine.<name>_from`` / ``<name>_iter``: the reader's ``first`` / ``iter`` (an engine without the stage has no such attribute)."""
+    return property(lambda self: getattr(self._reader(name), field))
+
+
 def interval_par(a, b, d):
     """Parameters of the ("interval", a, b) family (include/ptmi.h PTMI_LOGL_INTERVAL): a, w = b - a, log w."""
     a = np.broadcast_to(np.asarray(a, np.float64), (d,))
@@ -386,26 +426,17 @@ class PTEngine(object):
             raise ValueError("logl_in_support=True is a stage of the callback path: split=True (or rows_logl=True); the fused kernels "
                              "have no likelihood callback to spare")
         # posterior histograms of the cold chains (with_stages(hist=(lo, hi, nbins), hist_from=...); see the class docstring)
-        self.hist_spec = None
-        if self._hist is not None:
-            self.hist_spec = hist_spec(int(ndim), self._hist)
-            self.hist_from = int(burn) if self._hist_from is None else int(self._hist_from)
-            if self.hist_from < 0:
-                raise ValueError("hist_from = %d: the first iteration counted is hist_from + 1 >= 1" % self.hist_from)
-            self.hist_iter = self.hist_from
-        elif self._hist_from is not None:
-            raise ValueError("hist_from= goes with hist=(lo, hi, nbins)")
+        self._ring = []                                               # the ring's second readers, in the order update_cov serves them
+        self.hist_spec = None if self._hist is None else hist_spec(int(ndim), self._hist)
+        self._ring_reader("hist", self.hist_spec is not None, self._hist_from, burn,
+                          lambda eng, lo, hi, n: _lib.check(eng.lib.ptmi_hist_update(eng.h, lo, hi)))
         # joint histograms of parameter pairs of the cold chains (with_stages(pairs=(pairs, lo, hi, nbins), pairs_from=...); see the class docstring)
         self.pairs_spec = None
         if self._pairs is not None:
             from .pairs import pairs_spec
             self.pairs_spec = pairs_spec(int(ndim), self._pairs)
-            self.pairs_from = int(burn) if self._pairs_from is None else int(self._pairs_from)
-            if self.pairs_from < 0:
-                raise ValueError("pairs_from = %d: the first iteration counted is pairs_from + 1 >= 1" % self.pairs_from)
-            self.pairs_iter = self.pairs_from
-        elif self._pairs_from is not None:
-            raise ValueError("pairs_from= goes with pairs=(pairs, lo, hi, nbins)")
+        self._ring_reader("pairs", self.pairs_spec is not None, self._pairs_from, burn,
+                          lambda eng, lo, hi, n: _lib.check(eng.lib.ptmi_pairs_update(eng.h, lo, hi)))
         # convergence diagnostics of the cold chains (with_stages(diag=True, diag_from=..., diag_batch=..., diag_levels=...); see the class docstring)
         self.diag_on = bool(self._diag)
         if self.diag_on:
@@ -420,12 +451,10 @@ class PTEngine(object):
                 raise ValueError("diag=True reads the cold chains' ring: this engine (temp0 = %d) holds no rank 0 and owns no cold ring at "
                                  "all; the stage belongs on the block with temp0 = 0" % int(temp0))
             self.diag_batch, self.diag_levels = int(b0), int(L)
-            self.diag_from = int(burn) if self._diag_from is None else int(self._diag_from)
-            if self.diag_from < 0:
-                raise ValueError("diag_from = %d: the first iteration folded is diag_from + 1 >= 1" % self.diag_from)
-            self.diag_iter = self.diag_from
         elif self._diag_from is not None or self._diag_batch is not None or self._diag_levels is not None:
             raise ValueError("diag_from= / diag_batch= / diag_levels= go with diag=True")
+        self._ring_reader("diag", self.diag_on, self._diag_from, burn,
+                          lambda eng, lo, hi, n: _lib.check(eng.lib.ptmi_diag_update(eng.h, lo, hi, n)))
         # the ladder's summaries for the log-evidence (with_stages(evidence=True, evidence_from=..., evidence_every=...); see the class docstring)
         self.evidence_on = bool(self._ev)
         if self.evidence_on:
@@ -1029,12 +1058,8 @@ class PTEngine(object):
         """Covariance epoch after iteration ``it_done`` (:545-560): device Welford, host SVD."""
         if not self.owns_cold:
             return
-        if self.hist_spec is not None:
-            self._hist_sync(it_done)                                  # before the statistics, and before stats_async switches rings
-        if self.pairs_spec is not None:
-            self._pairs_sync(it_done)                                 # the same
-        if self.diag_on:
-            self._diag_sync(it_done)                                  # the same
+        for r in self._ring:
+            r.advance(self, it_done)                                  # before the statistics, and before stats_async switches rings
         # A factorization still pending from the epoch before (eig_lag >= the launches of a period) is finished here at the latest.
         # On the side stream (device factorizations) it goes on BESIDE this epoch's statistics, which do not read the table: they are
         # queued first, the wait for the old table comes behind them -- the same table in force for the same launches either way.
@@ -1113,27 +1138,37 @@ class PTEngine(object):
             self._eig_begin(self._st)
         self._eig_wait = self.eig_lag
 
+    # ------------------------------------------------------------------ the ring's second readers (_RingReader)
+    def _ring_reader(self, name, on, first, burn, update):
+        """The reader of the stage ``name`` that is ``on`` joins ``_ring``, from iteration ``first`` (``<name>_from``; default ``burn``)."""
+        _, hint, verb, _ = _RingReader.WORDS[name]
+        if not on:
+            if first is not None:
+                raise ValueError("%s_from= goes with %s" % (name, hint))
+            return
+        first = int(burn) if first is None else int(first)
+        if first < 0:
+            raise ValueError("%s_from = %d: the first iteration %s is %s_from + 1 >= 1" % (name, first, verb, name))
+        self._ring.append(_RingReader(name, first, update))
+
+    def _reader(self, name):
+        return next((r for r in self._ring if r.name == name), None)
+
+    def _ring_sync(self, name, it):
+        if self._reader(name) is None:
+            raise ValueError("no %s: PTEngine.with_stages(..., %s)" % _RingReader.WORDS[name][:2])
+        self._reader(name).sync(self, it)
+
+    hist_from, hist_iter = _ring_attr("hist", "first"), _ring_attr("hist", "iter")
+    pairs_from, pairs_iter = _ring_attr("pairs", "first"), _ring_attr("pairs", "iter")
+    diag_from, diag_iter = _ring_attr("diag", "first"), _ring_attr("diag", "iter")
+
     # ------------------------------------------------------------------ posterior histograms
     def hist_sync(self, it):
         """Count iterations ``(hist_iter, it]`` of every walker's cold chain into ``t["hist"]`` (``ptmi_hist_update``: asynchronous, the
         ring is only read).  ``it`` lies in the covariance period the ring holds; ``update_cov`` calls this at every period's end, so
         a caller only needs it for counts up to an iteration inside a period.  Nothing to do up to ``hist_from``."""
-        if self.hist_spec is None:
-            raise ValueError("no histogram: PTEngine.with_stages(..., hist=(lo, hi, nbins))")
-        if int(it) > self.iter:
-            raise ValueError("hist_sync(%d): the engine has reached iteration %d; the ring's rows beyond it are the period before's" % (int(it), self.iter))
-        self._hist_sync(it)
-
-    def _hist_sync(self, it):
-        it = int(it)
-        if it <= self.hist_iter:
-            return
-        base = ((it - 1) // self.cov_update) * self.cov_update
-        if self.hist_iter < base and self.owns_cold:
-            raise ValueError("hist_sync(%d): iterations %d..%d are no longer in the ring (it holds the period after %d); every period "
-                             "must end through update_cov" % (it, self.hist_iter + 1, base, base))
-        _lib.check(self.lib.ptmi_hist_update(self.h, self.hist_iter + 1, it))
-        self.hist_iter = it
+        self._ring_sync("hist", it)
 
     def hist_counts(self, it=None):
         """The histograms up to iteration ``it`` (default: the current one): a dict of ``counts`` uint64 [d][nbins], ``under`` / ``over``
@@ -1151,22 +1186,7 @@ class PTEngine(object):
         """Count iterations ``(pairs_iter, it]`` of every walker's cold chain into ``t["pairs"]`` (``ptmi_pairs_update``: asynchronous,
         the ring is only read).  ``it`` lies in the covariance period the ring holds; ``update_cov`` calls this at every period's end,
         so a caller only needs it for counts up to an iteration inside a period.  Nothing to do up to ``pairs_from``."""
-        if self.pairs_spec is None:
-            raise ValueError("no pair histogram: PTEngine.with_stages(..., pairs=(pairs, lo, hi, nbins))")
-        if int(it) > self.iter:
-            raise ValueError("pairs_sync(%d): the engine has reached iteration %d; the ring's rows beyond it are the period before's" % (int(it), self.iter))
-        self._pairs_sync(it)
-
-    def _pairs_sync(self, it):
-        it = int(it)
-        if it <= self.pairs_iter:
-            return
-        base = ((it - 1) // self.cov_update) * self.cov_update
-        if self.pairs_iter < base and self.owns_cold:
-            raise ValueError("pairs_sync(%d): iterations %d..%d are no longer in the ring (it holds the period after %d); every period "
-                             "must end through update_cov" % (it, self.pairs_iter + 1, base, base))
-        _lib.check(self.lib.ptmi_pairs_update(self.h, self.pairs_iter + 1, it))
-        self.pairs_iter = it
+        self._ring_sync("pairs", it)
 
     def pairs_counts(self, it=None):
         """The pair histograms up to iteration ``it`` (default: the current one): a dict of ``counts`` uint64 [npairs][nbins][nbins]
@@ -1185,22 +1205,7 @@ class PTEngine(object):
         """Fold iterations ``(diag_iter, it]`` of every walker's cold chain into ``t["diag"]`` (``ptmi_diag_update``: asynchronous, the ring
         is only read).  ``it`` lies in the covariance period the ring holds; ``update_cov`` calls this at every period's end, so a
         caller only needs it for sums up to an iteration inside a period.  Nothing to do up to ``diag_from``."""
-        if not self.diag_on:
-            raise ValueError("no diagnostics: PTEngine.with_stages(..., diag=True)")
-        if int(it) > self.iter:
-            raise ValueError("diag_sync(%d): the engine has reached iteration %d; the ring's rows beyond it are the period before's" % (int(it), self.iter))
-        self._diag_sync(it)
-
-    def _diag_sync(self, it):
-        it = int(it)
-        if it <= self.diag_iter:
-            return
-        base = ((it - 1) // self.cov_update) * self.cov_update
-        if self.diag_iter < base:
-            raise ValueError("diag_sync(%d): iterations %d..%d are no longer in the ring (it holds the period after %d); every period "
-                             "must end through update_cov" % (it, self.diag_iter + 1, base, base))
-        _lib.check(self.lib.ptmi_diag_update(self.h, self.diag_iter + 1, it, self.diag_iter - self.diag_from))
-        self.diag_iter = it
+        self._ring_sync("diag", it)
 
     def diag_moments(self, it=None):
         """The streaming sums up to iteration ``it`` (default: the current one): a dict of the planes ``c``, ``S1``, ``S2``, ``A`` [W][d],
@@ -1249,14 +1254,9 @@ class PTEngine(object):
                   eig_epochs=self.eig_epochs,
                   # eig_lag: an epoch's table that is not in force yet (its covariance is in t_cov; restore() factorizes it again)
                   eig_pending=int(self._eig_pending), eig_wait=int(self._eig_wait))
-        if self.hist_spec is not None:
-            st["hist_iter"] = self.hist_iter
-        if self.pairs_spec is not None:
-            st["pairs_iter"] = self.pairs_iter
+        st.update({r.name + "_iter": r.iter for r in self._ring})
         if self.evidence_on:
             st["ev_epochs"] = self.ev_epochs
-        if self.diag_on:
-            st["diag_iter"] = self.diag_iter
         if self.adapt_on:
             hist = self.ladder_history()
             st.update(lad_calls=self.lad_calls, lad_epochs=self.lad_epochs, lad_tries=np.asarray(self.lad_tries, dtype=np.int64),
@@ -1267,18 +1267,12 @@ class PTEngine(object):
 
     def restore(self, st):
         torch = _torch()
-        if self.hist_spec is not None and ("hist_iter" not in st or "t_hist" not in st):      # refused before anything is touched
-            raise ValueError("the checkpoint carries no histogram: it was written by a run without hist=")
-        if self.pairs_spec is not None and ("pairs_iter" not in st or "t_pairs" not in st
-                                            or tuple(np.shape(st["t_pairs"])) != tuple(self.t["pairs"].shape)):
-            raise ValueError("the checkpoint carries no pair histograms of this shape: it was written by a run without pairs= (or with "
-                             "other pairs or bins)")
+        for r in self._ring:                                          # refused before anything is touched; the histogram's shape is not looked at
+            if (r.name + "_iter" not in st or "t_" + r.name not in st
+                    or r.name != "hist" and tuple(np.shape(st["t_" + r.name])) != tuple(self.t[r.name].shape)):
+                raise ValueError(_RingReader.WORDS[r.name][3])
         if self.evidence_on and any(k not in st for k in ("ev_epochs", "t_ev_acc", "t_ev_cnt")):
             raise ValueError("the checkpoint carries no evidence accumulators: it was written by a run without evidence=True")
-        if self.diag_on and ("diag_iter" not in st or "t_diag" not in st
-                             or tuple(np.shape(st["t_diag"])) != tuple(self.t["diag"].shape)):
-            raise ValueError("the checkpoint carries no diagnostics sums of this shape: it was written by a run without diag=True (or "
-                             "with other diag_levels)")
         if self.adapt_on and any(k not in st for k in ("t_lad", "t_lad_seen", "lad_calls", "lad_epochs", "lad_tries", "lad_hist_iter",
                                                        "lad_hist_kappa", "lad_hist_planes")):
             raise ValueError("the checkpoint carries no ladder state: it was written by a run without adapt_ladder")
@@ -1305,14 +1299,10 @@ class PTEngine(object):
                     v.copy_(torch.from_numpy(np.ascontiguousarray(st["alt_" + k])).to(v.dtype))
         self.iter, self.swap_proposed = int(st["iter"]), int(st["swap_proposed"])
         self.eig_epochs = int(st["eig_epochs"])                       # (behind _eig_finish, which counts the dropped table)
-        if self.hist_spec is not None:
-            self.hist_iter = int(st["hist_iter"])
-        if self.pairs_spec is not None:
-            self.pairs_iter = int(st["pairs_iter"])
+        for r in self._ring:
+            r.iter = int(st[r.name + "_iter"])
         if self.evidence_on:
             self.ev_epochs = int(st["ev_epochs"])
-        if self.diag_on:
-            self.diag_iter = int(st["diag_iter"])
         if self.adapt_on:
             self.lad_calls, self.lad_epochs = int(st["lad_calls"]), int(st["lad_epochs"])
             self.lad_tries = [int(v) for v in st["lad_tries"]]

@@ -1069,21 +1069,26 @@ class PTSampler(object):
                 self.jumpDict[name][1] += int(dec[s0, 2] > 0.5)
 
     # ------------------------------------------------------------------ output files (:341-372, :722-766)
+    def _write_npz(self, name, data):
+        """``data`` -> <outDir>/<name>.npz, whole or not at all: written beside it, then moved onto it."""
+        tmp = os.path.join(self.outDir, name + ".tmp.npz")
+        np.savez(tmp, **data)
+        os.replace(tmp, os.path.join(self.outDir, name + ".npz"))
+
+    def _ring_upto(self, iter, read):
+        """``read(iter)`` of a stage that reads the cold chains' ring, with the engine at ``iter`` (the sampler's loops step the engine themselves)."""
+        self.engine.iter = max(self.engine.iter, int(iter))
+        return read(iter)
+
     def _write_hist(self, iter):
         """The histograms up to iteration ``iter`` (of the current covariance period) -> self.hist and <outDir>/hist.npz."""
-        self.engine.iter = max(self.engine.iter, int(iter))          # (the sampler's loops step the engine themselves)
-        self.hist = self.engine.hist_counts(iter)
-        tmp = os.path.join(self.outDir, "hist.tmp.npz")
-        np.savez(tmp, **self.hist)
-        os.replace(tmp, os.path.join(self.outDir, "hist.npz"))
+        self.hist = self._ring_upto(iter, self.engine.hist_counts)
+        self._write_npz("hist", self.hist)
 
     def _write_pairs(self, iter):
         """The pair histograms up to iteration ``iter`` (of the current covariance period) -> self.pairs2d and <outDir>/pairs.npz."""
-        self.engine.iter = max(self.engine.iter, int(iter))          # (the sampler's loops step the engine themselves)
-        self.pairs2d = self.engine.pairs_counts(iter)
-        tmp = os.path.join(self.outDir, "pairs.tmp.npz")
-        np.savez(tmp, **self.pairs2d)
-        os.replace(tmp, os.path.join(self.outDir, "pairs.npz"))
+        self.pairs2d = self._ring_upto(iter, self.engine.pairs_counts)
+        self._write_npz("pairs", self.pairs2d)
 
     def _write_evidence(self):
         """The estimates from the samples so far, with the moments they come from -> self.evidence and <outDir>/evidence.npz."""
@@ -1092,9 +1097,7 @@ class PTSampler(object):
         ev = estimates(mo["betas"], mo["n"], mo["shift"], mo["s1"], mo["s2"], mo["m"], mo["es"])
         ev.update(mo)
         self.evidence = ev
-        tmp = os.path.join(self.outDir, "evidence.tmp.npz")
-        np.savez(tmp, **ev)
-        os.replace(tmp, os.path.join(self.outDir, "evidence.npz"))
+        self._write_npz("evidence", ev)
 
     def _write_ladder(self):
         """The ladder in force, the one the run started with and every update so far -> self.ladder_adapted and <outDir>/ladder.npz."""
@@ -1103,22 +1106,17 @@ class PTSampler(object):
         la = dict(ladder=np.array(eng.ladder), ladder0=np.array(eng.ladder0), until=np.int64(eng.adapt_until), iter=hist["iter"],
                   kappa=hist["kappa"], A=hist["A"], history=hist["ladder"])
         self.ladder_adapted = la
-        tmp = os.path.join(self.outDir, "ladder.tmp.npz")
-        np.savez(tmp, **la)
-        os.replace(tmp, os.path.join(self.outDir, "ladder.npz"))
+        self._write_npz("ladder", la)
 
     def _write_diagnostics(self, iter):
         """The estimates up to iteration ``iter`` (of the current covariance period), with the sums they come from -> self.diagnostics and
         <outDir>/diagnostics.npz."""
-        self.engine.iter = max(self.engine.iter, int(iter))          # (the sampler's loops step the engine themselves)
-        mom = self.engine.diag_moments(iter)
+        mom = self._ring_upto(iter, self.engine.diag_moments)
         from .diagnostics import estimates
         est = estimates(mom)
         est.update(mom)
         self.diagnostics = est
-        tmp = os.path.join(self.outDir, "diagnostics.tmp.npz")
-        np.savez(tmp, **est)
-        os.replace(tmp, os.path.join(self.outDir, "diagnostics.npz"))
+        self._write_npz("diagnostics", est)
 
     def writeOutput(self, iter):
         if self.chain_diagnostics and not self.engine.diag_on:
