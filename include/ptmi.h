@@ -743,6 +743,38 @@ int ptmi_pairs_attach(ptmi_handle h, uint64_t *counts, const int32_t *pairs, int
                       int32_t nbins);
 int ptmi_pairs_update(ptmi_handle h, int64_t iter_lo, int64_t iter_hi);
 
+/* Thinned SAMPLES of EVERY cold chain, kept on the device (csrc/ptmi_samples.hip): what corner plots, derived parameters, posterior
+ * predictive draws and importance reweighting take, where the calls above yield fixed summaries.  The reference keeps the thinned rows
+ * of its one chain on the host (updateChains, :331-335); these calls keep a bounded set of snapshots of all nwalkers cold chains, read
+ * from the ring that ptmi_hist_update reads.  The caller owns the schedule (which iteration goes to which slot:
+ * ptmcmcsampler_amd/samples.py SlotPlan); the library gathers.  For walker w, iteration E + k of the period the ring holds and slot s:
+ *
+ *     r = k                                       without AMflag: every row is stored
+ *     r = the nearest k' <= k with NEW | KEY      with AMflag (ptmi_am_expand's rule; ring row 1 of a period is a KEY row, so the
+ *                                                 walk back never leaves the period)
+ *     rows[s][w][i]     = the element of parameter i in ring row r % cov_update        (k == cov_update sits in ring row 0)
+ *     aux[s][w][0 .. 1] = AMaux[w][k % cov_update][0 .. 1]                             lnL and lp of iteration E + k itself: AMaux
+ *                                                                                     is written at every iteration, stored or not
+ *
+ * moved as 64-bit words: NaN, infinities and -0.0 arrive bit for bit.
+ * rows: DEVICE double [nslots][W][ndim] in PARAMETER order whatever the ring's row format (ptmi_am_row_format); aux: DEVICE double
+ * [nslots][W][2] (lnL, lp), or NULL; both caller-owned, 8-byte aligned.  ptmi_samples_attach (once per handle): 1 <= nslots <= 65535;
+ * PTMI_EINVAL, the message says which: NULL or misaligned rows, misaligned aux, aux on a handle without AMaux, nslots out of range, a
+ * second attach ("already attached").  State lives in the handle and is freed with it: ptmi_config and ptmi_buffers are unchanged,
+ * and a handle that never attaches launches what it launched before.
+ * ptmi_samples_take gathers n (iteration, slot) pairs from the handle's CURRENT ring (ptmi_set_am_buffers): iters HOST [n] strictly
+ * ascending and all in one covariance period, E < iters[0], iters[n - 1] <= E + cov_update with E = ((iters[n - 1] - 1) / cov_update) *
+ * cov_update; slots HOST [n], distinct, 0 <= slot < nslots, so no two pairs of a call write the same cell.  PTMI_EINVAL, the message says
+ * which: before ptmi_samples_attach, n < 0, iterations that are not ascending, a repeated slot, a slot out of range, a range that
+ * crosses a period.  n == 0, or a handle with temp0 != 0: PTMI_OK, nothing done (as ptmi_update_cov).  The caller takes an iteration
+ * before the ring wraps; the ring is only read.  The host arrays are consumed before the call returns (the pairs travel as kernel
+ * arguments, 256 per launch): nothing on the host has to outlive the call.  One wave per (pair, walker); asynchronous on the handle's
+ * stream, no host synchronisation, no atomics. */
+int ptmi_samples_attach(ptmi_handle h, double *rows /* dev [nslots][W][ndim], PARAMETER order, caller-owned */,
+                        double *aux /* dev [nslots][W][2] (lnL, lp) or NULL */, int32_t nslots);
+int ptmi_samples_take(ptmi_handle h, const int64_t *iters /* host [n], strictly ascending */,
+                      const int32_t *slots /* host [n], distinct, 0 <= slot < nslots */, int32_t n);
+
 /* Self-test hooks used by the parity tests: evaluate the device's deterministic math on
  * n inputs (op: 0 log, 1 exp, 2 cos2pi, 3 sqrt, 4 reciprocal-free divide a/b with b=in2). */
 int ptmi_selftest_math(int device, int op, const double *in, const double *in2, double *out, int64_t n);

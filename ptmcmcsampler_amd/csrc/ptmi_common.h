@@ -257,6 +257,8 @@ struct ptmi_engine {
     struct ptmi_ladder_state *ladder;
     // joint histograms of parameter pairs from the cold chains (ptmi_pairs.hip): the state of ptmi_pairs_attach, or nullptr
     struct ptmi_pairs_state *pairs;
+    // thinned snapshots of the cold chains kept on the device (ptmi_samples.hip): the state of ptmi_samples_attach, or nullptr
+    struct ptmi_samples_state *samples;
 };
 enum { PTMI_GJ_NONE = 0, PTMI_GJ_PENDING = 1 /* proposals made, ptmi_gj_begin not yet called */, PTMI_GJ_ROUNDS = 2, PTMI_GJ_DONE = 3 };
 // the split path's refusals for gradient jumps (0: served; else the code, with the message set)
@@ -282,6 +284,8 @@ void ptmi_diag_free(ptmi_engine *h);
 void ptmi_ladder_free(ptmi_engine *h);
 // pair histograms (ptmi_pairs.hip): frees h->pairs, for ptmi_destroy
 void ptmi_pairs_free(ptmi_engine *h);
+// snapshots of the cold chains (ptmi_samples.hip): frees h->samples, for ptmi_destroy
+void ptmi_samples_free(ptmi_engine *h);
 // swap (ptmi_swap.hip): bytes of a record of d_pre (SwapPre), for ptmi_create
 constexpr size_t PTMI_SWAP_PRE_BYTES = 48;
 

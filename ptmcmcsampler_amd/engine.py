@@ -104,7 +104,9 @@ class _RingReader(object):
              "pairs": ("pair histogram", "pairs=(pairs, lo, hi, nbins)", "counted",
                        "the checkpoint carries no pair histograms of this shape: it was written by a run without pairs= (or with other pairs or bins)"),
              "diag": ("diagnostics", "diag=True", "folded",
-                      "the checkpoint carries no diagnostics sums of this shape: it was written by a run without diag=True (or with other diag_levels)")}
+                      "the checkpoint carries no diagnostics sums of this shape: it was written by a run without diag=True (or with other diag_levels)"),
+             "samples": ("sample buffer", "samples=slots", "taken",
+                         "the checkpoint carries no sample buffer of this shape: it was written by a run without samples= (or with other slots, every or samples_from)")}
 
     def __init__(self, name, first, update):
         self.name, self.first, self.iter, self.update = name, first, first, update
@@ -263,6 +265,17 @@ class PTEngine(CallbackPath):
     returns the planes, ``diagnostics(it=None)`` the estimates: Gelman-Rubin ``rhat``, ``tau`` (batch means pooled over the walkers),
     ``tau_walkers``, ``ess``.  The ring is only read: the chains are the same bits with and without.  ``t["diag"]`` and ``diag_iter`` are
     part of ``checkpoint()``.  Refused on an engine that owns no cold ring (``temp0 != 0``).
+    ``with_stages(..., samples=slots | dict(slots=, every=1), samples_from=None)``: thinned SAMPLES of every walker's cold chain, kept on
+    the device (include/ptmi.h ``ptmi_samples_*``, samples.py): a buffer of ``slots`` snapshots ``[W][ndim]`` in parameter order, each row
+    with its lnL and lp (``keep_lnl=True``), gathered from the AM ring whatever the ring mode.  The candidates are the iterations
+    ``samples_from + every * m`` (default ``samples_from = burn``); when the buffer is full every other snapshot is let go and the stride
+    doubles (``SlotPlan``), so the held snapshots are evenly spaced over the whole run so far, between ``slots // 2`` and ``slots`` of
+    them, and the run's length need not be known.  ``update_cov`` takes the period that ends before it touches anything else;
+    ``samples_sync(it)`` takes up to an iteration inside a period, ``samples(it=None)`` returns the held snapshots by iteration (host
+    arrays), ``samples_device()`` the same as device tensors.  The ring is only read: the chains are the same bits with and without.
+    ``t["samples"]``, ``t["samples_aux"]``, ``samples_iter`` and the plan's state are part of ``checkpoint()``, with ``every`` and
+    ``samples_from``: ``restore()`` refuses a checkpoint whose buffer was filled on another schedule.  Idle on an engine that
+    owns no cold ring.
     ``with_stages(..., adapt_ladder=True | dict(every=10, kappa=2.0, t0=10.0, until=None))``: the temperature ladder adapts during burn-in
     from EVERY walker's accepted swaps (include/ptmi.h ``ptmi_ladder_*``).  ``swap(it)`` counts the swap epochs of a window by the parity
     of the pairs they try (``swap_mode="oddeven"``: epoch ``it // tskip`` tries the pairs of its parity, so ``every`` is even; the sweep
@@ -287,6 +300,8 @@ class PTEngine(CallbackPath):
     _hist_from = None
     _pairs = None
     _pairs_from = None
+    _samples = None
+    _samples_from = None
     _ev = False
     _ev_from = None
     _ev_every = 1
@@ -319,7 +334,7 @@ class PTEngine(CallbackPath):
     @classmethod
     def with_stages(cls, *args, jumps_with_grad=False, aux=None, logl_in_support=False, hist=None, hist_from=None,
                     evidence=False, evidence_from=None, evidence_every=1, diag=False, diag_from=None, diag_batch=None, diag_levels=None,
-                    adapt_ladder=None, pairs=None, pairs_from=None, **kw):
+                    adapt_ladder=None, pairs=None, pairs_from=None, samples=None, samples_from=None, **kw):
         """``PTEngine(*args, **kw)`` with the stages of the composed ``_jump`` on the callback path (see the class docstring):
         ``jumps_with_grad=True`` lets ``jumps=`` stand beside ``grad_weights`` in one cycle, ``aux=[func, ...]`` are the auxiliary jumps,
         ``logl_in_support=True`` hands the likelihood callback only the rows whose prior is not -inf (``eval_callback``),
@@ -329,7 +344,9 @@ class PTEngine(CallbackPath):
         for R-hat and ESS (``diagnostics``), ``adapt_ladder=True`` or ``dict(every=10, kappa=2.0, t0=10.0, until=None)`` adapts the
         temperature ladder during burn-in from every walker's accepted swaps (``ladder_history``),
         ``pairs=(pairs, lo, hi, nbins)`` with ``pairs_from`` accumulates the joint histograms of parameter pairs of every cold chain
-        (``pairs_counts``; ``pairs``: int ``[npairs][2]`` or ``{"params": [indices]}`` = every pair of the list).
+        (``pairs_counts``; ``pairs``: int ``[npairs][2]`` or ``{"params": [indices]}`` = every pair of the list),
+        ``samples=slots`` or ``dict(slots=, every=1)`` with ``samples_from`` keeps evenly spaced snapshots of every cold chain on the device
+        (``samples``, ``samples_device``).
         The plain constructor keeps the parameters it had (tests/test_gj_groups.py holds them to the letter) and its refusals."""
         self = cls.__new__(cls)
         self.jumps_with_grad = bool(jumps_with_grad)
@@ -337,6 +354,7 @@ class PTEngine(CallbackPath):
         self.logl_in_support = bool(logl_in_support)
         self._hist, self._hist_from = hist, hist_from
         self._pairs, self._pairs_from = pairs, pairs_from
+        self._samples, self._samples_from = samples, samples_from
         self._ev, self._ev_from, self._ev_every = bool(evidence), evidence_from, evidence_every
         self._diag, self._diag_from, self._diag_batch, self._diag_levels = bool(diag), diag_from, diag_batch, diag_levels
         self._adapt = adapt_ladder
@@ -383,6 +401,13 @@ class PTEngine(CallbackPath):
             raise ValueError("diag_from= / diag_batch= / diag_levels= go with diag=True")
         self._ring_reader("diag", self.diag_on, self._diag_from, burn,
                           lambda eng, lo, hi, n: _lib.check(eng.lib.ptmi_diag_update(eng.h, lo, hi, n)))
+        # thinned snapshots of the cold chains, kept on the device (with_stages(samples=slots | dict(slots=, every=), samples_from=...); see the class docstring)
+        self.samples_spec = self._splan = None
+        if self._samples is not None:
+            from .samples import SlotPlan, samples_spec
+            self.samples_spec = samples_spec(self._samples)
+            self._splan = SlotPlan(*self.samples_spec)
+        self._ring_reader("samples", self.samples_spec is not None, self._samples_from, burn, PTEngine._samples_take)
         # the ladder's summaries for the log-evidence (with_stages(evidence=True, evidence_from=..., evidence_every=...); see the class docstring)
         self.evidence_on = bool(self._ev)
         if self.evidence_on:
@@ -641,6 +666,14 @@ class PTEngine(CallbackPath):
             # carry it by itself
             self.t["diag"] = z((2 * self.diag_levels + 3, W, d))
             _lib.check(self.lib.ptmi_diag_attach(self.h, C.c_void_p(self.t["diag"].data_ptr()), self.diag_levels, self.diag_batch))
+        if self.samples_spec is not None:
+            # double [slots][W][d] in parameter order and, with keep_lnl on the block that owns the cold ring, [slots][W][2] (lnL, lp);
+            # in self.t: checkpoints carry them by themselves
+            self.t["samples"] = z((self.samples_spec[0], W, d))
+            self.t["samples_aux"] = z((self.samples_spec[0], W, 2)) if self.t["AMaux"] is not None else None
+            _lib.check(self.lib.ptmi_samples_attach(self.h, C.c_void_p(self.t["samples"].data_ptr()),
+                                                    C.c_void_p(self.t["samples_aux"].data_ptr()) if self.t["samples_aux"] is not None else None,
+                                                    self.samples_spec[0]))
         self.de_on = False
         self.de_head = 0
         self.iter = 0
@@ -1080,6 +1113,7 @@ class PTEngine(CallbackPath):
     hist_from, hist_iter = _ring_attr("hist", "first"), _ring_attr("hist", "iter")
     pairs_from, pairs_iter = _ring_attr("pairs", "first"), _ring_attr("pairs", "iter")
     diag_from, diag_iter = _ring_attr("diag", "first"), _ring_attr("diag", "iter")
+    samples_from, samples_iter = _ring_attr("samples", "first"), _ring_attr("samples", "iter")
 
     # ------------------------------------------------------------------ posterior histograms
     def hist_sync(self, it):
@@ -1147,6 +1181,56 @@ class PTEngine(CallbackPath):
         out.update(first_iter=mom["first_iter"], last_iter=mom["last_iter"])
         return out
 
+    # ------------------------------------------------------------------ thinned samples
+    def _samples_take(self, lo, hi, n_done):
+        """The samples reader's update: the plan's snapshots among iterations ``lo .. hi`` in one ``ptmi_samples_take``."""
+        if not self.owns_cold:
+            return                                                    # no cold ring: idle, and the plan holds nothing
+        plan = self._splan
+        before = (plan.level, plan.slot_iter.copy())
+        pairs = plan.take(self.samples_from, lo, hi)
+        if pairs:
+            it = np.ascontiguousarray([i for i, _ in pairs], dtype=np.int64)
+            sl = np.ascontiguousarray([s for _, s in pairs], dtype=np.int32)
+            try:
+                _lib.check(self.lib.ptmi_samples_take(self.h, it.ctypes.data_as(C.POINTER(C.c_int64)), sl.ctypes.data_as(C.POINTER(C.c_int32)), len(pairs)))
+            except Exception:
+                plan.level, plan.slot_iter[:] = before                # nothing was gathered: the plan stays where the reader's iteration is
+                raise
+
+    def samples_sync(self, it):
+        """Take the plan's snapshots among iterations ``(samples_iter, it]`` of every walker's cold chain into ``t["samples"]``
+        (``ptmi_samples_take``: asynchronous, the ring is only read).  ``it`` lies in the covariance period the ring holds; ``update_cov``
+        calls this at every period's end, so a caller only needs it for snapshots up to an iteration inside a period.  Nothing to do up
+        to ``samples_from``."""
+        self._ring_sync("samples", it)
+
+    def samples_device(self, it=None):
+        """The held snapshots up to iteration ``it`` (default: the current one) as device tensors, no copy to the host: ``(x [n][W][d],
+        aux [n][W][2] (lnL, lp) or None, iters int64 [n] (host))``, by ascending iteration.  The tensors are gathered from ``t["samples"]``
+        on the engine's stream; a later ``run`` does not change them."""
+        torch = _torch()
+        self.samples_sync(self.iter if it is None else it)
+        iters, slots = self._splan.held()
+        with torch.cuda.stream(self.stream):
+            idx = torch.from_numpy(slots).to(self.device)
+            aux = self.t["samples_aux"]
+            return self.t["samples"][idx], (aux[idx] if aux is not None else None), iters
+
+    def samples(self, it=None):
+        """The held snapshots up to iteration ``it`` (default: the current one), by ascending iteration: a dict of ``x`` [n][W][d]
+        (parameter order), ``iters`` [n], ``every``, ``stride`` (= ``every << level``: the iterations between two snapshots), ``first_iter`` /
+        ``last_iter`` (the iterations the snapshots are spread over), ``nwalkers``, and, with ``keep_lnl=True``, ``lnlike`` [n][W] and
+        ``lnprob`` [n][W] = ``lnlike / temps_mh[0] + lp`` (computed as the sampler's chain files compute it: ``(1 / temps_mh[0]) * lnlike + lp``)."""
+        x, aux, iters = self.samples_device(it)
+        out = dict(x=x.cpu().numpy(), iters=iters.copy(), every=np.int64(self._splan.every), stride=np.int64(self._splan.stride),
+                   first_iter=np.int64(self.samples_from + 1), last_iter=np.int64(self.samples_iter), nwalkers=np.int64(self.W))
+        if aux is not None:
+            a = aux.cpu().numpy()
+            out["lnlike"] = np.ascontiguousarray(a[..., 0])
+            out["lnprob"] = (1.0 / self.temps_mh[0]) * a[..., 0] + a[..., 1]
+        return out
+
     def update_de(self, it_done=None):
         if self.owns_cold and self.t["DE"] is not None:
             if it_done is not None:
@@ -1173,6 +1257,9 @@ class PTEngine(CallbackPath):
                   # eig_lag: an epoch's table that is not in force yet (its covariance is in t_cov; restore() factorizes it again)
                   eig_pending=int(self._eig_pending), eig_wait=int(self._eig_wait))
         st.update({r.name + "_iter": r.iter for r in self._ring})
+        if self._splan is not None:
+            st.update(samples_level=self._splan.level, samples_slot_iter=self._splan.slot_iter.copy(), samples_every=self._splan.every,
+                      samples_from=self.samples_from)
         if self.evidence_on:
             st["ev_epochs"] = self.ev_epochs
         if self.adapt_on:
@@ -1189,6 +1276,11 @@ class PTEngine(CallbackPath):
             if (r.name + "_iter" not in st or "t_" + r.name not in st
                     or r.name != "hist" and tuple(np.shape(st["t_" + r.name])) != tuple(self.t[r.name].shape)):
                 raise ValueError(_RingReader.WORDS[r.name][3])
+        if self._splan is not None and (any(k not in st for k in ("samples_level", "samples_slot_iter", "samples_every", "samples_from"))
+                                        or np.shape(st["samples_slot_iter"]) != (self._splan.nslots,)
+                                        or int(st["samples_every"]) != self._splan.every or int(st["samples_from"]) != self.samples_from
+                                        or (self.t["samples_aux"] is not None) != ("t_samples_aux" in st)):
+            raise ValueError(_RingReader.WORDS["samples"][3])
         if self.evidence_on and any(k not in st for k in ("ev_epochs", "t_ev_acc", "t_ev_cnt")):
             raise ValueError("the checkpoint carries no evidence accumulators: it was written by a run without evidence=True")
         if self.adapt_on and any(k not in st for k in ("t_lad", "t_lad_seen", "lad_calls", "lad_epochs", "lad_tries", "lad_hist_iter",
@@ -1219,6 +1311,9 @@ class PTEngine(CallbackPath):
         self.eig_epochs = int(st["eig_epochs"])                       # (behind _eig_finish, which counts the dropped table)
         for r in self._ring:
             r.iter = int(st[r.name + "_iter"])
+        if self._splan is not None:
+            self._splan.level = int(st["samples_level"])
+            self._splan.slot_iter[:] = np.asarray(st["samples_slot_iter"], dtype=np.int64)
         if self.evidence_on:
             self.ev_epochs = int(st["ev_epochs"])
         if self.adapt_on:

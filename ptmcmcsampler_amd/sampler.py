@@ -41,6 +41,13 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
   ``{"params": [indices]}`` = every pair of the list; ``<outDir>/pairs.npz`` (``counts`` [npairs][nbins][nbins], ``outside``, ``pairs``,
   ``edges``, ``first_iter``, ``last_iter``, ``nwalkers``) at every save, ``sampler.pairs2d`` after the run (``pairs.credible_levels``
   gives the contour thresholds); ``checkpoint=True`` runs resume the counts, a replay of chain files cannot;
+* ``sampler.posterior_samples = slots`` or ``{"slots": n, "every": k}`` (before ``sample()``; any likelihood, any path): thinned SAMPLES of
+  EVERY walker's cold chain after ``burn`` -- what corner / getdist / ChainConsumer, derived parameters and reweighting take -- kept on the
+  device in a buffer of ``slots`` snapshots that doubles its stride whenever it is full, so the snapshots stay evenly spaced over a run
+  of any length (``PTEngine.with_stages(samples=...)``, samples.py ``SlotPlan``, csrc/ptmi_samples.hip).  ``<outDir>/samples.npz`` (``x``
+  [n][nwalkers][ndim], ``lnlike``, ``lnprob`` [n][nwalkers], ``iters``, ``every``, ``stride``, ``first_iter``, ``last_iter``, ``nwalkers``) at
+  every save where the held set has changed and at the end of the run, ``sampler.samples`` after the run (``samples.flat`` gives one
+  array per quantity); ``checkpoint=True`` runs resume the buffer, a replay of chain files cannot;
 * ``sampler.chain_diagnostics = True`` or ``{"batch": b0, "levels": L, "stop_ess": N, "stop_rhat": r}`` (before ``sample()``; any likelihood,
   any path): Gelman-Rubin R-hat, the integrated autocorrelation time and the effective sample size of every parameter from EVERY
   walker's cold chain after ``burn`` -- where the ``neff`` rule (PTMCMCSampler.py:510-521) looks at one kept chain.  The device streams the
@@ -183,6 +190,13 @@ class PTSampler(object):
     # after the run.  pairs: int [npairs][2] or {"params": [indices]}; lo / hi: scalars or [ndim].  An attribute for the same reason
     posterior_pairs = None
     pairs2d = None
+    # s.posterior_samples = slots, or {"slots": n, "every": k} (before sample()): thinned SAMPLES of EVERY walker's cold chain after burn,
+    # kept on the device in a buffer of `slots` evenly spaced snapshots that thins itself as the run grows (PTEngine.with_stages(samples=...),
+    # samples.py): <outDir>/samples.npz whenever the held set has changed at a save and at the end of the run, s.samples after the run.
+    # An attribute for the same reason
+    posterior_samples = None
+    samples = None
+    _last_save = False
     # s.log_evidence = True, or {"every": k} (before sample()): ln Z from the ladder of EVERY walker -- per-temperature lnL moments taken on
     # the device behind every (k-th) swap after burn (PTEngine.with_stages(evidence=True)): <outDir>/evidence.npz at every save, s.evidence
     # after the run.  An attribute for the same reason as batched_aux
@@ -440,6 +454,10 @@ class PTSampler(object):
             raise NotImplementedError("posterior_pairs counts every walker's cold chain on the device; chain files hold the kept walkers' "
                                       "thinned rows only, so a replayed run cannot continue the counts: resume from a device checkpoint "
                                       "(PTSampler(..., checkpoint=True) from the first run on)")
+        if self._replaying and self.posterior_samples is not None:
+            raise NotImplementedError("posterior_samples keeps snapshots of every walker's cold chain on the device; chain files hold the kept "
+                                      "walkers' thinned rows only, so a replayed run cannot continue the buffer: resume from a device checkpoint "
+                                      "(PTSampler(..., checkpoint=True) from the first run on)")
         if self._replaying and self.log_evidence:
             raise NotImplementedError("log_evidence sums the lnL of every walker's whole ladder on the device; chain files hold the kept "
                                       "walkers' thinned rows only, so a replayed run cannot continue the sums: resume from a device checkpoint "
@@ -552,7 +570,7 @@ class PTSampler(object):
             split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
             jumps=[(f, n) for f, n in stage_list] if stage_list else None,
             jumps_with_grad=bool(stage_list) and sum(self._grad_weights) > 0, aux=list(self._batched_aux) or None,
-            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **({"pairs": self.posterior_pairs} if self.posterior_pairs is not None else {}), **self._evidence_kw(), **self._diag_kw(), **self._adapt_kw(),
+            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **({"pairs": self.posterior_pairs} if self.posterior_pairs is not None else {}), **({"samples": self.posterior_samples} if self.posterior_samples is not None else {}), **self._evidence_kw(), **self._diag_kw(), **self._adapt_kw(),
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     def _evidence_kw(self):
@@ -698,7 +716,11 @@ class PTSampler(object):
                         self.Niter = end
             it = end + 1
         eng.iter = self.Niter
-        self.writeOutput(self.Niter)
+        self._last_save = True                                        # (samples.npz is written whether or not the held set has changed)
+        try:
+            self.writeOutput(self.Niter)
+        finally:
+            self._last_save = False
         if self.verbose:
             print(message)
 
@@ -759,6 +781,8 @@ class PTSampler(object):
                                   # (the pair histograms' pairs and bins, only where there are some)
                                   *((("pairs", eng.pairs_from, eng.pairs_spec[3], eng.pairs_spec[0].tobytes()), *eng.pairs_spec[1:3])
                                     if eng.pairs_spec is not None else ()),
+                                  # (the sample buffer's slots and spacing, only where there is one)
+                                  *((("samples", eng.samples_from) + tuple(eng.samples_spec),) if eng.samples_spec is not None else ()),
                                   # (the evidence stage's sampling, only where it is on)
                                   *((("evidence", eng.evidence_from, eng.evidence_every),) if eng.evidence_on else ()),
                                   # (the diagnostics stage's batches, only where it is on)
@@ -1090,6 +1114,16 @@ class PTSampler(object):
         self.pairs2d = self._ring_upto(iter, self.engine.pairs_counts)
         self._write_npz("pairs", self.pairs2d)
 
+    def _write_samples(self, iter, always=False):
+        """The held snapshots up to iteration ``iter`` (of the current covariance period) -> self.samples and, where the held set has
+        changed since the last write (or ``always``), <outDir>/samples.npz."""
+        eng = self.engine
+        self._ring_upto(iter, eng.samples_sync)
+        held = eng._splan.held()[0]
+        if always or self.samples is None or not np.array_equal(held, self.samples["iters"]):
+            self.samples = eng.samples(iter)
+            self._write_npz("samples", self.samples)
+
     def _write_evidence(self):
         """The estimates from the samples so far, with the moments they come from -> self.evidence and <outDir>/evidence.npz."""
         from .evidence import estimates
@@ -1139,6 +1173,10 @@ class PTSampler(object):
             raise ValueError("posterior_pairs was set after the engine was built: set it before the first sample()")
         if self.engine.pairs_spec is not None and iter > 0:
             self._write_pairs(iter)                                   # the same
+        if self.posterior_samples is not None and self.engine.samples_spec is None:
+            raise ValueError("posterior_samples was set after the engine was built: set it before the first sample()")
+        if self.engine.samples_spec is not None and iter > 0:
+            self._write_samples(iter, always=self._last_save)         # the same; only where the held set has changed, and at the run's end
         if iter // self.thin >= self.ind_next_write:
             self._counters()
             self._writeToFile(iter)
