@@ -775,6 +775,42 @@ int ptmi_samples_attach(ptmi_handle h, double *rows /* dev [nslots][W][ndim], PA
 int ptmi_samples_take(ptmi_handle h, const int64_t *iters /* host [n], strictly ascending */,
                       const int32_t *slots /* host [n], distinct, 0 <= slot < nslots */, int32_t n);
 
+/* The BEST-FIT row of EVERY cold chain over ALL iterations (csrc/ptmi_best.hip): the maximum a posteriori (MAP) and the maximum
+ * likelihood (ML) point -- the reference value of a corner plot, the start of an optimiser or a Fisher estimate, the lnL_max of an
+ * information criterion.  They replace the arg-max a user of the reference takes over the lnprob / lnlike columns of the chain file
+ * that _writeToFile writes (chain[np.argmax(chain[:, -4])], chain[np.argmax(chain[:, -3])]): that file holds the thinned rows of one
+ * chain, these calls see every iteration of all nwalkers cold chains, read from the ring that ptmi_hist_update reads.  Per walker w two
+ * planes keep a running best each, with the score
+ *
+ *     plane 0 (MAP):  s = beta0 * lnL + lp        the product rounded, then the sum: no fused multiply-add (the lnprob of the chain files)
+ *     plane 1 (ML):   s = lnL
+ *
+ * lnL, lp = AMaux[w][k % cov_update][0 .. 1] of iteration E + k itself (AMaux is written at every iteration, stored or not).  Going
+ * through the iterations in ascending order a candidate replaces the held best iff s is not NaN AND (nothing is held OR s > held), the
+ * strict IEEE comparison: the earliest iteration with the maximum wins, 0.0 and -0.0 tie, a NaN never wins and never poisons, -inf
+ * wins only against "nothing held" -- so the state does not depend on how a run is cut into calls.  Where plane p of walker w improves:
+ *
+ *     rows[p][w][i]      = the element of parameter i in ring row r % cov_update, r = k without AMflag, else the nearest k' <= k with
+ *                          NEW | KEY (ptmi_am_expand's rule, clamped to the period; k == cov_update sits in ring row 0)
+ *     val[p][w][0 .. 2]  = s, lnL, lp
+ *     iters[p][w]        = E + k
+ *
+ * rows, lnL and lp moved as 64-bit words: payloads arrive as they were.
+ * rows: DEVICE double [2][W][ndim] in PARAMETER order whatever the ring's row format (ptmi_am_row_format); val: DEVICE double
+ * [2][W][3]; iters: DEVICE int64 [2][W], set to -1 (= nothing held) by the caller; all caller-owned, 8-byte aligned.  ptmi_best_attach
+ * (once per handle): PTMI_EINVAL, the message says which: NULL or misaligned rows / val / iters, a handle without AMaux, beta0 not
+ * finite or not positive, a second attach ("already attached").  State lives in the handle and is freed with it: ptmi_config and
+ * ptmi_buffers are unchanged, and a handle that never attaches launches what it launched before.
+ * ptmi_best_update takes iterations iter_lo .. iter_hi of the handle's CURRENT ring (ptmi_set_am_buffers), all in one covariance
+ * period: E < iter_lo, iter_hi <= E + cov_update with E = ((iter_hi - 1) / cov_update) * cov_update.  PTMI_EINVAL: before
+ * ptmi_best_attach, a range that crosses a period, a handle with no AM buffer.  iter_hi < iter_lo, or a handle with temp0 != 0:
+ * PTMI_OK, nothing launched (as ptmi_update_cov).  The caller takes an iteration before the ring wraps; the ring is only read
+ * (16 * W * (iter_hi - iter_lo + 1) bytes), at most 2 * W * (ndim + 4) * 8 bytes are written.  One wave per walker, one launch;
+ * asynchronous on the handle's stream, no host synchronisation, no atomics. */
+int ptmi_best_attach(ptmi_handle h, double *rows /* dev [2][W][ndim], PARAMETER order, caller-owned */,
+                     double *val /* dev [2][W][3]: score, lnL, lp */, int64_t *iters /* dev [2][W], -1 = nothing held */, double beta0);
+int ptmi_best_update(ptmi_handle h, int64_t iter_lo, int64_t iter_hi);
+
 /* Self-test hooks used by the parity tests: evaluate the device's deterministic math on
  * n inputs (op: 0 log, 1 exp, 2 cos2pi, 3 sqrt, 4 reciprocal-free divide a/b with b=in2). */
 int ptmi_selftest_math(int device, int op, const double *in, const double *in2, double *out, int64_t n);

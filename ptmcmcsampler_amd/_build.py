@@ -99,6 +99,7 @@ def build(force=False, verbose=False, jobs=None):
             (os.path.join(CSRC, "ptmi_ladder.hip"), os.path.join(OBJ, "ladder.o"), []),       # the temperature ladder adapted from every walker's accepted swaps
             (os.path.join(CSRC, "ptmi_pairs.hip"), os.path.join(OBJ, "pairs.o"), []),         # joint histograms of parameter pairs of the cold chains from the AM ring
             (os.path.join(CSRC, "ptmi_samples.hip"), os.path.join(OBJ, "samples.o"), []),     # thinned snapshots of every cold chain from the AM ring, kept on the device
+            (os.path.join(CSRC, "ptmi_best.hip"), os.path.join(OBJ, "best.o"), []),           # the best-fit (MAP / ML) row of every cold chain over all iterations, from the AM ring
             (os.path.join(CSRC, "ptmi_dense_rows.hip"), os.path.join(OBJ, "dense_rows.o"), [])]   # ... and the built-in dense Gaussian / priors over rows
     for g, e in sorted(shapes(), key=lambda s: -s[0] * s[1]):       # biggest units first
         for fam in (1, 0, 2, 3):

@@ -62,6 +62,7 @@ SYMBOLS = (
     "ptmi_ladder_attach", "ptmi_ladder_update", "ptmi_ladder_publish", "ptmi_ladder_read",
     "ptmi_pairs_attach", "ptmi_pairs_update",
     "ptmi_samples_attach", "ptmi_samples_take",
+    "ptmi_best_attach", "ptmi_best_update",
     "ptmi_am_flags_ok", "ptmi_am_expand", "ptmi_test_replay",
     "ptmi_selftest_math", "ptmi_selftest_philox", "ptmi_malloc", "ptmi_free", "ptmi_memcpy_h2d", "ptmi_memcpy_d2h",
     "ptmi_memset", "ptmi_timer_start", "ptmi_timer_stop_ms",
@@ -156,10 +157,11 @@ def load():
               ptmi_ladder_publish=[H], ptmi_ladder_read=[H, _dp, _dp, _dp],
               ptmi_pairs_attach=[H, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, _dp, _dp, C.c_int32], ptmi_pairs_update=[H, C.c_int64, C.c_int64],
               ptmi_samples_attach=[H, C.c_void_p, C.c_void_p, C.c_int32], ptmi_samples_take=[H, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32],
+              ptmi_best_attach=[H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double], ptmi_best_update=[H, C.c_int64, C.c_int64],
               ptmi_last_gj_launch=[H] + [C.POINTER(C.c_int32)] * 4)
     for n, at in cj.items():
         if SO == os.environ.get("PTMI_LIB") and not hasattr(L, n):
-            continue                                  # an older build for an A/B measurement: no custom-jump, auxiliary, support, histogram, evidence, diagnostics, ladder, pair-histogram or snapshot stage, no gradient-jump launch report (using it raises)
+            continue                                  # an older build for an A/B measurement: no custom-jump, auxiliary, support, histogram, evidence, diagnostics, ladder, pair-histogram, snapshot or best-fit stage, no gradient-jump launch report (using it raises)
         getattr(L, n).argtypes = at
     L.ptmi_selftest_math.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     L.ptmi_selftest_philox.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64]

@@ -477,6 +477,7 @@ int ptmi_destroy(ptmi_handle h)
     ptmi_ladder_free(h);
     ptmi_pairs_free(h);
     ptmi_samples_free(h);
+    ptmi_best_free(h);
     (void)hipFree(h->d_gj_tab); (void)hipFree(h->d_gj_scr); (void)hipFree(h->d_gj_scal); (void)hipFree(h->d_gj_order); (void)hipFree(h->d_gj_bucket);
     if (h->side) { (void)hipStreamDestroy(h->side); (void)hipEventDestroy(h->side_go); (void)hipEventDestroy(h->side_done); }
     if (h->ev0) (void)hipEventDestroy(h->ev0);

@@ -259,6 +259,8 @@ struct ptmi_engine {
     struct ptmi_pairs_state *pairs;
     // thinned snapshots of the cold chains kept on the device (ptmi_samples.hip): the state of ptmi_samples_attach, or nullptr
     struct ptmi_samples_state *samples;
+    // the best-fit row of every cold chain (ptmi_best.hip): the state of ptmi_best_attach, or nullptr
+    struct ptmi_best_state *best;
 };
 enum { PTMI_GJ_NONE = 0, PTMI_GJ_PENDING = 1 /* proposals made, ptmi_gj_begin not yet called */, PTMI_GJ_ROUNDS = 2, PTMI_GJ_DONE = 3 };
 // the split path's refusals for gradient jumps (0: served; else the code, with the message set)
@@ -286,6 +288,8 @@ void ptmi_ladder_free(ptmi_engine *h);
 void ptmi_pairs_free(ptmi_engine *h);
 // snapshots of the cold chains (ptmi_samples.hip): frees h->samples, for ptmi_destroy
 void ptmi_samples_free(ptmi_engine *h);
+// best-fit rows of the cold chains (ptmi_best.hip): frees h->best, for ptmi_destroy
+void ptmi_best_free(ptmi_engine *h);
 // swap (ptmi_swap.hip): bytes of a record of d_pre (SwapPre), for ptmi_create
 constexpr size_t PTMI_SWAP_PRE_BYTES = 48;
 

@@ -1,7 +1,7 @@
 // ptmi_ring_weight.h -- what the units that read the AM ring a second time share (ptmi_hist.hip, ptmi_pairs.hip, ptmi_diag.hip,
-// ptmi_samples.hip): the checks their *_update / *_take calls open with and, for the two that count, the weight of every ring row in a
-// range of iterations and the check of the bin bounds.  Every includer gets its own copy; PTMI_RING_RANGE_ONLY (ptmi_diag.hip,
-// ptmi_samples.hip) leaves out what only the counting units use.
+// ptmi_samples.hip, ptmi_best.hip): the checks their *_update / *_take calls open with and, for the two that count, the weight of every
+// ring row in a range of iterations and the check of the bin bounds.  Every includer gets its own copy; PTMI_RING_RANGE_ONLY
+// (ptmi_diag.hip, ptmi_samples.hip, ptmi_best.hip) leaves out what only the counting units use.
 #pragma once
 #include "ptmi_common.h"
 #include <math.h>

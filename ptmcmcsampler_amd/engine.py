@@ -94,6 +94,17 @@ def hist_edges(lo, hi, nbins):
     return e
 
 
+def best_pick(score, iters):
+    """The walker ``PTEngine.best`` reports for one plane: the device's rule (include/ptmi.h ``ptmi_best_attach``) over ascending walker
+    index -- a walker that holds something (``iters >= 0``) replaces the pick iff nothing is picked yet or its score is ``>`` the
+    pick's, so the lowest index wins a tie; -1 where no walker holds anything."""
+    pick = -1
+    for w in range(len(iters)):
+        if iters[w] >= 0 and (pick < 0 or score[w] > score[pick]):
+            pick = w
+    return pick
+
+
 class _RingReader(object):
     """A stage that reads the cold chains' AM ring a second time: iterations ``first + 1`` on, ``iter`` the last one taken.
     ``update(eng, lo, hi, n_done)`` issues the stage's C call for iterations ``lo .. hi`` of the period the ring holds, ``n_done`` taken
@@ -106,7 +117,9 @@ class _RingReader(object):
              "diag": ("diagnostics", "diag=True", "folded",
                       "the checkpoint carries no diagnostics sums of this shape: it was written by a run without diag=True (or with other diag_levels)"),
              "samples": ("sample buffer", "samples=slots", "taken",
-                         "the checkpoint carries no sample buffer of this shape: it was written by a run without samples= (or with other slots, every or samples_from)")}
+                         "the checkpoint carries no sample buffer of this shape: it was written by a run without samples= (or with other slots, every or samples_from)"),
+             "best": ("best-fit tracker", "best=True", "compared",
+                      "the checkpoint carries no best-fit rows of this shape: it was written by a run without best=True (or with another best_from)")}
 
     def __init__(self, name, first, update):
         self.name, self.first, self.iter, self.update = name, first, first, update
@@ -276,6 +289,17 @@ class PTEngine(CallbackPath):
     ``t["samples"]``, ``t["samples_aux"]``, ``samples_iter`` and the plan's state are part of ``checkpoint()``, with ``every`` and
     ``samples_from``: ``restore()`` refuses a checkpoint whose buffer was filled on another schedule.  Idle on an engine that
     owns no cold ring.
+    ``with_stages(..., best=True, best_from=None)``: the BEST-FIT row of every walker's cold chain over ALL iterations, tracked on the
+    device (include/ptmi.h ``ptmi_best_*``): per walker the row with the largest ``lnprob = (1 / temps_mh[0]) * lnlike + lp`` (MAP) and
+    the row with the largest ``lnlike`` (ML), each in parameter order with its score, lnL, lp and iteration (``keep_lnl=True``), compared
+    from the AM ring whatever the ring mode.  ``best_from`` defaults to 0, not ``burn``: an optimum is an optimum whenever it was
+    visited; iteration 0 (``p0``) is not in the ring and is not a candidate.  A candidate replaces the held row iff its score is not NaN
+    and nothing is held or the score is ``>`` the held one, so the earliest iteration with the maximum wins however the run is cut
+    into calls.  ``update_cov`` takes the period that ends before it touches anything else; ``best_sync(it)`` takes up to an iteration
+    inside a period, ``best(it=None, per_walker=False)`` returns the best point of all walkers (host), ``best_device()`` the per-walker
+    device tensors.  The ring is only read: the chains are the same bits with and without.  ``t["best"]``, ``t["best_val"]``,
+    ``t["best_iters"]``, ``best_iter`` and ``best_from`` are part of ``checkpoint()``: ``restore()`` refuses a checkpoint without them or
+    with another ``best_from``.  Idle on an engine that owns no cold ring.
     ``with_stages(..., adapt_ladder=True | dict(every=10, kappa=2.0, t0=10.0, until=None))``: the temperature ladder adapts during burn-in
     from EVERY walker's accepted swaps (include/ptmi.h ``ptmi_ladder_*``).  ``swap(it)`` counts the swap epochs of a window by the parity
     of the pairs they try (``swap_mode="oddeven"``: epoch ``it // tskip`` tries the pairs of its parity, so ``every`` is even; the sweep
@@ -302,6 +326,8 @@ class PTEngine(CallbackPath):
     _pairs_from = None
     _samples = None
     _samples_from = None
+    _best = False
+    _best_from = None
     _ev = False
     _ev_from = None
     _ev_every = 1
@@ -334,7 +360,7 @@ class PTEngine(CallbackPath):
     @classmethod
     def with_stages(cls, *args, jumps_with_grad=False, aux=None, logl_in_support=False, hist=None, hist_from=None,
                     evidence=False, evidence_from=None, evidence_every=1, diag=False, diag_from=None, diag_batch=None, diag_levels=None,
-                    adapt_ladder=None, pairs=None, pairs_from=None, samples=None, samples_from=None, **kw):
+                    adapt_ladder=None, pairs=None, pairs_from=None, samples=None, samples_from=None, best=False, best_from=None, **kw):
         """``PTEngine(*args, **kw)`` with the stages of the composed ``_jump`` on the callback path (see the class docstring):
         ``jumps_with_grad=True`` lets ``jumps=`` stand beside ``grad_weights`` in one cycle, ``aux=[func, ...]`` are the auxiliary jumps,
         ``logl_in_support=True`` hands the likelihood callback only the rows whose prior is not -inf (``eval_callback``),
@@ -346,7 +372,9 @@ class PTEngine(CallbackPath):
         ``pairs=(pairs, lo, hi, nbins)`` with ``pairs_from`` accumulates the joint histograms of parameter pairs of every cold chain
         (``pairs_counts``; ``pairs``: int ``[npairs][2]`` or ``{"params": [indices]}`` = every pair of the list),
         ``samples=slots`` or ``dict(slots=, every=1)`` with ``samples_from`` keeps evenly spaced snapshots of every cold chain on the device
-        (``samples``, ``samples_device``).
+        (``samples``, ``samples_device``), ``best=True`` with ``best_from`` (default 0, not ``burn``: an optimum is an optimum whenever
+        it was visited) tracks the MAP and the ML row of every cold chain over all iterations (``best``, ``best_device``; iteration 0,
+        the starting point, is not in the ring and is not a candidate).
         The plain constructor keeps the parameters it had (tests/test_gj_groups.py holds them to the letter) and its refusals."""
         self = cls.__new__(cls)
         self.jumps_with_grad = bool(jumps_with_grad)
@@ -355,7 +383,8 @@ class PTEngine(CallbackPath):
         self._hist, self._hist_from = hist, hist_from
         self._pairs, self._pairs_from = pairs, pairs_from
         self._samples, self._samples_from = samples, samples_from
-        self._ev, self._ev_from, self._ev_every = bool(evidence), evidence_from, evidence_every
+        self._best, self._best_from = bool(best), best_from
+        self._ev,self._ev_from, self._ev_every = bool(evidence), evidence_from, evidence_every
         self._diag, self._diag_from, self._diag_batch, self._diag_levels = bool(diag), diag_from, diag_batch, diag_levels
         self._adapt = adapt_ladder
         self.__init__(*args, **kw)
@@ -408,6 +437,12 @@ class PTEngine(CallbackPath):
             self.samples_spec = samples_spec(self._samples)
             self._splan = SlotPlan(*self.samples_spec)
         self._ring_reader("samples", self.samples_spec is not None, self._samples_from, burn, PTEngine._samples_take)
+        # the best-fit (MAP / ML) row of every cold chain over all iterations (with_stages(best=True, best_from=...); see the class docstring)
+        self.best_on = bool(self._best)
+        if self.best_on and not keep_lnl:
+            raise ValueError("best=True compares the lnL and lp of every iteration: it needs keep_lnl=True (AMaux beside the ring's rows)")
+        self._ring_reader("best", self.best_on, self._best_from, 0,       # from iteration 0 on, not burn: an optimum is one whenever it was visited
+                          lambda eng, lo, hi, n: _lib.check(eng.lib.ptmi_best_update(eng.h, lo, hi)) if eng.owns_cold else None)
         # the ladder's summaries for the log-evidence (with_stages(evidence=True, evidence_from=..., evidence_every=...); see the class docstring)
         self.evidence_on = bool(self._ev)
         if self.evidence_on:
@@ -674,6 +709,15 @@ class PTEngine(CallbackPath):
             _lib.check(self.lib.ptmi_samples_attach(self.h, C.c_void_p(self.t["samples"].data_ptr()),
                                                     C.c_void_p(self.t["samples_aux"].data_ptr()) if self.t["samples_aux"] is not None else None,
                                                     self.samples_spec[0]))
+        if self.best_on:
+            # double [2][W][d] (MAP, ML) in parameter order, double [2][W][3] (score, lnL, lp) and int64 [2][W] (the iteration, -1 =
+            # nothing held); in self.t: checkpoints carry them by themselves.  A block that owns no cold ring attaches nothing and stays idle
+            self.t["best"] = z((2, W, d))
+            self.t["best_val"] = z((2, W, 3))
+            self.t["best_iters"] = torch.full((2, W), -1, dtype=i64, device=self.device)
+            if self.owns_cold:
+                _lib.check(self.lib.ptmi_best_attach(self.h, C.c_void_p(self.t["best"].data_ptr()), C.c_void_p(self.t["best_val"].data_ptr()),
+                                                     C.c_void_p(self.t["best_iters"].data_ptr()), 1.0 / float(self.temps_mh[0])))
         self.de_on = False
         self.de_head = 0
         self.iter = 0
@@ -1114,6 +1158,7 @@ class PTEngine(CallbackPath):
     pairs_from, pairs_iter = _ring_attr("pairs", "first"), _ring_attr("pairs", "iter")
     diag_from, diag_iter = _ring_attr("diag", "first"), _ring_attr("diag", "iter")
     samples_from, samples_iter = _ring_attr("samples", "first"), _ring_attr("samples", "iter")
+    best_from, best_iter = _ring_attr("best", "first"), _ring_attr("best", "iter")
 
     # ------------------------------------------------------------------ posterior histograms
     def hist_sync(self, it):
@@ -1231,6 +1276,49 @@ class PTEngine(CallbackPath):
             out["lnprob"] = (1.0 / self.temps_mh[0]) * a[..., 0] + a[..., 1]
         return out
 
+    # ------------------------------------------------------------------ best-fit rows
+    def best_sync(self, it):
+        """Compare iterations ``(best_iter, it]`` of every walker's cold chain with the held MAP and ML rows in ``t["best"]``
+        (``ptmi_best_update``: asynchronous, the ring is only read).  ``it`` lies in the covariance period the ring holds; ``update_cov``
+        calls this at every period's end, so a caller only needs it for the best row up to an iteration inside a period.  Nothing to
+        do up to ``best_from``."""
+        self._ring_sync("best", it)
+
+    def best_device(self, it=None):
+        """The held rows up to iteration ``it`` (default: the current one) as the device tensors themselves, no copy to the host:
+        ``(rows [2][W][d] (MAP, ML; parameter order), val [2][W][3] (score, lnL, lp), iters int64 [2][W] (-1: nothing held))``.  They
+        are ``t["best"]``, ``t["best_val"]`` and ``t["best_iters"]``: a later ``run`` goes on updating them on the engine's stream."""
+        self.best_sync(self.iter if it is None else it)
+        return self.t["best"], self.t["best_val"], self.t["best_iters"]
+
+    def best(self, it=None, per_walker=False):
+        """The best-fit point of ALL cold chains up to iteration ``it`` (default: the current one): a dict of ``x_map`` [d], ``lnprob_map``,
+        ``lnlike_map``, ``lp_map``, ``iter_map``, ``walker_map`` (the row with the largest ``lnprob = (1 / temps_mh[0]) * lnlike + lp``, the
+        chain files' column) and ``x_ml`` [d], ``lnlike_ml``, ``lp_ml``, ``lnprob_ml``, ``iter_ml``, ``walker_ml`` (the row with the largest
+        ``lnlike``), ``first_iter`` / ``last_iter`` (the iterations compared), ``nwalkers``.  Iteration 0, the starting point, is not in
+        the ring and is not a candidate.  Among the walkers the rule is the device's over ascending walker index (``best_pick``): held,
+        strict ``>``, the lowest index on ties.  Only ``val`` and ``iters`` and the ONE winning row per plane are read back; with
+        ``per_walker=True`` also ``x`` [2][W][d], ``val`` [2][W][3] and ``iters`` [2][W] of every walker.  Where nothing is held yet
+        ``iter_*`` and ``walker_*`` are -1 and the values NaN."""
+        rows, val, iters = self.best_device(it)
+        val, iters = val.cpu().numpy(), iters.cpu().numpy()
+        d = rows.shape[-1]
+        wm, wl = best_pick(val[0, :, 0], iters[0]), best_pick(val[1, :, 0], iters[1])
+        nan = np.float64(np.nan)
+        out = {}
+        for p, w, tag in ((0, wm, "map"), (1, wl, "ml")):
+            s, lnl, lp = (val[p, w] if w >= 0 else (nan, nan, nan))
+            out["x_" + tag] = rows[p, w].cpu().numpy() if w >= 0 else np.full(d, np.nan)
+            out["lnlike_" + tag], out["lp_" + tag] = np.float64(lnl), np.float64(lp)
+            # plane 0's score IS lnprob; for the ML row it is computed as the chain files compute it
+            with np.errstate(invalid="ignore"):
+                out["lnprob_" + tag] = np.float64(s) if p == 0 else np.float64((1.0 / self.temps_mh[0]) * lnl + lp)
+            out["iter_" + tag], out["walker_" + tag] = np.int64(iters[p, w] if w >= 0 else -1), np.int64(w)
+        out.update(first_iter=np.int64(self.best_from + 1), last_iter=np.int64(self.best_iter), nwalkers=np.int64(self.W))
+        if per_walker:
+            out.update(x=rows.cpu().numpy(), val=val, iters=iters)
+        return out
+
     def update_de(self, it_done=None):
         if self.owns_cold and self.t["DE"] is not None:
             if it_done is not None:
@@ -1260,6 +1348,8 @@ class PTEngine(CallbackPath):
         if self._splan is not None:
             st.update(samples_level=self._splan.level, samples_slot_iter=self._splan.slot_iter.copy(), samples_every=self._splan.every,
                       samples_from=self.samples_from)
+        if self.best_on:
+            st["best_from"] = self.best_from
         if self.evidence_on:
             st["ev_epochs"] = self.ev_epochs
         if self.adapt_on:
@@ -1281,6 +1371,10 @@ class PTEngine(CallbackPath):
                                         or int(st["samples_every"]) != self._splan.every or int(st["samples_from"]) != self.samples_from
                                         or (self.t["samples_aux"] is not None) != ("t_samples_aux" in st)):
             raise ValueError(_RingReader.WORDS["samples"][3])
+        if self.best_on and (any(k not in st for k in ("best_from", "t_best_val", "t_best_iters")) or int(st["best_from"]) != self.best_from
+                             or tuple(np.shape(st["t_best_val"])) != tuple(self.t["best_val"].shape)
+                             or tuple(np.shape(st["t_best_iters"])) != tuple(self.t["best_iters"].shape)):
+            raise ValueError(_RingReader.WORDS["best"][3])
         if self.evidence_on and any(k not in st for k in ("ev_epochs", "t_ev_acc", "t_ev_cnt")):
             raise ValueError("the checkpoint carries no evidence accumulators: it was written by a run without evidence=True")
         if self.adapt_on and any(k not in st for k in ("t_lad", "t_lad_seen", "lad_calls", "lad_epochs", "lad_tries", "lad_hist_iter",

@@ -48,6 +48,14 @@ the reference runs unchanged as ONE process driving one GPU.  Differences, all a
   [n][nwalkers][ndim], ``lnlike``, ``lnprob`` [n][nwalkers], ``iters``, ``every``, ``stride``, ``first_iter``, ``last_iter``, ``nwalkers``) at
   every save where the held set has changed and at the end of the run, ``sampler.samples`` after the run (``samples.flat`` gives one
   array per quantity); ``checkpoint=True`` runs resume the buffer, a replay of chain files cannot;
+* ``sampler.track_best = True`` or ``{"from": k}`` (before ``sample()``; any likelihood, any path): the BEST-FIT point of the run -- where a
+  user of the reference takes ``chain[np.argmax(chain[:, -4])]`` (MAP) and ``chain[np.argmax(chain[:, -3])]`` (ML) from the thinned rows of
+  the one chain file -- over EVERY iteration of EVERY walker's cold chain from iteration ``k + 1`` on (default 0: an optimum is one
+  whenever it was visited, burn-in included; ``p0`` itself is not a candidate), tracked on the device
+  (``PTEngine.with_stages(best=True)``, csrc/ptmi_best.hip).  ``<outDir>/best.npz`` (``x_map``, ``lnprob_map``, ``lnlike_map``, ``lp_map``,
+  ``iter_map``, ``walker_map``, the same with ``_ml``, ``first_iter``, ``last_iter``, ``nwalkers`` and every walker's held rows ``x``
+  [2][nwalkers][ndim], ``val`` [2][nwalkers][3] = (score, lnlike, lp), ``iters`` [2][nwalkers]) at every save and at the end of the run,
+  ``sampler.best`` after the run; ``checkpoint=True`` runs resume the held rows, a replay of chain files cannot;
 * ``sampler.chain_diagnostics = True`` or ``{"batch": b0, "levels": L, "stop_ess": N, "stop_rhat": r}`` (before ``sample()``; any likelihood,
   any path): Gelman-Rubin R-hat, the integrated autocorrelation time and the effective sample size of every parameter from EVERY
   walker's cold chain after ``burn`` -- where the ``neff`` rule (PTMCMCSampler.py:510-521) looks at one kept chain.  The device streams the
@@ -197,6 +205,12 @@ class PTSampler(object):
     posterior_samples = None
     samples = None
     _last_save = False
+    # s.track_best = True, or {"from": k} (before sample()): the best-fit point -- the MAP row (largest lnprob) and the ML row (largest
+    # lnlike) of EVERY walker's cold chain over ALL iterations from k + 1 on (default 0: burn-in included), tracked on the device
+    # (PTEngine.with_stages(best=True)): <outDir>/best.npz at every save and at the end of the run, s.best after the run.  An attribute
+    # for the same reason
+    track_best = None
+    best = None
     # s.log_evidence = True, or {"every": k} (before sample()): ln Z from the ladder of EVERY walker -- per-temperature lnL moments taken on
     # the device behind every (k-th) swap after burn (PTEngine.with_stages(evidence=True)): <outDir>/evidence.npz at every save, s.evidence
     # after the run.  An attribute for the same reason as batched_aux
@@ -458,6 +472,10 @@ class PTSampler(object):
             raise NotImplementedError("posterior_samples keeps snapshots of every walker's cold chain on the device; chain files hold the kept "
                                       "walkers' thinned rows only, so a replayed run cannot continue the buffer: resume from a device checkpoint "
                                       "(PTSampler(..., checkpoint=True) from the first run on)")
+        if self._replaying and self._best_kw():
+            raise NotImplementedError("track_best compares every iteration of every walker's cold chain on the device; chain files hold the kept "
+                                      "walkers' thinned rows only, so a replayed run cannot continue the comparison: resume from a device checkpoint "
+                                      "(PTSampler(..., checkpoint=True) from the first run on)")
         if self._replaying and self.log_evidence:
             raise NotImplementedError("log_evidence sums the lnL of every walker's whole ladder on the device; chain files hold the kept "
                                       "walkers' thinned rows only, so a replayed run cannot continue the sums: resume from a device checkpoint "
@@ -570,7 +588,7 @@ class PTSampler(object):
             split_nuts=self._batched_grads and self.batched_nuts, rows_logl=self.rows_logl,
             jumps=[(f, n) for f, n in stage_list] if stage_list else None,
             jumps_with_grad=bool(stage_list) and sum(self._grad_weights) > 0, aux=list(self._batched_aux) or None,
-            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **({"pairs": self.posterior_pairs} if self.posterior_pairs is not None else {}), **({"samples": self.posterior_samples} if self.posterior_samples is not None else {}), **self._evidence_kw(), **self._diag_kw(), **self._adapt_kw(),
+            logl_in_support=bool(self.logl_in_support), hist=self.posterior_hist, **({"pairs": self.posterior_pairs} if self.posterior_pairs is not None else {}), **({"samples": self.posterior_samples} if self.posterior_samples is not None else {}), **self._best_kw(), **self._evidence_kw(), **self._diag_kw(), **self._adapt_kw(),
             w_host=len(self.host_jumps), keep_lnl=True, groups=None if len(self.groups) == 1 and len(self.groups[0]) == self.ndim and np.array_equal(np.asarray(self.groups[0]), np.arange(self.ndim)) else self.groups)
 
     def _evidence_kw(self):
@@ -583,6 +601,17 @@ class PTSampler(object):
         if isinstance(le, dict) and set(le) <= {"every"}:
             return dict(evidence=True, evidence_every=le.get("every", 1))
         raise ValueError('log_evidence is True or {"every": k} (got %r)' % (le,))
+
+    def _best_kw(self):
+        """``track_best`` -> the keywords of ``PTEngine.with_stages`` (none where it is off; ``best_from`` is the engine's default, 0)."""
+        tb = self.track_best
+        if tb is None or tb is False:
+            return {}
+        if tb is True:
+            return dict(best=True)
+        if isinstance(tb, dict) and set(tb) <= {"from"}:
+            return dict(best=True, **({"best_from": tb["from"]} if "from" in tb else {}))
+        raise ValueError('track_best is True or {"from": k} (got %r)' % (tb,))
 
     def _adapt_kw(self):
         """``adapt_ladder`` -> the keyword of ``PTEngine.with_stages`` (none where it is off; the engine checks the values)."""
@@ -783,6 +812,8 @@ class PTSampler(object):
                                     if eng.pairs_spec is not None else ()),
                                   # (the sample buffer's slots and spacing, only where there is one)
                                   *((("samples", eng.samples_from) + tuple(eng.samples_spec),) if eng.samples_spec is not None else ()),
+                                  # (the best-fit tracker's first iteration, only where it is on)
+                                  *((("best", eng.best_from),) if eng.best_on else ()),
                                   # (the evidence stage's sampling, only where it is on)
                                   *((("evidence", eng.evidence_from, eng.evidence_every),) if eng.evidence_on else ()),
                                   # (the diagnostics stage's batches, only where it is on)
@@ -1124,6 +1155,12 @@ class PTSampler(object):
             self.samples = eng.samples(iter)
             self._write_npz("samples", self.samples)
 
+    def _write_best(self, iter):
+        """The best-fit point up to iteration ``iter`` (of the current covariance period), with every walker's held rows -> self.best and
+        <outDir>/best.npz."""
+        self.best = self._ring_upto(iter, lambda it: self.engine.best(it, per_walker=True))
+        self._write_npz("best", self.best)
+
     def _write_evidence(self):
         """The estimates from the samples so far, with the moments they come from -> self.evidence and <outDir>/evidence.npz."""
         from .evidence import estimates
@@ -1177,6 +1214,10 @@ class PTSampler(object):
             raise ValueError("posterior_samples was set after the engine was built: set it before the first sample()")
         if self.engine.samples_spec is not None and iter > 0:
             self._write_samples(iter, always=self._last_save)         # the same; only where the held set has changed, and at the run's end
+        if self._best_kw() and not getattr(self.engine, "best_on", False):
+            raise ValueError("track_best was set after the engine was built: set it before the first sample()")
+        if getattr(self.engine, "best_on", False) and iter > 0:
+            self._write_best(iter)                                    # ahead of the checkpoint: it carries the held rows up to here
         if iter // self.thin >= self.ind_next_write:
             self._counters()
             self._writeToFile(iter)
