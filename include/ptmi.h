@@ -250,6 +250,18 @@ enum { PTMI_GJL_WAVE = 1,      /* a jump takes the whole wave, one chain at a ti
        PTMI_GJL_AM_AHEAD = 256 /* the launch was a piece behind the matrix product that computes its AM increments */ };
 int ptmi_last_gj_launch(ptmi_handle h, int32_t *layout, int32_t *lds_levels, int32_t *lds_bytes, int32_t *nslots);
 
+/* Which kernels the most recent swap launched (ptmi_swap, ptmi_swap_sweep, ptmi_swap_sweep_blocks): every route gives the same
+ * tables, so only this report tells a test which one it ran.  The route follows from the ladder's length alone (the tables of a
+ * block's walkers must fit 160 KB of LDS), from the swap mode and from the test hook PTMI_SWAP_FUSED.  `kernel` is one of the values
+ * below, `wpb` the walkers per block (0 for PTMI_SWL_ODDEVEN, whose blocks are not made of walkers), `lds_bytes` the dynamic LDS of a block, `hop_in_sweep` 1 when the sweep's write-out did the
+ * multi-hop scan itself (sharded form only; with 0 ptmi_exchange_pack runs the standalone scan).  All four are 0 before the first swap. */
+enum { PTMI_SWL_FUSED = 1,     /* swap_fused_kernel: the pairs' records made in the block, the tables in LDS */
+       PTMI_SWL_LDS = 2,       /* swap_prepare_kernel + swap_sweep_kernel with the tables in LDS */
+       PTMI_SWL_DIRECT = 3,    /* swap_prepare_kernel + swap_sweep_kernel storing straight to memory: ladders whose tables do not fit the
+                                * LDS with 8 walkers per block; the AM row and the multi-hop scan are kernels of their own */
+       PTMI_SWL_ODDEVEN = 4    /* odd/even mode with the whole ladder local: one thread per tried pair, no LDS */ };
+int ptmi_last_swap_launch(ptmi_handle h, int32_t *kernel, int32_t *wpb, int32_t *lds_bytes, int32_t *hop_in_sweep);
+
 /* PTswap (:631-697) for iteration `iter` when the whole ladder is on this GPU. */
 int ptmi_swap(ptmi_handle h, int64_t iter);
 

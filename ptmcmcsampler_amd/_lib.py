@@ -34,6 +34,8 @@ class Config(C.Structure):
 VAR_STAGED, VAR_FULL, VAR_LDS_UT, VAR_GROUPS, VAR_GRADJUMP, VAR_UNIFORM, VAR_AMQ, VAR_LDS_BOX, VAR_LDS_DRAWT, VAR_DENSE_SCAM, VAR_PERSISTENT, VAR_PC, VAR_UTPAD = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 1 << 28   # ptmi_last_mh_variant
 # ptmi_last_gj_launch: the layout of the most recent gradient-jump launch and the flags or-ed to it
 GJL_WAVE, GJL_PAIR, GJL_W16, GJL_CHAIN, GJL_LAYOUT_MASK, GJL_DIAG, GJL_GRP, GJL_BOX_LDS, GJL_ORDERED, GJL_AM_AHEAD = 1, 2, 3, 4, 15, 16, 32, 64, 128, 256
+# ptmi_last_swap_launch: the kernels of the most recent swap
+SWL_FUSED, SWL_LDS, SWL_DIRECT, SWL_ODDEVEN = 1, 2, 3, 4
 SWAP_MODES = {"sweep": 0, "oddeven": 1}
 PICK_MODES = {"chain": 0, "walker": 1}        # PTMI_PICK_CHAIN, PTMI_PICK_WALKER      # PTMI_SWAP_SWEEP, PTMI_SWAP_ODDEVEN
 
@@ -49,7 +51,7 @@ class Buffers(C.Structure):
 # every symbol include/ptmi.h declares
 SYMBOLS = (
     "ptmi_last_error", "ptmi_version", "ptmi_device_count", "ptmi_lanes_for", "ptmi_lanes_for_grad", "ptmi_temperature_ladder", "ptmi_de_row_stride", "ptmi_am_row_format", "ptmi_create", "ptmi_destroy",
-    "ptmi_sync", "ptmi_eval_state", "ptmi_set_de_active", "ptmi_mh_steps", "ptmi_last_mh_variant", "ptmi_last_gj_launch", "ptmi_swap", "ptmi_swap_gather_lnl",
+    "ptmi_sync", "ptmi_eval_state", "ptmi_set_de_active", "ptmi_mh_steps", "ptmi_last_mh_variant", "ptmi_last_gj_launch", "ptmi_last_swap_launch", "ptmi_swap", "ptmi_swap_gather_lnl",
     "ptmi_swap_sweep", "ptmi_swap_sweep_blocks", "ptmi_exchange_pack", "ptmi_exchange_apply", "ptmi_exchange_status", "ptmi_exchange_multihop",
     "ptmi_swap_write_am", "ptmi_update_cov", "ptmi_update_cov_on", "ptmi_set_am_buffers", "ptmi_eig_jacobi", "ptmi_eig_ql", "ptmi_eig_ql_from", "ptmi_eig_sytrd", "ptmi_eig_sytrd_from", "ptmi_eig_sytrd_info", "ptmi_update_de", "ptmi_set_de_head", "ptmi_propose", "ptmi_accept", "ptmi_accept_propose", "ptmi_proposals", "ptmi_rows_logl", "ptmi_rows_logl_grad", "ptmi_rows_logp", "ptmi_split_am_piece", "ptmi_split_am_prepare", "ptmi_set_stream", "ptmi_set_proposals", "ptmi_device_iter", "ptmi_set_device_iter",
     "ptmi_gj_work_bytes", "ptmi_gj_begin", "ptmi_gj_step",
@@ -158,10 +160,11 @@ def load():
               ptmi_pairs_attach=[H, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, _dp, _dp, C.c_int32], ptmi_pairs_update=[H, C.c_int64, C.c_int64],
               ptmi_samples_attach=[H, C.c_void_p, C.c_void_p, C.c_int32], ptmi_samples_take=[H, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32],
               ptmi_best_attach=[H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double], ptmi_best_update=[H, C.c_int64, C.c_int64],
-              ptmi_last_gj_launch=[H] + [C.POINTER(C.c_int32)] * 4)
+              ptmi_last_gj_launch=[H] + [C.POINTER(C.c_int32)] * 4,
+              ptmi_last_swap_launch=[H] + [C.POINTER(C.c_int32)] * 4)
     for n, at in cj.items():
         if SO == os.environ.get("PTMI_LIB") and not hasattr(L, n):
-            continue                                  # an older build for an A/B measurement: no custom-jump, auxiliary, support, histogram, evidence, diagnostics, ladder, pair-histogram, snapshot or best-fit stage, no gradient-jump launch report (using it raises)
+            continue                                  # an older build for an A/B measurement: no custom-jump, auxiliary, support, histogram, evidence, diagnostics, ladder, pair-histogram, snapshot or best-fit stage, no gradient-jump or swap launch report (using it raises)
         getattr(L, n).argtypes = at
     L.ptmi_selftest_math.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     L.ptmi_selftest_philox.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64]

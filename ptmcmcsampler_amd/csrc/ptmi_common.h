@@ -200,6 +200,7 @@ struct ptmi_engine {
     int de_on, de_head;
     int last_variant;   // PTMI_VAR_* flags of the most recent fused-MH launch (ptmi_last_mh_variant)
     int gj_last[4];     // PTMI_GJL_* layout | flags, LDS levels, LDS bytes, chain slots of the most recent gradient-jump launch (ptmi_last_gj_launch)
+    int swap_last[4];   // PTMI_SWL_* kernel, walkers per block, LDS bytes, multi-hop scan in the write-out of the most recent swap launch (ptmi_last_swap_launch)
     hipEvent_t ev0, ev1;
     hipStream_t side;            // pooled statistics at ndim > 111: the diagonal macro tiles run beside the off-diagonal ones
     hipEvent_t side_go, side_done;

@@ -437,6 +437,12 @@ static int swap_parity(const ptmi_config &c, int64_t iter)
     return (int)((c.tskip > 0 ? iter / c.tskip : iter) & 1);
 }
 
+// what ptmi_last_swap_launch reports
+static void swap_report(ptmi_engine *h, int kernel, int wpb, size_t lds, bool hop)
+{
+    h->swap_last[0] = kernel; h->swap_last[1] = wpb; h->swap_last[2] = (int)lds; h->swap_last[3] = hop ? 1 : 0;
+}
+
 static int launch_swap_sweep(ptmi_engine *h, int W, int n, const SwapPre *pre, int32_t *slot_of, int32_t *temp_of,
                              int32_t *map, u64 *nswap, int local0, int nlocal, int parity, int32_t *inv, int hop_nt = 0, bool *hop_done = nullptr,
                              const SwapAmRow *amr = nullptr, bool *am_done = nullptr)
@@ -460,9 +466,11 @@ static int launch_swap_sweep(ptmi_engine *h, int W, int n, const SwapPre *pre, i
         hipLaunchKernelGGL(swap_sweep_kernel<true>, dim3((unsigned)((W + wpb - 1) / wpb)), dim3(256), lds, h->stream, W, n, h->d_ladder, pre,
                            slot_of, temp_of, map, nswap, local0, nlocal, parity, inv, wpb, hop_nt, h->d_hop, with_am ? *amr : none);
         if (am_done) *am_done = with_am;
+        swap_report(h, PTMI_SWL_LDS, wpb, lds, hop_nt > 0);
     } else {
         hipLaunchKernelGGL(swap_sweep_kernel<false>, dim3((unsigned)((W + 63) / 64)), dim3(64), 0, h->stream, W, n, h->d_ladder, pre,
                            slot_of, temp_of, map, nswap, local0, nlocal, parity, inv, 64, 0, (int32_t *)nullptr, none);
+        swap_report(h, PTMI_SWL_DIRECT, 64, 0, false);
     }
     return PTMI_OK;
 }
@@ -499,6 +507,7 @@ static int launch_swap_fused(ptmi_engine *h, int W, int n, const SwapSrc &src, i
     hipLaunchKernelGGL(swap_fused_kernel, dim3((unsigned)((W + wpb - 1) / wpb)), dim3(SWF_BLK), lds, h->stream, W, n, src, slot_of, temp_of, map,
                        nswap, local0, nlocal, parity, inv, wpb, lg, hop_nt, h->d_hop, with_am ? *amr : none);
     if (am_done) *am_done = with_am;
+    swap_report(h, PTMI_SWL_FUSED, wpb, lds, hop_nt > 0);
     *used = true;
     return PTMI_OK;
 }
@@ -518,6 +527,7 @@ int ptmi_swap(ptmi_handle h, int64_t iter)
             hipLaunchKernelGGL(swap_oddeven_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream, W, c.ntemps,
                                h->d_ladder, (const double *)h->buf.lnL, h->buf.slot_of, h->buf.temp_of, (u64 *)h->buf.nswap,
                                (long long)iter, c.seed, c.walker0, parity);
+        swap_report(h, PTMI_SWL_ODDEVEN, 0, 0, false);
         HIPCHK(hipGetLastError());
         return ptmi_swap_write_am(h, iter);
     }
@@ -540,6 +550,13 @@ int ptmi_swap(ptmi_handle h, int64_t iter)
                                    (c.temp0 == 0 && h->buf.AM) ? &amr : nullptr, &am_done)) return rc;
     HIPCHK(hipGetLastError());
     return am_done ? PTMI_OK : ptmi_swap_write_am(h, iter);
+}
+
+int ptmi_last_swap_launch(ptmi_handle h, int32_t *kernel, int32_t *wpb, int32_t *lds_bytes, int32_t *hop_in_sweep)
+{
+    if (!h || !kernel || !wpb || !lds_bytes || !hop_in_sweep) return fail(PTMI_EINVAL, "NULL argument");
+    *kernel = h->swap_last[0]; *wpb = h->swap_last[1]; *lds_bytes = h->swap_last[2]; *hop_in_sweep = h->swap_last[3];
+    return PTMI_OK;
 }
 
 int ptmi_swap_gather_lnl(ptmi_handle h, double *out)

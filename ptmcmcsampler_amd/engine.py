@@ -1502,6 +1502,13 @@ class PTEngine(CallbackPath):
         _lib.check(self.lib.ptmi_last_gj_launch(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def last_swap_launch(self):
+        """(kernel, walkers per block, dynamic LDS bytes, multi-hop scan in the write-out) of the last swap launch -- ``swap``, ``sweep``
+        or ``sweep_blocks`` (``_lib.SWL_*``; ``ptmi_last_swap_launch``): all zero before the first one."""
+        v = [C.c_int32(0) for _ in range(4)]
+        _lib.check(self.lib.ptmi_last_swap_launch(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def swap(self, it):
         """PT swap of iteration ``it`` with the whole ladder on this GPU (:631-697)."""
         _lib.check(self.lib.ptmi_swap(self.h, it))

@@ -92,6 +92,26 @@ def test_gj_launch_report_matches_the_header(lib):
     assert [v.value for v in out] == [7] * 4
 
 
+def test_swap_launch_report_matches_the_header(lib):
+    """ptmi_last_swap_launch: the PTMI_SWL_* kernels the swap-route tests assert on are the header's and the binding's; the symbol is
+    declared with four int32 outputs, bound with them, and refuses NULL arguments without touching a device or its outputs."""
+    import ctypes as C
+    hdr = open(os.path.join(ROOT, "include", "ptmi.h")).read()
+    vals = {n: int(v) for n, v in re.findall(r"\bPTMI_(SWL_[A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    assert vals == dict(SWL_FUSED=1, SWL_LDS=2, SWL_DIRECT=3, SWL_ODDEVEN=4)
+    for n, v in vals.items():
+        assert getattr(lib, n) == v, n
+    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert re.search(r"\bint\s+ptmi_last_swap_launch\s*\(\s*ptmi_handle\s+h\s*,\s*int32_t\s*\*\s*kernel\s*,\s*int32_t\s*\*\s*wpb\s*,"
+                     r"\s*int32_t\s*\*\s*lds_bytes\s*,\s*int32_t\s*\*\s*hop_in_sweep\s*\)\s*;", plain)
+    L = lib.load()
+    assert "ptmi_last_swap_launch" in lib.SYMBOLS
+    assert L.ptmi_last_swap_launch.argtypes == [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
+    out = [C.c_int32(7) for _ in range(4)]
+    assert L.ptmi_last_swap_launch(None, *[C.byref(v) for v in out]) != 0 and "NULL" in L.ptmi_last_error().decode()
+    assert [v.value for v in out] == [7] * 4
+
+
 def test_no_cpu_fallback(lib):
     """Without a device the product path refuses to run instead of computing on the host."""
     import numpy as np
