@@ -359,8 +359,13 @@ int ptmi_eig_ql_from(ptmi_handle h, void *stream, const double *cov_in, double *
  * deflation, roots of the secular equation by bisection, Gu / Eisenstat weights), back-transformed through the reflectors.
  * Replaces the np.linalg.svd of :797-803 where the ROCm library's eigensolver (torch.linalg.eigh: 35 ms of small kernels at
  * 1000 x 1000) is the epoch.  On `stream` (NULL: the handle's), results into Ut_out [ndim][ndim] / S_out [ndim] (NULL: the handle's
- * Ut / S): eigenvalues in absolute value, descending; no sign rule.  No oracle restates its last bits: the tests hold every table
- * it makes to U diag(S) U^T = cov and U U^T = I at 1e-12 and step the ORACLE's chains with it (tests/test_device_tables_gpu.py). */
+ * Ut / S): eigenvalues in absolute value, descending; no sign rule.  A merge deflates by LAPACK dlaed2's test with a tolerance
+ * that carries the matrix's own norm (csrc/ptmi_dc.inc.h), so the factorization commutes with a power of two times cov: the same Ut,
+ * that power of two times S, bit for bit.  Its last bits are its own; what holds it: oracle/eig_dc.py restates the algorithm on the
+ * CPU (tests/test_eig_dc.py, against LAPACK), tests/test_eig_dc_gpu.py drives the reduction, the tridiagonal solver and the whole
+ * pipeline one by one against LAPACK and that restatement -- residual, orthogonality and eigenvalues within a measured multiple of
+ * LAPACK's own, U diag(+-S) U^T = cov at 1e-12 max|cov| from 2^-300 to 2^300 times the matrix, indefinite and singular input
+ * included -- and tests/test_device_tables_gpu.py steps the ORACLE's chains with the tables it makes. */
 int ptmi_eig_sytrd(ptmi_handle h, void *stream, double *Ut_out, double *S_out);
 /* The same from the covariance `cov_in` [ndim][ndim] (device; NULL: the handle's cov): a caller that runs the factorization BESIDE
  * later work -- the statistics of the next covariance epoch overwrite the handle's cov -- hands in its own copy (PTEngine: eig_lag
@@ -371,6 +376,23 @@ int ptmi_eig_sytrd_from(ptmi_handle h, void *stream, const double *cov_in, doubl
  * follows the factorization on its stream into pinned memory, so the call never waits; check it once that stream has been waited for
  * (the engine does at its next covariance epoch and in sync()).  Non-zero: Ut / S of that epoch are not to be trusted. */
 int ptmi_eig_sytrd_info(ptmi_handle h, int32_t *info);
+/* The stages of ptmi_eig_sytrd on their own, for tests.
+ * ptmi_eig_dc_tridiag: the divide-and-conquer kernels on the caller's symmetric tridiagonal matrix, no back-transformation.  The order
+ * is the handle's ndim and nothing else -- the tree of the solver is built once per handle for that order, so the call takes no
+ * order of its own -- 1 <= ndim <= 1024 (1 and 2 included, below ptmi_eig_sytrd's 3).  All pointers are device memory: d
+ * [ndim] the diagonal, e [ndim - 1] the off-diagonal (unused at ndim = 1), W [ndim] the eigenvalues ascending, Z [ndim][ndim] the
+ * eigenvectors, vector-major (row v belongs to W[v]); cnt (may be NULL) [2 * merges]: for every merge of the tree, bottom level
+ * first and left to right within a level, the number of secular roots it found and the number of eigenvalues it deflated (their sum
+ * is the merge's order).  On `stream` (NULL: the handle's); the convergence word goes where ptmi_eig_sytrd_info reads it.  The call
+ * uses the scratch and the convergence word of ptmi_eig_sytrd: it must not overlap a factorization of the same handle on another
+ * stream (an engine with eig_lag: wait for the pending table first), nor another call of itself.
+ * ptmi_eig_sytrd_reduction: copies what the tridiagonalization of the handle's most recent ptmi_eig_sytrd[_from] left in the scratch
+ * to the caller's device buffers, on `stream` (NULL: the handle's; a stream other than the factorization's must wait for it first):
+ * D [ndim], E [ndim - 1], tau [ndim - 1], A [ndim][ndim] in LAPACK dsytrd's column-major lower storage -- reflector m is (1 at
+ * m + 1, A[m * ndim + i] for i >= m + 2); every other entry of A is still the input's (d and e come in D and E only).  Before any
+ * factorization: PTMI_EINVAL. */
+int ptmi_eig_dc_tridiag(ptmi_handle h, void *stream, const double *d, const double *e, double *W, double *Z, int32_t *cnt);
+int ptmi_eig_sytrd_reduction(ptmi_handle h, void *stream, double *D, double *E, double *tau, double *A);
 
 /* _updateDEbuffer (:806-817): drop the oldest cov_update rows of each DE history and
  * append the AM buffer (pooled mode: row r comes from walker r mod W). */

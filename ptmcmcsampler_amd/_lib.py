@@ -53,7 +53,7 @@ SYMBOLS = (
     "ptmi_last_error", "ptmi_version", "ptmi_device_count", "ptmi_lanes_for", "ptmi_lanes_for_grad", "ptmi_temperature_ladder", "ptmi_de_row_stride", "ptmi_am_row_format", "ptmi_create", "ptmi_destroy",
     "ptmi_sync", "ptmi_eval_state", "ptmi_set_de_active", "ptmi_mh_steps", "ptmi_last_mh_variant", "ptmi_last_gj_launch", "ptmi_last_swap_launch", "ptmi_swap", "ptmi_swap_gather_lnl",
     "ptmi_swap_sweep", "ptmi_swap_sweep_blocks", "ptmi_exchange_pack", "ptmi_exchange_apply", "ptmi_exchange_status", "ptmi_exchange_multihop",
-    "ptmi_swap_write_am", "ptmi_update_cov", "ptmi_update_cov_on", "ptmi_set_am_buffers", "ptmi_eig_jacobi", "ptmi_eig_ql", "ptmi_eig_ql_from", "ptmi_eig_sytrd", "ptmi_eig_sytrd_from", "ptmi_eig_sytrd_info", "ptmi_update_de", "ptmi_set_de_head", "ptmi_propose", "ptmi_accept", "ptmi_accept_propose", "ptmi_proposals", "ptmi_rows_logl", "ptmi_rows_logl_grad", "ptmi_rows_logp", "ptmi_split_am_piece", "ptmi_split_am_prepare", "ptmi_set_stream", "ptmi_set_proposals", "ptmi_device_iter", "ptmi_set_device_iter",
+    "ptmi_swap_write_am", "ptmi_update_cov", "ptmi_update_cov_on", "ptmi_set_am_buffers", "ptmi_eig_jacobi", "ptmi_eig_ql", "ptmi_eig_ql_from", "ptmi_eig_sytrd", "ptmi_eig_sytrd_from", "ptmi_eig_sytrd_info", "ptmi_eig_dc_tridiag", "ptmi_eig_sytrd_reduction", "ptmi_update_de", "ptmi_set_de_head", "ptmi_propose", "ptmi_accept", "ptmi_accept_propose", "ptmi_proposals", "ptmi_rows_logl", "ptmi_rows_logl_grad", "ptmi_rows_logp", "ptmi_split_am_piece", "ptmi_split_am_prepare", "ptmi_set_stream", "ptmi_set_proposals", "ptmi_device_iter", "ptmi_set_device_iter",
     "ptmi_gj_work_bytes", "ptmi_gj_begin", "ptmi_gj_step",
     "ptmi_cj_attach", "ptmi_cj_work_bytes", "ptmi_cj_begin", "ptmi_cj_end", "ptmi_cj_box_draw",
     "ptmi_aux_attach", "ptmi_aux_begin", "ptmi_aux_end",
@@ -111,6 +111,8 @@ def load():
     L.ptmi_eig_sytrd_from.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ptmi_eig_ql_from.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ptmi_eig_sytrd_info.argtypes = [H, C.POINTER(C.c_int32)]
+    L.ptmi_eig_dc_tridiag.argtypes = [H] + [C.c_void_p] * 6
+    L.ptmi_eig_sytrd_reduction.argtypes = [H] + [C.c_void_p] * 5
     L.ptmi_set_de_active.argtypes = [H, C.c_int]
     L.ptmi_set_de_head.argtypes = [H, C.c_int32]
     L.ptmi_mh_steps.argtypes = [H, C.c_int64, C.c_int32]

@@ -206,6 +206,7 @@ struct ptmi_engine {
     hipEvent_t side_go, side_done;
     double *d_utpad;             // zero-padded copy of the pooled eigenvector table for the 16- / 64-lane shapes (KArgs::UtPad)
     void *d_sy_scr;              // ptmi_eig_sytrd: the working matrix, d / e / tau, the eigenvectors, the exchange vectors and the barrier word
+    int sy_reduced;              // ... 1 once a reduction has been queued into it (ptmi_eig_sytrd_reduction)
     void *dc_plan;               // ... the divide-and-conquer solver's tree and scratch (DcPlan, ptmi_eig.hip)
     int32_t *h_sy_info;          // pinned: the divide-and-conquer solver's convergence word of the last factorization that has finished
     void *d_qlg_scr;             // ptmi_eig_ql with parameter groups: a group's packed matrices, their eigenvectors and eigenvalues

@@ -6,8 +6,11 @@
 //   * the matrix is split in halves down to leaves of <= 16 rows (T = diag(T1', T2') + |rho| v v^T at every split, rho the
 //     off-diagonal entry cut); a leaf is solved by implicit QL in one wave;
 //   * a merge sorts the children's eigenvalues, DEFLATES (a tiny component of z = the adjoining rows of the children's eigenvectors,
-//     or two close eigenvalues after a plane rotation: LAPACK dlaed2's test) -- the nearly degenerate spectra an isotropic target
-//     adapts to deflate almost completely -- and finds the remaining k eigenvalues as roots of the secular equation
+//     or two close eigenvalues after a plane rotation: LAPACK dlaed2's test, with the tolerance 8 eps max(max|D|, max|z| (max|d| +
+//     max|e|)) -- D the children's eigenvalues, d / e the node's own matrix: dstedc scales the matrix to unit norm before dlaed2
+//     compares |D| with the dimensionless |z|, here z carries the norm instead, so that a power of two times the matrix gives the
+//     same deflations, the same vectors and that power of two times the eigenvalues, bit for bit) -- the nearly degenerate spectra
+//     an isotropic target adapts to deflate almost completely -- and finds the remaining k eigenvalues as roots of the secular equation
 //     1 + rho sum_i z_i^2 / (d_i - lambda) = 0 by BISECTION in coordinates shifted to the closer pole (a wave per root, the sum over
 //     the lanes): monotone on its interval, no safeguards to get wrong, and the differences d_i - lambda_j come out to full relative
 //     accuracy, which is what the stabilisation needs;
@@ -15,7 +18,9 @@
 //     rank-one update are orthogonal to working precision however close the roots are, and the children's vectors are multiplied
 //     by them on the matrix cores (v_mfma_f64_16x16x4_f64).
 // Checked against numpy on random, Wilkinson, nearly degenerate and near-identity matrices (tests/test_eig_jacobi.py): eigenvalues,
-// orthogonality and residual at a few 1e-15.  Its last bits are its own (no oracle restates it), like the library's before it.
+// orthogonality and residual at a few 1e-15.  Its last bits are its own; oracle/eig_dc.py restates the algorithm (plan, leaf, merge,
+// reduction) on the CPU, and tests/test_eig_dc_gpu.py drives the stages one by one -- the tridiagonal solver through
+// ptmi_eig_dc_tridiag, the reduction through ptmi_eig_sytrd_reduction -- against LAPACK and that restatement, over 2^-300 .. 2^300.
 #pragma once
 
 namespace dc {
@@ -157,6 +162,8 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_kernel(Args a)
         zt = t < n1 ? a.Qin[(size_t)(off + t) * n + off + n1 - 1] : sgn * a.Qin[(size_t)(off + t) * n + off + n1];
         zt *= 0.70710678118654752440;                                  // |z| = sqrt 2 -> 1 (rho doubles)
         Ds[t] = Dt;                                                    // staged unsorted first
+        rc[t] = __builtin_fabs(a.d[off + t]);                          // the node's own matrix (d after the splits), for its norm
+        rs[t] = t + 1 < nn ? __builtin_fabs(a.e[off + t]) : 0.0;
     }
     __syncthreads();
     int rank = 0;
@@ -168,12 +175,18 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_kernel(Args a)
     __syncthreads();
     if (t == 0) {
         const double rho = 2.0 * __builtin_fabs(e_cut);
-        double dmax = 0.0, zmax = 0.0;
+        double dmax = 0.0, zmax = 0.0, tdmax = 0.0, temax = 0.0;
         for (int j = 0; j < nn; ++j) {
             dmax = __builtin_fabs(Ds[j]) > dmax ? __builtin_fabs(Ds[j]) : dmax;
             zmax = __builtin_fabs(zs[j]) > zmax ? __builtin_fabs(zs[j]) : zmax;
+            tdmax = rc[j] > tdmax ? rc[j] : tdmax;
+            temax = rs[j] > temax ? rs[j] : temax;
         }
-        const double tol = 8.0 * 2.220446049250313e-16 * (dmax > zmax ? dmax : zmax);
+        // dlaed2's tolerance 8 eps max(|d|, |z|) is stated for a matrix dstedc has scaled to unit norm; nothing is scaled here, so
+        // the dimensionless z carries the node's norm max|d| + max|e| (maxima and a sum: a power of two times the matrix gives
+        // that power of two times tol, and every comparison below decides as before)
+        const double znorm = zmax * (tdmax + temax);
+        const double tol = 8.0 * 2.220446049250313e-16 * (dmax > znorm ? dmax : znorm);
         int k = 0, ndf = 0, nrot = 0, pj = -1;
         if (rho * zmax <= tol) {
             for (int j = 0; j < nn; ++j) defl[ndf++] = j;              // nothing couples the halves

@@ -1020,6 +1020,7 @@ struct DcPlan {
     dc::Node *d_nodes = nullptr;                       // all merges, level by level
     dc::Leaf *d_leaves = nullptr;
     char *scr = nullptr;                               // two vector buffers, U, the per-row arrays
+    int *info = nullptr;                               // a convergence word of the plan's own (ptmi_eig_dc_tridiag), in the slack of scr
 };
 static int dc_plan_get(ptmi_engine *h, int n, DcPlan **out)
 {
@@ -1059,6 +1060,7 @@ static int dc_plan_get(ptmi_engine *h, int n, DcPlan **out)
         delete P;
         return fail(PTMI_EHIP, "divide-and-conquer scratch: %s", hipGetErrorString(e));
     }
+    P->info = (int *)(P->scr + bytes) - 16;
     h->dc_plan = P;
     *out = P;
     return PTMI_OK;
@@ -1072,9 +1074,10 @@ void ptmi_dc_plan_free(ptmi_engine *h)
     h->dc_plan = nullptr;
 }
 // eigenvalues (ascending, *Dres) and eigenvectors (vector-major, *Zres) of the tridiagonal matrix (D, E), back-transformed through the
-// reflectors (A, tau) of the reduction; everything queued on st
+// reflectors (A, tau) of the reduction (A NULL: the tridiagonal matrix's own vectors); everything queued on st
 static int dc_solve(ptmi_engine *h, hipStream_t st, int n, const double *D, const double *E, const double *A, const double *tau,
-                    const double **Dres, const double **Zres, int *info /* device: zeroed by the caller; a leaf that did not converge sets it */)
+                    const double **Dres, const double **Zres, int *info /* device: zeroed by the caller; a leaf that did not converge sets it */,
+                    const int **cnt = nullptr /* device [2 * nnodes]: k and the number deflated of every merge */)
 {
     DcPlan *P = nullptr;
     if (int rc = dc_plan_get(h, n, &P)) return rc;
@@ -1096,7 +1099,7 @@ static int dc_solve(ptmi_engine *h, hipStream_t st, int n, const double *D, cons
     a.keepv = q; q += n; a.deflv = q; q += n; a.org = q; q += n; a.rankk = q; q += n; a.rankd = q; q += n;
     a.cnt = q;
     HIPCHK(hipMemcpyAsync(a.d, D, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(a.e, E, sizeof(double) * (n - 1), hipMemcpyDeviceToDevice, st));
+    if (n > 1) HIPCHK(hipMemcpyAsync(a.e, E, sizeof(double) * (n - 1), hipMemcpyDeviceToDevice, st));
     if (P->nnodes) hipLaunchKernelGGL(dc::split_kernel, dim3((P->nnodes + 63) / 64), dim3(64), 0, st, (const dc::Node *)P->d_nodes, P->nnodes, a.d, (const double *)a.e);
     HIPCHK(hipMemsetAsync(Qa, 0, sizeof(double) * nn, st));
     hipLaunchKernelGGL(dc::leaf_kernel, dim3(P->nleaves), dim3(64), 0, st, (const dc::Leaf *)P->d_leaves, n, (const double *)a.d, (const double *)a.e, Da, Qa, info);
@@ -1104,6 +1107,7 @@ static int dc_solve(ptmi_engine *h, hipStream_t st, int n, const double *D, cons
     for (int lv = 0; lv < P->nlevels; ++lv) {
         const int cnt = P->lvl_cnt[lv], nmax = P->lvl_nmax[lv];
         a.nodes = P->d_nodes + P->lvl_off[lv];
+        a.cnt = q + 2 * P->lvl_off[lv];
         a.Qin = Qin; a.Qout = Qout; a.Din = Din; a.Dout = Dout;
         HIPCHK(hipMemsetAsync(Qout, 0, sizeof(double) * nn, st));
         hipLaunchKernelGGL(dc::prep_kernel, dim3(cnt), dim3(dc::PREP_THREADS), 0, st, a);
@@ -1116,8 +1120,9 @@ static int dc_solve(ptmi_engine *h, hipStream_t st, int n, const double *D, cons
         double *tq = Qin; Qin = Qout; Qout = tq;
         double *td = Din; Din = Dout; Dout = td;
     }
-    hipLaunchKernelGGL(dc::backtransform_kernel, dim3((n + 4 * dc::VPW - 1) / (4 * dc::VPW)), dim3(256), 0, st, A, tau, n, Qin);
+    if (A) hipLaunchKernelGGL(dc::backtransform_kernel, dim3((n + 4 * dc::VPW - 1) / (4 * dc::VPW)), dim3(256), 0, st, A, tau, n, Qin);
     HIPCHK(hipGetLastError());
+    if (cnt) *cnt = q;
     *Dres = Din;
     *Zres = Qin;
     return PTMI_OK;
@@ -1177,6 +1182,7 @@ int ptmi_eig_sytrd_from(ptmi_handle h, void *stream, const double *cov_in, doubl
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(last[di], st));
     }
+    h->sy_reduced = 1;
     // the tridiagonal matrix's eigenvectors by the engine's own divide-and-conquer kernels, back-transformed through the reflectors
     const double *Dres = nullptr, *Zres = nullptr;
     if (int rc = dc_solve(h, st, n, D, E, A, tau, &Dres, &Zres, info)) return rc;
@@ -1196,5 +1202,63 @@ int ptmi_eig_sytrd_info(ptmi_handle h, int32_t *info)
 {
     if (!h || !info) return fail(PTMI_EINVAL, "NULL argument");
     *info = h->h_sy_info ? h->h_sy_info[0] : 0;
+    return PTMI_OK;
+}
+
+// the stages on their own (tests/test_eig_dc_gpu.py): the tridiagonal solver on the caller's matrix, and the reduction's output
+// a matrix that is ONE leaf (n <= dc::LEAF, no merge): the leaf's eigenvalues come in the order its QL iteration leaves them (the
+// merges sort their children's, ptmi_eig_sytrd sorts by size at the end) -- ranked ascending here, ties by position as in rank_kernel
+__global__ __launch_bounds__(64) void dc_leaf_sort_kernel(const double *D, const double *Q, int n, double *W, double *Z)
+{
+    const int t = (int)threadIdx.x;
+    if (t >= n) return;
+    const double mine = D[t];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) { const double o = D[j]; rank += (o < mine) || (o == mine && j < t); }
+    W[rank] = mine;
+    for (int i = 0; i < n; ++i) Z[(size_t)rank * n + i] = Q[(size_t)t * n + i];
+}
+
+int ptmi_eig_dc_tridiag(ptmi_handle h, void *stream, const double *d, const double *e, double *W, double *Z, int32_t *cnt)
+{
+    if (!h || !d || !W || !Z) return fail(PTMI_EINVAL, "NULL argument");
+    const int n = h->cfg.ndim;
+    if (n < 1 || n > dc::NMAX) return fail(PTMI_EUNSUPPORTED, "ptmi_eig_dc_tridiag: 1 <= ndim <= %d", dc::NMAX);
+    if (n > 1 && !e) return fail(PTMI_EINVAL, "NULL argument");
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    DcPlan *P = nullptr;
+    if (int rc = dc_plan_get(h, n, &P)) return rc;
+    HIPCHK(hipMemsetAsync(P->info, 0, sizeof(int), st));
+    const double *Dres = nullptr, *Zres = nullptr;
+    const int *counts = nullptr;
+    if (int rc = dc_solve(h, st, n, d, e, nullptr, nullptr, &Dres, &Zres, P->info, &counts)) return rc;
+    if (P->nlevels == 0) {
+        hipLaunchKernelGGL(dc_leaf_sort_kernel, dim3(1), dim3(64), 0, st, Dres, Zres, n, W, Z);
+        HIPCHK(hipGetLastError());
+    } else {
+        HIPCHK(hipMemcpyAsync(W, Dres, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(Z, Zres, sizeof(double) * n * n, hipMemcpyDeviceToDevice, st));
+    }
+    if (cnt && P->nnodes) HIPCHK(hipMemcpyAsync(cnt, counts, sizeof(int32_t) * 2 * P->nnodes, hipMemcpyDeviceToDevice, st));
+    if (!h->h_sy_info) {
+        HIPCHK(hipHostMalloc((void **)&h->h_sy_info, 2 * sizeof(int32_t)));
+        h->h_sy_info[0] = 0; h->h_sy_info[1] = 0;
+    }
+    HIPCHK(hipMemcpyAsync(h->h_sy_info, P->info, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    return PTMI_OK;
+}
+
+int ptmi_eig_sytrd_reduction(ptmi_handle h, void *stream, double *D, double *E, double *tau, double *A)
+{
+    if (!h || !D || !E || !tau || !A) return fail(PTMI_EINVAL, "NULL argument");
+    if (!h->d_sy_scr || !h->sy_reduced) return fail(PTMI_EINVAL, "ptmi_eig_sytrd_reduction: no ptmi_eig_sytrd has run on this handle");
+    const int n = h->cfg.ndim;
+    const size_t nn = (size_t)n * n;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    const double *As = (const double *)h->d_sy_scr, *Ds = As + nn, *Es = Ds + n, *ts = Es + n;
+    HIPCHK(hipMemcpyAsync(A, As, sizeof(double) * nn, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(D, Ds, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(E, Es, sizeof(double) * (n - 1), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(tau, ts, sizeof(double) * (n - 1), hipMemcpyDeviceToDevice, st));
     return PTMI_OK;
 }

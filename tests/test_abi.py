@@ -112,6 +112,22 @@ def test_swap_launch_report_matches_the_header(lib):
     assert [v.value for v in out] == [7] * 4
 
 
+def test_eigensolver_stage_drivers_match_the_header(lib):
+    """ptmi_eig_dc_tridiag and ptmi_eig_sytrd_reduction (the stages of ptmi_eig_sytrd on their own, tests/test_eig_dc_gpu.py): declared
+    with the arguments the tests pass, bound with them, and both refuse NULL arguments without touching a device."""
+    import ctypes as C
+    hdr = open(os.path.join(ROOT, "include", "ptmi.h")).read()
+    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert re.search(r"\bint\s+ptmi_eig_dc_tridiag\s*\(\s*ptmi_handle\s+h\s*,\s*void\s*\*\s*stream\s*,\s*const\s+double\s*\*\s*d\s*,"
+                     r"\s*const\s+double\s*\*\s*e\s*,\s*double\s*\*\s*W\s*,\s*double\s*\*\s*Z\s*,\s*int32_t\s*\*\s*cnt\s*\)\s*;", plain)
+    assert re.search(r"\bint\s+ptmi_eig_sytrd_reduction\s*\(\s*ptmi_handle\s+h\s*,\s*void\s*\*\s*stream\s*,\s*double\s*\*\s*D\s*,"
+                     r"\s*double\s*\*\s*E\s*,\s*double\s*\*\s*tau\s*,\s*double\s*\*\s*A\s*\)\s*;", plain)
+    L = lib.load()
+    assert L.ptmi_eig_dc_tridiag.argtypes == [C.c_void_p] * 7 and L.ptmi_eig_sytrd_reduction.argtypes == [C.c_void_p] * 6
+    assert L.ptmi_eig_dc_tridiag(None, None, None, None, None, None, None) == -1 and "NULL" in L.ptmi_last_error().decode()      # PTMI_EINVAL
+    assert L.ptmi_eig_sytrd_reduction(None, None, None, None, None, None) == -1 and "NULL" in L.ptmi_last_error().decode()
+
+
 def test_no_cpu_fallback(lib):
     """Without a device the product path refuses to run instead of computing on the host."""
     import numpy as np
