@@ -6,6 +6,7 @@
 // unrolled into a loop with an explicit stack of pending left subtrees in global scratch (same merges, same order of
 // draws).  Checked bit for bit against oracle/ptmcmc_oracle.c (nuts_call / hmc_call), which replays the reference.
 #pragma once
+#include <type_traits>
 #include "ptmi_common.h"
 
 
@@ -83,7 +84,7 @@ struct GradJump {
         return group_sum<G>(p);
     }
     // out[i] = sum_k T[k][i] v[k], k ascending, one fma per term.  WHICH >= 0: a whitening table (read through L2: these
-    // are the layouts of ndim > 32; the 4-lane shapes run GradJumpWide); WHICH < 0: the global table Tg.
+    // are the layouts of ndim > 32; the 4-lane shapes run GradJumpLanes); WHICH < 0: the global table Tg.
     template <int WHICH>
     __device__ __forceinline__ void tab_vec(const double *Tg, const double (&v)[EPL], double (&out)[EPL]) const
     {
@@ -512,498 +513,222 @@ __device__ __forceinline__ double lane_xor16(double v)
     return __longlong_as_double((long long)(((u64)h << 32) | l));
 }
 
-// GC = 16 (round 5; kernel shape (16, 7), ndim <= 64, diagonal whitening): the chain's sixteen lane groups are the wave's sixteen quads,
-// element i = g + 16 e in lane 4 g + e -- the 16-lane order of a dot product is then a chain along the quad (quad_perm shifts) and the
-// butterfly g ^ 8, 4, 2, 1 = lane ^ 32, 16, 8, 4 in the vector pipe (v_permlane32/16_swap, row rotations); the Box-Muller partners
-// (k, k + 16) are quad neighbours.  The template's EPL is then LD / 4 = 16.
-template <int EPL, int LOGL, int GC = 4, bool FULLTAB = false /* GC = 16: full whitening tables (else diagonal ones: decided at compile time there) */>
-struct GradJumpWide {
-    static constexpr int G = GC, NS = GC == 4 ? EPL : 4 /* slots of a lane group */, LD = GC * NS, LEV = gjw_level_doubles(LD / 4);
-    static_assert(GC == 4 || (GC == 16 && EPL == 16), "whole-wave layouts: 4 lane groups in rows of 16 lanes, or 16 lane groups in quads");
-    const KArgs &a;
-    const int d, L, we, wg, wi;
-    const bool act;                  // this lane holds an element of the chain's vectors
-    const int col;                   // its index (0 on idle lanes: their reads are dropped)
-    const long long ch, nch;
-    const double beta;
-    const long long it;
-    const u32 sid;
-    const int vb;                    // 64 doubles of the block's LDS: the vector of a table product, in element order
-    double blo = 0.0, bhi = 0.0;     // this lane's bounds of a box prior
-    double iv_lo = 0.0, iv_w = 0.0, iv_lw = 0.0;     // this lane's parameters of the interval family
-    u32 nm = 0, ns = 0, nleap = 0;
-#ifdef PTMI_GJ_PROFILE
-    mutable unsigned long long prof[GJP_N] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+// ---- the lane layouts of GradJumpLanes.  A layout owns what differs between them and nothing else: its constants (G lane groups
+// of NS slots, LD = G NS elements, CHAINS per wave, DRAWS lanes to a scalar-draw pass), the lane -> (we slot, wg lane group, hh
+// chain of the wave) map, the dot product in the 4-lane order (row_chain, rows_sum), the curved family's pair partner, "all / any
+// over the chain's lanes", a lane's slot in a scalar-draw pass and the broadcast of a cached draw word, the lane that writes the
+// chain's scalars and the ordering after those writes, the numbering of the tree-stack entries, the full-table product, and which
+// form of the dual-averaging update runs (GradJumpLanes::nuts).  The expressions are the ones each layout's kernels were tuned
+// with: tools/kernel_diff.py holds a change here to "same instructions" (profiles/r22_gj_lanes.txt).
+struct GjWholeWave {                 // one chain per wave: what its two layouts share
+    static constexpr int CHAINS = 1, DRAWS = 64;
+    static constexpr int hh(int) { return 0; }
+    __device__ __forceinline__ static bool all(bool ok, int) { return __ballot(ok) == ~0ull; }
+    __device__ __forceinline__ static bool any(bool v, int) { return __ballot(v) != 0ull; }
+    __device__ __forceinline__ static u32 draw_slot(int L) { return (u32)L; }
+    __device__ __forceinline__ static u32 draw_lane(u32 v, int src, int) { return (u32)__builtin_amdgcn_readlane((int)v, src); }
+    __device__ __forceinline__ static bool leader(int L) { return L == 0; }
+    // the chain's tree-stack entry of height h among the block's in LDS / among all in the global scratch
+    __device__ __forceinline__ static int lds_entry(const KArgs &, int h, int) { return h; }
+    __device__ __forceinline__ static size_t scr_entry(const KArgs &a, int h, int) { return (size_t)blockIdx.x * (size_t)(a.nuts_maxdepth + 1) + (size_t)h; }
+    __device__ __forceinline__ static void order() { __syncthreads(); }      // one wave per block: orders lane 0's writes before the others' reads
+    static constexpr bool DA_TWO_LANES = false;                              // the dual-averaging update as written in the reference
+};
 
-    __device__ __forceinline__ GradJumpWide(const KArgs &a_, long long ch_, double beta_, long long it_, u32 sid_, int vb_)
-        : a(a_), d(a_.d), L((int)threadIdx.x), we(GC == 4 ? (L & 15) : (L & 3)), wg(GC == 4 ? (L >> 4) : (L >> 2)), wi(wg + GC * we), act(we < NS && wi < a_.d), col(act ? wi : 0),
-          ch(ch_), nch((long long)a_.W * a_.nt), beta(beta_), it(it_), sid(sid_), vb(vb_)
-    {
-        if (a.logp_kind == PTMI_LOGP_BOX) { blo = a.logp_par[col]; bhi = a.logp_par[d + col]; }
-        if (LOGL == PTMI_LOGL_INTERVAL) { iv_lo = a.logl_par[col]; iv_w = a.logl_par[d + col]; iv_lw = a.logl_par[2 * d + col]; }
-    }
-
-    // ---- draws
-    __device__ __forceinline__ double momenta()                            // NJ:92-94; directions k and k + 4 share one Box-Muller
-    {
-        const u32 block = nm++;
-        double r = 0.0;
-        if (act) {
-            const int k = wg + GC * (we & ~1);
-            u64 e0, e1;
-            philox_words(a.seed, (u64)it, sid, SLOT_GJ + 4096u * block + (u32)k, e0, e1);
-            const double rr = det_sqrt(-2.0 * det_log(w2uniform_open(e0)));
-            double sn, cs;
-            det_sincos2pi(w2uniform(e1), sn, cs);
-            r = (we & 1) ? rr * sn : rr * cs;
-        }
-        return r;
-    }
-    // Scalar draws: slot n of the call is a Philox call of its own.  Lane j evaluates slot 64 b + j, so one pass of the
-    // generator (the same instructions a single draw would cost the wave) serves the next 64 draws of the call.
-    u64 sw_cache = 0;
-    u32 sw_base = 0xFFFFFFFFu;
-    __device__ __forceinline__ u64 scalar_word()
-    {
-        GJP_T0(t0);
-        const u32 slot = ns++;
-        if ((slot & ~63u) != sw_base) {
-            sw_base = slot & ~63u;
-            u64 w0, w1;
-            philox_words(a.seed, (u64)it, sid, SLOT_GJS + sw_base + (u32)L, w0, w1);
-            sw_cache = w0;
-        }
-        const int src = (int)(slot & 63u);
-        const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)sw_cache, src), hi = (u32)__builtin_amdgcn_readlane((int)(u32)(sw_cache >> 32), src);
-        GJP_ADD(GJP_DRAW, t0);
-        return ((u64)hi << 32) | lo;
-    }
-    __device__ __forceinline__ double uniform() { return w2uniform(scalar_word()); }
-    __device__ __forceinline__ double exponential() { return -det_log(w2uniform_open(scalar_word())); }
-    __device__ __forceinline__ int randint(int lo, int hi) { return lo + (int)w2index(scalar_word(), (u64)(hi - lo)); }
-
-    // ---- linear algebra
+// 4 lane groups in the wave's rows of 16 lanes (kernel shapes of 4 lanes, ndim <= 32): element i = g + 4 e in lane 16 g + e
+template <int EPL>
+struct GjRows16 : GjWholeWave {
+    static constexpr int G = 4, NS = EPL, LD = 4 * EPL;
+    static_assert(gjw_table_doubles(EPL) == 3 * LD * LD, "the LDS tables have rows of LD");
+    static constexpr int we(int L) { return L & 15; }
+    static constexpr int wg(int L) { return L >> 4; }
+    __device__ __forceinline__ static bool diagonal(const KArgs &a) { return (bool)a.gj_diag; }
     // Sum over the chain in the 4-lane order: per row the chain p = fma(x_e, y_e, p) over its slots.  Every lane recomputes
     // its link from its left neighbour's value in each of the EPL steps: lane e is right from step e + 1 on (lane 0 has no
     // neighbour and starts from 0), so after EPL steps lane EPL - 1 of row g holds the chain of lane group g; then (p0 + p2) + (p1 + p3).
-    __device__ __forceinline__ double row_chain(double x, double y) const
+    __device__ __forceinline__ static double row_chain(double x, double y, int)
     {
         double p = 0.0;
-        if constexpr (GC == 4) {
 #pragma unroll
-            for (int e = 0; e < EPL; ++e) p = __builtin_fma(x, y, dppf64<0x111>(p));      // row_shr:1, 0 into lane 0
-        } else {                                                         // along the quad: quad_perm [0, 0, 1, 2], the first lane starts from 0
-#pragma unroll
-            for (int e = 0; e < NS; ++e) {
-                const double left = dppf64<0x90>(p);
-                p = __builtin_fma(x, y, we == 0 ? 0.0 : left);
-            }
-        }
+        for (int e = 0; e < EPL; ++e) p = __builtin_fma(x, y, dppf64<0x111>(p));      // row_shr:1, 0 into lane 0
         return p;
     }
-    __device__ __forceinline__ double rows_sum(double p) const
+    __device__ __forceinline__ static double rows_sum(double p)
     {
-        if constexpr (GC == 16) {                                       // group_sum<16>'s butterfly over the lane groups, the chains' ends in lane 3 of the quads
-            double s = sum_xor32(p);                                     // g ^ 8
-            s = sum_xor16(s);                                            // g ^ 4
-            s = s + dppf64<0x128>(s);                                    // g ^ 2: row_ror:8
-            s = s + dppf64<0x124>(s);                                    // g ^ 1: row_ror:4 on data of period 8
-            return quad_bcastf<3>(s);
-        }
         const double p0 = lane_get(p, EPL - 1), p1 = lane_get(p, 16 + EPL - 1), p2 = lane_get(p, 32 + EPL - 1), p3 = lane_get(p, 48 + EPL - 1);
         return (p0 + p2) + (p1 + p3);
     }
-    __device__ __forceinline__ double dot(double x, double y) const
+    __device__ __forceinline__ static double partner(double v) { return lane_xor16(v); }      // lane group g ^ 1, same slot
+    template <int WHICH, class GJ>
+    __device__ __forceinline__ static double tab_product(const GJ &s, const double *Tg, double v)
     {
-        GJP_T0(t0);
-        const double r = rows_sum(row_chain(x, y));
-        GJP_ADD(GJP_DOT, t0);
-        return r;
-    }
-    // out[i] = sum_k T[k][i] v[k], k ascending, one fma per term; WHICH >= 0: the LDS copy of a whitening table (rows of LD)
-    template <int WHICH>
-    __device__ __forceinline__ double tab_vec(const double *Tg, double v) const
-    {
-        GJP_T0(t0);
-        double acc = 0.0;
-        if (WHICH >= 0 && (GC == 16 ? !FULLTAB : (bool)a.gj_diag)) {     // diagonal whitening table: one multiplication per element (oracle: tab_vec)
-            const double r = act ? gj_lds[WHICH * LD + col] * v : 0.0;  // (the block's LDS then holds the three diagonals only)
-            GJP_ADD(GJP_TABVEC, t0);
-            return r;
-        }
-        if constexpr (GC == 16) {
-            // 16 lane groups (ndim <= 64): the vector through LDS in element order as below, the table's rows from global memory (3 d^2
-            // doubles, cache resident: the LDS copies of 64 x 64 tables would leave one wave per CU), sixteen terms at a time
-            __syncthreads();
-            if (act) gj_lds[vb + wi] = v;
-            __syncthreads();
-            const double *T = WHICH >= 0 ? a.gj_tab + (size_t)WHICH * d * d : Tg;
-#pragma unroll 1
-            for (int k0 = 0; k0 < d; k0 += 16) {
-                double tk[16], vk[16];
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int k = k0 + j;
-                    tk[j] = T[(size_t)(k < d ? k : 0) * d + col];
-                    vk[j] = gj_lds[vb + (k < 64 ? k : 0)];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const double nxt = __builtin_fma(tk[j], vk[j], acc);
-                    acc = k0 + j < d ? nxt : acc;
-                }
-            }
-            GJP_ADD(GJP_TABVEC, t0);
-            return act ? acc : 0.0;
-        }
-        else {
         // The vector goes through LDS in element order and every lane reads all of it back (same address for the whole wave:
         // a broadcast); two readlanes per term instead had each fma wait on a fresh scalar pair.  Straight-line on purpose:
         // with a (wave-uniform) branch around every term each table read waited for its own LDS round trip -- 2 400 cycles
         // per product, more than half of a gradient jump.  Rows k >= d of the LDS tables are zeros; their terms are computed and dropped.
+        double acc = 0.0;
         __syncthreads();                                                 // the previous product's readers are through
-        if (act) gj_lds[vb + wi] = v;
+        if (s.act) gj_lds[s.vb + s.wi] = v;
         __syncthreads();
         // all reads first (the scheduling barrier keeps them there): left to the scheduler they went out two at a time
         // and the chain of fmas waited for an LDS round trip at every other term
-        double tk[4 * EPL], vk[4 * EPL];
+        double tk[LD], vk[LD];
 #pragma unroll
-        for (int k = 0; k < 4 * EPL; ++k) {
-            tk[k] = WHICH >= 0 ? gj_lds[(WHICH * LD + k) * LD + col] : Tg[(size_t)(k < d ? k : 0) * d + col];
-            vk[k] = gj_lds[vb + k];
+        for (int k = 0; k < LD; ++k) {
+            tk[k] = WHICH >= 0 ? gj_lds[(WHICH * LD + k) * LD + s.col] : Tg[(size_t)(k < s.d ? k : 0) * s.d + s.col];
+            vk[k] = gj_lds[s.vb + k];
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (d == 4 * EPL) {
+        if (s.d == LD) {
 #pragma unroll
-            for (int k = 0; k < 4 * EPL; ++k) acc = __builtin_fma(tk[k], vk[k], acc);
+            for (int k = 0; k < LD; ++k) acc = __builtin_fma(tk[k], vk[k], acc);
         } else {                                                         // (a uniform branch per term instead of the select is 4x slower)
 #pragma unroll
-            for (int k = 0; k < 4 * EPL; ++k) {
+            for (int k = 0; k < LD; ++k) {
                 const double nxt = __builtin_fma(tk[k], vk[k], acc);
-                acc = k < d ? nxt : acc;
+                acc = k < s.d ? nxt : acc;
             }
         }
-        GJP_ADD(GJP_TABVEC, t0);
-        return act ? acc : 0.0;
-        }
-    }
-    __device__ __forceinline__ double logl_grad(double x, double &g) const
-    {
-        GJP_T0(t0);
-        if (LOGL == PTMI_LOGL_ISO) {
-            g = -x;
-            const double r = -0.5 * dot(x, x);
-            GJP_ADD(GJP_LOGL, t0);
-            return r;
-        } else if (LOGL == PTMI_LOGL_DENSE) {
-            const double r = act ? x - a.logl_par[col] : 0.0;
-            const double v = tab_vec<-1>(a.logl_par + d, r);                 // the gradient -P r: the full product
-            g = -v;
-            const double vh = tab_vec<-1>(a.logl_par + d + (size_t)d * d, r);  // the value: eval_logl's half table Tl
-            const double rr = -dot(r, vh);
-            GJP_ADD(GJP_LOGL, t0);
-            return rr;
-        } else if (LOGL == PTMI_LOGL_INTERVAL) {
-            double gv;
-            const double t = interval_elem<true>(x, iv_lo, iv_w, iv_lw, gv);
-            g = act ? gv : 0.0;
-            const double r = dot(act ? t : 0.0, 1.0);
-            GJP_ADD(GJP_LOGL, t0);
-            return r;
-        } else {
-            auto partner = [&](double v) {                                 // the pair's other member: lane group g ^ 1, same slot
-                if constexpr (GC == 4) return lane_xor16(v);
-                else return __shfl_xor(v, 4, 64);
-            };
-            const double other = partner(x);
-            const bool even = !(wg & 1);
-            const bool pair = we < NS && (even ? wi + 1 < d : wi < d);
-            const double xx = even ? x : other, y = even ? other : x;
-            const double x2 = xx * xx;
-            const double gg = 9.0 + 4.0 * x2 + 9.0 * y;
-            const double l0 = -x2 - gg * gg;
-            const double ym = y - 2.0;
-            const double l1 = -8.0 * x2 - 8.0 * (ym * ym);
-            // both lanes of a pair hold the same l0 and l1: the even one takes exp(l0), the odd one exp(l1), and they trade
-            const double ex = det_exp(even ? l0 : l1), ox = partner(ex);
-            const double e0 = even ? ex : ox, e1 = 0.5 * (even ? ox : ex);
-            const double sum = e0 + e1;
-            const double tl = det_log(sum);                                // wanted on the even lanes only; same cost for the wave
-            const double d0 = even ? -2.0 * xx - 16.0 * gg * xx : -18.0 * gg;
-            const double d1 = even ? -16.0 * xx : -16.0 * ym;
-            const double gv = (e0 * d0 + e1 * d1) / sum;
-            g = pair ? gv : 0.0;
-            const double r = dot(pair && even ? tl : 0.0, 1.0);
-            GJP_ADD(GJP_LOGL, t0);
-            return r;
-        }
-    }
-    __device__ __forceinline__ double logp(double x) const
-    {
-        if (a.logp_kind == PTMI_LOGP_BOX) {
-            const bool ok = !act || ((blo <= x) & (bhi >= x));
-            return __ballot(ok) == ~0ull ? 0.0 : -__builtin_inf();
-        }
-        return 0.0;
-    }
-    __device__ __forceinline__ double func_grad_white(double q, double &gradw) const       // NJ:71-90
-    {
-        const double x = tab_vec<GJT_BACKWARD>(nullptr, q);
-        double g;
-        const double ll = logl_grad(x, g);
-        const double lp = logp(x);
-        g = beta * g + 0.0;
-        gradw = tab_vec<GJT_GRADIENT>(nullptr, g);
-        return beta * ll + lp;
-    }
-    __device__ __forceinline__ double joint_of(double logl, double r) const { return logl - 0.5 * dot(r, r); }
-    __device__ __forceinline__ double leapfrog(double theta, double r, double grad, double eps, double &to, double &ro, double &go)   // NJ:149-169
-    {
-        nleap += 1;
-        const double he = 0.5 * eps;
-        const double rh = r + he * grad;
-        const double tn = theta + eps * rh;
-        double gn;
-        const double lpp = func_grad_white(tn, gn);
-        to = tn;
-        go = gn;
-        ro = rh + he * gn;
-        return lpp;
-    }
-    __device__ __forceinline__ bool keep_going(double tm, double tp, double rm, double rp) const                // NJ:465-493
-    {
-        const double dt = tp - tm;
-        const double cx = row_chain(dt, rm), cy = row_chain(dt, rp);      // two independent chains: they overlap
-        const double x = rows_sum(cx), y = rows_sum(cy);
-        return (x >= 0.0) & (y >= 0.0);
-    }
-    __device__ __forceinline__ bool any_inf(double v) const { return __ballot(act && __builtin_isinf(v)) != 0ull; }
-
-    // ------------------------------------------------------------------ HMC (NJ:238-291)
-    __device__ __forceinline__ double hmc(double *st, double x, double &qout)
-    {
-        st[GJ_HITER] += 1.0;
-        double q = tab_vec<GJT_FORWARD>(nullptr, x), grad;
-        const double logp0 = func_grad_white(q, grad);
-        double p = momenta();
-        const double joint0 = joint_of(logp0, p);
-        const int nsteps = randint(a.hmc_min, a.hmc_max);
-        double joint1 = joint0;
-        for (int k = 0; k < nsteps; ++k) {
-            const double logp1 = leapfrog(q, p, grad, a.hmc_eps, q, p, grad);
-            joint1 = joint_of(logp1, p);
-            if (joint1 - 1000.0 < joint0) break;                         // NJ:284-286
-        }
-        qout = tab_vec<GJT_BACKWARD>(nullptr, q);
-        return joint1 - joint0;
-    }
-
-    // ------------------------------------------------------------------ NUTS
-    __device__ __forceinline__ double find_reasonable_epsilon(double theta0, double grad0, double logp0)   // NJ:435-463, loops bounded
-    {
-        double tp, rp, gp;
-        double eps = 1.0;
-        const double r0 = momenta();
-        double logpp = leapfrog(theta0, r0, grad0, eps, tp, rp, gp);
-        const bool ginf = any_inf(gp);                                   // not refreshed in the loop (NJ:449-452)
-        double k = 1.0;
-        for (int n = 0; n < 100 && (__builtin_isinf(logpp) || ginf); ++n) {
-            k *= 0.5;
-            logpp = leapfrog(theta0, r0, grad0, eps * k, tp, rp, gp);
-        }
-        eps = 0.5 * k * eps;
-        double ap = det_exp(joint_of(logpp, rp) - joint_of(logp0, r0));
-        const bool up = ap > 0.5;
-        for (int n = 0; n < 100 && ((up ? ap : 1.0 / ap) > (up ? 0.5 : 2.0)); ++n) {
-            eps = eps * (up ? 2.0 : 0.5);
-            logpp = leapfrog(theta0, r0, grad0, eps, tp, rp, gp);
-            ap = det_exp(joint_of(logpp, rp) - joint_of(logp0, r0));
-        }
-        return eps;
-    }
-
-    struct Tree {
-        double far_t, far_r, cand_t, cand_g;
-        double logp, alpha;
-        long long n, nalpha;
-        int s;
-    };
-    // the tree stack (see GradJump::build_tree): the entry of height h in slot h, pending heights in a mask.  Heights below
-    // gj_lds_levels (11: trees of up to 2^11 leapfrogs) are in the block's LDS; the higher ones -- the reference doubles without a
-    // cap (NJ:716-802), the ABI allows 24 -- in the wave's slice of the global scratch: reached once in 2^h leapfrogs, if ever,
-    // so only their correctness matters (keeping all 25 in LDS cost the config-5 kernel 25 %: five waves per CU instead of eight)
-    __device__ __forceinline__ int slot_of(int h) const { return a.gj_stack_off + h * LEV; }
-    __device__ __forceinline__ double *glevel(int h) const
-    {
-        return a.gj_scr + ((size_t)blockIdx.x * (size_t)(a.nuts_maxdepth + 1) + (size_t)h) * LEV;
-    }
-    // NJ:495-652 as a loop, as GradJump::build_tree
-    __device__ __forceinline__ void build_tree(double &tg, double &rg, double &gg, double logu, int v, int j, double eps, double joint0, Tree &cur)
-    {
-        u32 pend = 0;
-        for (;;) {
-            const double logpp = leapfrog(tg, rg, gg, (double)v * eps, tg, rg, gg);
-            GJP_T0(tl0);
-            const double joint = joint_of(logpp, rg);
-            cur.n = logu < joint;
-            cur.s = (logu - 1000.0) < joint;
-            cur.far_t = tg; cur.far_r = rg; cur.cand_t = tg; cur.cand_g = gg;
-            cur.logp = logpp;
-            const double ex = det_exp(joint - joint0);
-            cur.alpha = ex < 1.0 ? ex : 1.0;                             // Python's min(1.0, e): 1.0 when e is NaN
-            cur.nalpha = 1;
-            GJP_ADD(GJP_LEAF, tl0);
-            int h = 0;
-            for (;;) {
-                const int top_h = pend ? (int)__builtin_ctz(pend) : -1;
-                if (top_h == h) {                                        // cur is the right sibling of the stack top
-                    GJP_T0(tm0);
-                    pend &= pend - 1u;
-                    double t_logp, t_n, t_alpha, t_nalpha, e_ct, e_cg, e_ft, e_fr;
-                    if (h < a.gj_lds_levels) {                                     // wave-uniform
-                        const int b = slot_of(h);
-                        t_logp = gj_lds[b + GJL_VECS * LD + GJS_LOGP]; t_n = gj_lds[b + GJL_VECS * LD + GJS_N];
-                        t_alpha = gj_lds[b + GJL_VECS * LD + GJS_ALPHA]; t_nalpha = gj_lds[b + GJL_VECS * LD + GJS_NALPHA];
-                        e_ct = act ? gj_lds[b + GJL_CAND_T * LD + col] : 0.0; e_cg = act ? gj_lds[b + GJL_CAND_G * LD + col] : 0.0;
-                        e_ft = act ? gj_lds[b + GJL_FAR_T * LD + col] : 0.0; e_fr = act ? gj_lds[b + GJL_FAR_R * LD + col] : 0.0;
-                    } else {
-                        const double *gp = glevel(h);
-                        t_logp = gp[GJL_VECS * LD + GJS_LOGP]; t_n = gp[GJL_VECS * LD + GJS_N];
-                        t_alpha = gp[GJL_VECS * LD + GJS_ALPHA]; t_nalpha = gp[GJL_VECS * LD + GJS_NALPHA];
-                        e_ct = act ? gp[GJL_CAND_T * LD + col] : 0.0; e_cg = act ? gp[GJL_CAND_G * LD + col] : 0.0;
-                        e_ft = act ? gp[GJL_FAR_T * LD + col] : 0.0; e_fr = act ? gp[GJL_FAR_R * LD + col] : 0.0;
-                    }
-                    const long long tot = (long long)t_n + cur.n;
-                    const double den = (double)tot > 1.0 ? (double)tot : 1.0;
-                    const bool take_u = uniform() < (double)cur.n / den;
-                    if (!take_u) {
-                        cur.cand_t = e_ct;
-                        cur.cand_g = e_cg;
-                        cur.logp = t_logp;
-                    }
-                    cur.far_t = e_ft;
-                    cur.far_r = e_fr;
-                    cur.n = tot;
-                    const bool go = v == 1 ? keep_going(cur.far_t, tg, cur.far_r, rg) : keep_going(tg, cur.far_t, rg, cur.far_r);
-                    cur.s = cur.s && go;                                 // the popped tree has s = 1
-                    cur.alpha = t_alpha + cur.alpha;
-                    cur.nalpha = (long long)t_nalpha + cur.nalpha;
-                    h += 1;
-                    GJP_ADD(GJP_MERGE, tm0);
-                    continue;
-                }
-                if (h == j) return;
-                if (cur.s == 0) {
-                    if (pend == 0) return;
-                    h = top_h;
-                    continue;
-                }
-                GJP_T0(tp0);
-                if (h < a.gj_lds_levels) {                               // push: wait for the right sibling
-                    const int b = slot_of(h);
-                    if (act) {                                           // in element order: 4 LD doubles per entry instead of 4 x 64
-                        gj_lds[b + GJL_FAR_T * LD + wi] = cur.far_t;
-                        gj_lds[b + GJL_FAR_R * LD + wi] = cur.far_r;
-                        gj_lds[b + GJL_CAND_T * LD + wi] = cur.cand_t;
-                        gj_lds[b + GJL_CAND_G * LD + wi] = cur.cand_g;
-                    }
-                    if (L == 0) {
-                        gj_lds[b + GJL_VECS * LD + GJS_LOGP] = cur.logp;
-                        gj_lds[b + GJL_VECS * LD + GJS_N] = (double)cur.n;
-                        gj_lds[b + GJL_VECS * LD + GJS_ALPHA] = cur.alpha;
-                        gj_lds[b + GJL_VECS * LD + GJS_NALPHA] = (double)cur.nalpha;
-                    }
-                } else {
-                    double *gp = glevel(h);
-                    if (act) {
-                        gp[GJL_FAR_T * LD + wi] = cur.far_t;
-                        gp[GJL_FAR_R * LD + wi] = cur.far_r;
-                        gp[GJL_CAND_T * LD + wi] = cur.cand_t;
-                        gp[GJL_CAND_G * LD + wi] = cur.cand_g;
-                    }
-                    if (L == 0) {
-                        gp[GJL_VECS * LD + GJS_LOGP] = cur.logp;
-                        gp[GJL_VECS * LD + GJS_N] = (double)cur.n;
-                        gp[GJL_VECS * LD + GJS_ALPHA] = cur.alpha;
-                        gp[GJL_VECS * LD + GJS_NALPHA] = (double)cur.nalpha;
-                    }
-                    __threadfence_block();                               // the wave's own global stores, visible to its other lanes
-                }
-                __syncthreads();                                         // one wave per block: orders lane 0's writes before the others' reads
-                pend |= 1u << h;
-                GJP_ADD(GJP_PUSH, tp0);
-                break;
-            }
-        }
-    }
-
-    // NUTSJump.__call__ (NJ:654-840), as GradJump::nuts; the two ends of the trajectory and the sample stay in registers
-    __device__ __forceinline__ double nuts(double *st, double x, double &qout)
-    {
-        st[GJ_NITER] += 1.0;
-        const double q = tab_vec<GJT_FORWARD>(nullptr, x);
-        double grad;
-        const double logp0 = func_grad_white(q, grad);
-        if (st[GJ_HAVE_EPS] == 0.0) {
-            st[GJ_EPS] = find_reasonable_epsilon(q, grad, logp0);
-            st[GJ_MU] = det_log(10.0 * st[GJ_EPS]);
-            st[GJ_HAVE_EPS] = 1.0;
-        }
-        const double r0 = momenta();
-        const double joint = joint_of(logp0, r0);
-        const double logu = joint - exponential();
-        double lnprob = logp0;
-        double sample = q, tm = q, rm = r0, gm = grad, tp = q, rp = r0, gp = grad;
-        int j = 0, s = 1;
-        long long n = 1;
-        double alpha = 0.0;
-        long long nalpha = 1;
-        const double eps = st[GJ_EPS];
-        while (s == 1) {
-            const int dir = 2 * (int)(uniform() < 0.5) - 1;
-            double tg = dir == -1 ? tm : tp, rg = dir == -1 ? rm : rp, gg = dir == -1 ? gm : gp;
-            Tree t;
-            build_tree(tg, rg, gg, logu, dir, j, eps, joint, t);
-            if (dir == -1) { tm = tg; rm = rg; gm = gg; } else { tp = tg; rp = rg; gp = gg; }
-            if (t.s == 1) {
-                const double ratio = (double)t.n / (double)n;
-                if (uniform() < (1.0 < ratio ? 1.0 : ratio)) { sample = t.cand_t; lnprob = t.logp; }
-            }
-            n += t.n;
-            const bool go = keep_going(tm, tp, rm, rp);
-            s = t.s && go;
-            alpha = t.alpha;
-            nalpha = t.nalpha;
-            j += 1;
-            if (j > a.nuts_maxdepth) s = 0;                              // cap (not in the reference)
-        }
-        // dual averaging (NJ:805-816): gamma = 0.05, t0 = 10, kappa = 0.75
-        const double it_call = st[GJ_NITER];
-        double eta = 1.0 / (it_call + 10.0);
-        st[GJ_HBAR] = (1.0 - eta) * st[GJ_HBAR] + eta * (a.nuts_delta - alpha / (double)nalpha);
-        if (it <= (long long)a.gj_nburn) {
-            st[GJ_EPS] = det_exp(st[GJ_MU] - det_sqrt(it_call) / 0.05 * st[GJ_HBAR]);
-            eta = det_exp(-0.75 * det_log(it_call));
-            st[GJ_EPSBAR] = det_exp((1.0 - eta) * det_log(st[GJ_EPSBAR]) + eta * det_log(st[GJ_EPS]));
-        } else {
-            st[GJ_EPS] = st[GJ_EPSBAR];
-        }
-        qout = tab_vec<GJT_BACKWARD>(nullptr, sample);
-        return logp0 - lnprob;                                           // undoes the outer Hastings ratio (NJ:838)
+        return acc;
     }
 };
 
+// 16 lane groups in the wave's quads (round 5; kernel shape (16, 7), ndim <= 64): element i = g + 16 e in lane 4 g + e -- the 16-lane
+// order of a dot product is then a chain along the quad (quad_perm shifts) and the butterfly g ^ 8, 4, 2, 1 = lane ^ 32, 16, 8, 4 in
+// the vector pipe (v_permlane32/16_swap, row rotations); the Box-Muller partners (k, k + 16) are quad neighbours.
+template <bool FULLTAB /* full whitening tables (else diagonal ones: decided at compile time here) */>
+struct GjQuads : GjWholeWave {
+    static constexpr int G = 16, NS = 4, LD = 64;
+    static constexpr int we(int L) { return L & 3; }
+    static constexpr int wg(int L) { return L >> 2; }
+    __device__ __forceinline__ static bool diagonal(const KArgs &) { return !FULLTAB; }
+    __device__ __forceinline__ static double row_chain(double x, double y, int we)
+    {
+        double p = 0.0;                                                  // along the quad: quad_perm [0, 0, 1, 2], the first lane starts from 0
+#pragma unroll
+        for (int e = 0; e < NS; ++e) {
+            const double left = dppf64<0x90>(p);
+            p = __builtin_fma(x, y, we == 0 ? 0.0 : left);
+        }
+        return p;
+    }
+    __device__ __forceinline__ static double rows_sum(double p)          // group_sum<16>'s butterfly over the lane groups, the chains' ends in lane 3 of the quads
+    {
+        double s = sum_xor32(p);                                         // g ^ 8
+        s = sum_xor16(s);                                                // g ^ 4
+        s = s + dppf64<0x128>(s);                                        // g ^ 2: row_ror:8
+        s = s + dppf64<0x124>(s);                                        // g ^ 1: row_ror:4 on data of period 8
+        return quad_bcastf<3>(s);
+    }
+    __device__ __forceinline__ static double partner(double v) { return __shfl_xor(v, 4, 64); }
+    template <int WHICH, class GJ>
+    __device__ __forceinline__ static double tab_product(const GJ &s, const double *Tg, double v)
+    {
+        // the vector through LDS in element order as in GjRows16, the table's rows from global memory (3 d^2 doubles, cache
+        // resident: the LDS copies of 64 x 64 tables would leave one wave per CU), sixteen terms at a time
+        double acc = 0.0;
+        __syncthreads();
+        if (s.act) gj_lds[s.vb + s.wi] = v;
+        __syncthreads();
+        const double *T = WHICH >= 0 ? s.a.gj_tab + (size_t)WHICH * s.d * s.d : Tg;
+#pragma unroll 1
+        for (int k0 = 0; k0 < s.d; k0 += 16) {
+            double tk[16], vk[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int k = k0 + j;
+                tk[j] = T[(size_t)(k < s.d ? k : 0) * s.d + s.col];
+                vk[j] = gj_lds[s.vb + (k < 64 ? k : 0)];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const double nxt = __builtin_fma(tk[j], vk[j], acc);
+                acc = k0 + j < s.d ? nxt : acc;
+            }
+        }
+        return acc;
+    }
+};
 
-template <int EPL, int LOGL>
-struct GradJumpPair {
-    static constexpr int G = 4, LD = 4 * EPL;
-    // TWO chains per wave: chain slot hh = lane >> 5 owns a half-wave.  Inside its half a chain's lane group g = 2 r + sub sits in
-    // row r = (lane >> 4) & 1 at lanes 8 sub .. 8 sub + EPL - 1 (element i = g + 4 e in lane 16 r + 8 sub + e): row shifts and the
-    // xor-8 partner stay inside a row, everything else goes through ds_bpermute inside the half.  Every "scalar" of a call is a
-    // per-lane value (it was one already: f64 arithmetic is vector arithmetic), so the two calls run as one instruction stream and
-    // part ways only where their control flow does (divergent branches; the halves never read each other's lanes).
+// TWO chains per wave (round 5; 4-lane shapes with diagonal whitening, iso / curved families): chain hh = lane >> 5 owns a half-wave.
+// Inside its half a chain's lane group g = 2 r + sub sits in row r = (lane >> 4) & 1 at lanes 8 sub .. 8 sub + EPL - 1 (element
+// i = g + 4 e in lane 16 r + 8 sub + e): row shifts and the xor-8 partner stay inside a row, everything else goes through ds_bpermute
+// inside the half.  Every "scalar" of a call is a per-lane value (it was one already: f64 arithmetic is vector arithmetic), so the
+// two calls run as one instruction stream and part ways only where their control flow does (divergent branches; the halves never
+// read each other's lanes).
+template <int EPL>
+struct GjHalves {
+    static constexpr int G = 4, NS = EPL, LD = 4 * EPL, CHAINS = 2, DRAWS = 32;
+    static constexpr int hh(int L) { return L >> 5; }
+    static constexpr int we(int L) { return L & 7; }
+    static constexpr int wg(int L) { return 2 * ((L >> 4) & 1) + ((L >> 3) & 1); }
+    __device__ __forceinline__ static u32 draw_slot(int L) { return (u32)(L & 31); }
+    __device__ __forceinline__ static u32 draw_lane(u32 v, int src, int hh) { return (u32)__builtin_amdgcn_ds_bpermute(((hh << 5) + src) << 2, (int)v); }
+    __device__ __forceinline__ static double half_lanef(double v, int src, int hh)
+    {
+        const u64 b = (u64)__double_as_longlong(v);
+        return __longlong_as_double((long long)(((u64)draw_lane((u32)(b >> 32), src, hh) << 32) | draw_lane((u32)b, src, hh)));
+    }
+    __device__ __forceinline__ static bool all(bool ok, int hh) { return ((__ballot(ok) >> (hh << 5)) & 0xFFFFFFFFull) == 0xFFFFFFFFull; }
+    __device__ __forceinline__ static bool any(bool v, int hh) { return ((__ballot(v) >> (hh << 5)) & 0xFFFFFFFFull) != 0ull; }
+    __device__ __forceinline__ static bool leader(int L) { return (L & 31) == 0; }
+    __device__ __forceinline__ static int lds_entry(const KArgs &a, int h, int hh) { return hh * a.gj_lds_levels + h; }
+    __device__ __forceinline__ static size_t scr_entry(const KArgs &a, int h, int hh)
+    {
+        return ((size_t)blockIdx.x * 2 + (size_t)hh) * (size_t)(a.nuts_maxdepth + 1) + (size_t)h;
+    }
+    // one wave: its LDS / global accesses are served in order; the fence orders the compiler (no barrier inside divergent code)
+    __device__ __forceinline__ static void order() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
+    __device__ __forceinline__ static bool diagonal(const KArgs &a) { return (bool)a.gj_diag; }
+    __device__ __forceinline__ static double row_chain(double x, double y, int we)
+    {
+        double p = 0.0;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+            const double left = dppf64<0x111>(p);                       // row_shr:1
+            p = __builtin_fma(x, y, we == 0 ? 0.0 : left);              // a lane group's chain starts from 0 at its first lane
+        }
+        return p;
+    }
+    // (p0 + p2) + (p1 + p3) of the four lane groups' chains (lane EPL - 1 of the half's four rows of eight), on every lane of the
+    // half, in the vector pipe: lanes 16 apart through v_permlane16_swap, 8 apart through a row rotation, then the row's lane
+    // EPL - 1 to the whole row (row_newbcast).  Four ds_bpermute pairs took an LDS round trip on the critical path of every
+    // dot product -- four to a leapfrog of a deep tree, whose chain of dependent instructions is what a launch lasts (§3.5).
+    __device__ __forceinline__ static double rows_sum(double p)
+    {
+        double s = sum_xor16(p);                                        // rows 0 + 1 (2 + 3) of the half: (p0 + p2) at lane EPL - 1, (p1 + p3) at lane 8 + EPL - 1
+        s = s + dppf64<0x128>(s);                                       // row_ror:8: (p0 + p2) + (p1 + p3), or the same two terms the other way round
+        return dppf64<0x150 + EPL - 1>(s);
+    }
+    __device__ __forceinline__ static double partner(double v) { return dppf64<0x128>(v); }   // lane group g ^ 1 = lane ^ 8 (row_ror:8), same slot
+    // (this layout runs with diagonal whitening tables and the iso / curved families only: the host picks it then)
+    template <int WHICH, class GJ>
+    __device__ __forceinline__ static double tab_product(const GJ &, const double *, double) { __builtin_trap(); return 0.0; }
+    static constexpr bool DA_TWO_LANES = true;                               // the dual-averaging update evaluates side by side on two lanes (half_lanef)
+};
+
+// the lane <-> element map of a layout: over lanes 0..63 the active lanes of each chain hold every element 0 .. LD - 1 exactly once
+template <class Lay>
+constexpr bool gj_lane_map_ok()
+{
+    int active = 0;
+    for (int L = 0; L < 64; ++L) active += Lay::we(L) < Lay::NS;
+    for (int c = 0; c < Lay::CHAINS; ++c)
+        for (int i = 0; i < Lay::LD; ++i) {
+            int n = 0;
+            for (int L = 0; L < 64; ++L) n += Lay::hh(L) == c && Lay::we(L) < Lay::NS && Lay::wg(L) + Lay::G * Lay::we(L) == i;
+            if (n != 1) return false;
+        }
+    return active == Lay::CHAINS * Lay::LD;
+}
+
+// One chain's gradient jump on the lanes of a layout Lay (GjRows16, GjQuads, GjHalves): the code of GradJump with one element per lane
+template <class Lay, int LOGL>
+struct GradJumpLanes {
+    static constexpr int G = Lay::G, NS = Lay::NS /* slots of a lane group */, LD = Lay::LD, LEV = GJL_VECS * LD + GJS_SCALARS /* a stack entry */;
+    static_assert(gj_lane_map_ok<Lay>(), "every element of a chain vector in exactly one lane");
+    static_assert(LEV == gjw_level_doubles(LD / 4), "the stack entry the host's LDS budget counts");
     const KArgs &a;
     const int d, L, hh, we, wg, wi;
     const bool act;                  // this lane holds an element of the chain's vectors
@@ -1020,29 +745,21 @@ struct GradJumpPair {
     mutable unsigned long long prof[GJP_N] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
 
-    __device__ __forceinline__ GradJumpPair(const KArgs &a_, long long ch_, double beta_, long long it_, u32 sid_, int vb_)
-        : a(a_), d(a_.d), L((int)threadIdx.x), hh(L >> 5), we(L & 7), wg(2 * ((L >> 4) & 1) + ((L >> 3) & 1)), wi(wg + 4 * we), act(we < EPL && wi < a_.d), col(act ? wi : 0),
+    __device__ __forceinline__ GradJumpLanes(const KArgs &a_, long long ch_, double beta_, long long it_, u32 sid_, int vb_)
+        : a(a_), d(a_.d), L((int)threadIdx.x), hh(Lay::hh(L)), we(Lay::we(L)), wg(Lay::wg(L)), wi(wg + G * we), act(we < NS && wi < a_.d), col(act ? wi : 0),
           ch(ch_), nch((long long)a_.W * a_.nt), beta(beta_), it(it_), sid(sid_), vb(vb_)
     {
         if (a.logp_kind == PTMI_LOGP_BOX) { blo = a.logp_par[col]; bhi = a.logp_par[d + col]; }
         if (LOGL == PTMI_LOGL_INTERVAL) { iv_lo = a.logl_par[col]; iv_w = a.logl_par[d + col]; iv_lw = a.logl_par[2 * d + col]; }
     }
 
-    __device__ __forceinline__ u32 half_lane32(u32 v, int src) const { return (u32)__builtin_amdgcn_ds_bpermute(((hh << 5) + src) << 2, (int)v); }
-    __device__ __forceinline__ double half_lanef(double v, int src) const
-    {
-        const u64 b = (u64)__double_as_longlong(v);
-        return __longlong_as_double((long long)(((u64)half_lane32((u32)(b >> 32), src) << 32) | half_lane32((u32)b, src)));
-    }
-    __device__ __forceinline__ bool half_all(bool ok) const { return ((__ballot(ok) >> (hh << 5)) & 0xFFFFFFFFull) == 0xFFFFFFFFull; }
-    __device__ __forceinline__ bool half_any(bool v) const { return ((__ballot(v) >> (hh << 5)) & 0xFFFFFFFFull) != 0ull; }
     // ---- draws
-    __device__ __forceinline__ double momenta()                            // NJ:92-94; directions k and k + 4 share one Box-Muller
+    __device__ __forceinline__ double momenta()                            // NJ:92-94; directions k and k + G share one Box-Muller
     {
         const u32 block = nm++;
         double r = 0.0;
         if (act) {
-            const int k = wg + 4 * (we & ~1);
+            const int k = wg + G * (we & ~1);
             u64 e0, e1;
             philox_words(a.seed, (u64)it, sid, SLOT_GJ + 4096u * block + (u32)k, e0, e1);
             const double rr = det_sqrt(-2.0 * det_log(w2uniform_open(e0)));
@@ -1052,22 +769,24 @@ struct GradJumpPair {
         }
         return r;
     }
-    // Scalar draws: slot n of the call is a Philox call of its own.  Lane j evaluates slot 64 b + j, so one pass of the
-    // generator (the same instructions a single draw would cost the wave) serves the next 64 draws of the call.
+    // Scalar draws: slot n of the call is a Philox call of its own.  Lane j of the chain's DRAWS lanes (the wave, or its half)
+    // evaluates slot DRAWS b + j, so one pass of the generator (the same instructions a single draw would cost the wave) serves
+    // the next DRAWS draws of the call.
     u64 sw_cache = 0;
     u32 sw_base = 0xFFFFFFFFu;
     __device__ __forceinline__ u64 scalar_word()
     {
         GJP_T0(t0);
+        constexpr u32 M = Lay::DRAWS - 1;
         const u32 slot = ns++;
-        if ((slot & ~31u) != sw_base) {                                  // (per half: lane j of the half evaluates slot 32 b + j of ITS chain's call)
-            sw_base = slot & ~31u;
+        if ((slot & ~M) != sw_base) {
+            sw_base = slot & ~M;
             u64 w0, w1;
-            philox_words(a.seed, (u64)it, sid, SLOT_GJS + sw_base + (u32)(L & 31), w0, w1);
+            philox_words(a.seed, (u64)it, sid, SLOT_GJS + sw_base + Lay::draw_slot(L), w0, w1);
             sw_cache = w0;
         }
-        const int src = (int)(slot & 31u);
-        const u32 lo = half_lane32((u32)sw_cache, src), hi = half_lane32((u32)(sw_cache >> 32), src);
+        const int src = (int)(slot & M);
+        const u32 lo = Lay::draw_lane((u32)sw_cache, src, hh), hi = Lay::draw_lane((u32)(sw_cache >> 32), src, hh);
         GJP_ADD(GJP_DRAW, t0);
         return ((u64)hi << 32) | lo;
     }
@@ -1075,76 +794,27 @@ struct GradJumpPair {
     __device__ __forceinline__ double exponential() { return -det_log(w2uniform_open(scalar_word())); }
     __device__ __forceinline__ int randint(int lo, int hi) { return lo + (int)w2index(scalar_word(), (u64)(hi - lo)); }
 
-    // ---- linear algebra
-    // Sum over the chain in the 4-lane order: per row the chain p = fma(x_e, y_e, p) over its slots.  Every lane recomputes
-    // its link from its left neighbour's value in each of the EPL steps: lane e is right from step e + 1 on (lane 0 has no
-    // neighbour and starts from 0), so after EPL steps lane EPL - 1 of row g holds the chain of lane group g; then (p0 + p2) + (p1 + p3).
-    __device__ __forceinline__ double row_chain(double x, double y) const
-    {
-        double p = 0.0;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            const double left = dppf64<0x111>(p);                       // row_shr:1
-            p = __builtin_fma(x, y, we == 0 ? 0.0 : left);              // a lane group's chain starts from 0 at its first lane
-        }
-        return p;
-    }
-    // (p0 + p2) + (p1 + p3) of the four lane groups' chains (lane EPL - 1 of the half's four rows of eight), on every lane of the
-    // half, in the vector pipe: lanes 16 apart through v_permlane16_swap, 8 apart through a row rotation, then the row's lane
-    // EPL - 1 to the whole row (row_newbcast).  Four ds_bpermute pairs took an LDS round trip on the critical path of every
-    // dot product -- four to a leapfrog of a deep tree, whose chain of dependent instructions is what a launch lasts (§3.5).
-    __device__ __forceinline__ double rows_sum(double p) const
-    {
-        double s = sum_xor16(p);                                        // rows 0 + 1 (2 + 3) of the half: (p0 + p2) at lane EPL - 1, (p1 + p3) at lane 8 + EPL - 1
-        s = s + dppf64<0x128>(s);                                       // row_ror:8: (p0 + p2) + (p1 + p3), or the same two terms the other way round
-        return dppf64<0x150 + EPL - 1>(s);
-    }
+    // ---- linear algebra: a sum over the chain in the 4-lane (16-lane) order is the layout's chain of fmas along a lane group's
+    // slots, then its sum over the lane groups
+    __device__ __forceinline__ double row_chain(double x, double y) const { return Lay::row_chain(x, y, we); }
     __device__ __forceinline__ double dot(double x, double y) const
     {
         GJP_T0(t0);
-        const double r = rows_sum(row_chain(x, y));
+        const double r = Lay::rows_sum(row_chain(x, y));
         GJP_ADD(GJP_DOT, t0);
         return r;
     }
-    // out[i] = sum_k T[k][i] v[k], k ascending, one fma per term; WHICH >= 0: the LDS copy of a whitening table (rows of LD)
+    // out[i] = sum_k T[k][i] v[k], k ascending, one fma per term; WHICH >= 0: a whitening table, WHICH < 0: the global table Tg
     template <int WHICH>
     __device__ __forceinline__ double tab_vec(const double *Tg, double v) const
     {
         GJP_T0(t0);
-        double acc = 0.0;
-        if (WHICH >= 0 && a.gj_diag) {                                   // diagonal whitening table: one multiplication per element (oracle: tab_vec)
+        if (WHICH >= 0 && Lay::diagonal(a)) {                            // diagonal whitening table: one multiplication per element (oracle: tab_vec)
             const double r = act ? gj_lds[WHICH * LD + col] * v : 0.0;  // (the block's LDS then holds the three diagonals only)
             GJP_ADD(GJP_TABVEC, t0);
             return r;
         }
-        // (the pair layout runs with diagonal whitening tables and the iso / curved families only: the host picks it then)
-        __builtin_trap();
-        // The vector goes through LDS in element order and every lane reads all of it back (same address for the whole wave:
-        // a broadcast); two readlanes per term instead had each fma wait on a fresh scalar pair.  Straight-line on purpose:
-        // with a (wave-uniform) branch around every term each table read waited for its own LDS round trip -- 2 400 cycles
-        // per product, more than half of a gradient jump.  Rows k >= d of the LDS tables are zeros; their terms are computed and dropped.
-        __syncthreads();                                                 // the previous product's readers are through
-        if (act) gj_lds[vb + wi] = v;
-        __syncthreads();
-        // all reads first (the scheduling barrier keeps them there): left to the scheduler they went out two at a time
-        // and the chain of fmas waited for an LDS round trip at every other term
-        double tk[4 * EPL], vk[4 * EPL];
-#pragma unroll
-        for (int k = 0; k < 4 * EPL; ++k) {
-            tk[k] = WHICH >= 0 ? gj_lds[(WHICH * LD + k) * LD + col] : Tg[(size_t)(k < d ? k : 0) * d + col];
-            vk[k] = gj_lds[vb + k];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (d == 4 * EPL) {
-#pragma unroll
-            for (int k = 0; k < 4 * EPL; ++k) acc = __builtin_fma(tk[k], vk[k], acc);
-        } else {                                                         // (a uniform branch per term instead of the select is 4x slower)
-#pragma unroll
-            for (int k = 0; k < 4 * EPL; ++k) {
-                const double nxt = __builtin_fma(tk[k], vk[k], acc);
-                acc = k < d ? nxt : acc;
-            }
-        }
+        const double acc = Lay::template tab_product<WHICH>(*this, Tg, v);
         GJP_ADD(GJP_TABVEC, t0);
         return act ? acc : 0.0;
     }
@@ -1172,9 +842,9 @@ struct GradJumpPair {
             GJP_ADD(GJP_LOGL, t0);
             return r;
         } else {
-            const double other = dppf64<0x128>(x);                         // the pair's other member: lane group g ^ 1 = lane ^ 8 (row_ror:8), same slot
+            const double other = Lay::partner(x);                           // the pair's other member: lane group g ^ 1, same slot
             const bool even = !(wg & 1);
-            const bool pair = we < EPL && (even ? wi + 1 < d : wi < d);
+            const bool pair = we < NS && (even ? wi + 1 < d : wi < d);
             const double xx = even ? x : other, y = even ? other : x;
             const double x2 = xx * xx;
             const double gg = 9.0 + 4.0 * x2 + 9.0 * y;
@@ -1182,7 +852,7 @@ struct GradJumpPair {
             const double ym = y - 2.0;
             const double l1 = -8.0 * x2 - 8.0 * (ym * ym);
             // both lanes of a pair hold the same l0 and l1: the even one takes exp(l0), the odd one exp(l1), and they trade
-            const double ex = det_exp(even ? l0 : l1), ox = dppf64<0x128>(ex);
+            const double ex = det_exp(even ? l0 : l1), ox = Lay::partner(ex);
             const double e0 = even ? ex : ox, e1 = 0.5 * (even ? ox : ex);
             const double sum = e0 + e1;
             const double tl = det_log(sum);                                // wanted on the even lanes only; same cost for the wave
@@ -1199,7 +869,7 @@ struct GradJumpPair {
     {
         if (a.logp_kind == PTMI_LOGP_BOX) {
             const bool ok = !act || ((blo <= x) & (bhi >= x));
-            return half_all(ok) ? 0.0 : -__builtin_inf();
+            return Lay::all(ok, hh) ? 0.0 : -__builtin_inf();
         }
         return 0.0;
     }
@@ -1231,10 +901,10 @@ struct GradJumpPair {
     {
         const double dt = tp - tm;
         const double cx = row_chain(dt, rm), cy = row_chain(dt, rp);      // two independent chains: they overlap
-        const double x = rows_sum(cx), y = rows_sum(cy);
+        const double x = Lay::rows_sum(cx), y = Lay::rows_sum(cy);
         return (x >= 0.0) & (y >= 0.0);
     }
-    __device__ __forceinline__ bool any_inf(double v) const { return half_any(act && __builtin_isinf(v)); }
+    __device__ __forceinline__ bool any_inf(double v) const { return Lay::any(act && __builtin_isinf(v), hh); }
 
     // ------------------------------------------------------------------ HMC (NJ:238-291)
     __device__ __forceinline__ double hmc(double *st, double x, double &qout)
@@ -1288,12 +958,10 @@ struct GradJumpPair {
     // the tree stack (see GradJump::build_tree): the entry of height h in slot h, pending heights in a mask.  Heights below
     // gj_lds_levels (11: trees of up to 2^11 leapfrogs) are in the block's LDS; the higher ones -- the reference doubles without a
     // cap (NJ:716-802), the ABI allows 24 -- in the wave's slice of the global scratch: reached once in 2^h leapfrogs, if ever,
-    // so only their correctness matters (keeping all 25 in LDS cost the config-5 kernel 25 %: five waves per CU instead of eight)
-    __device__ __forceinline__ int slot_of(int h) const { return a.gj_stack_off + (hh * a.gj_lds_levels + h) * gjw_level_doubles(EPL); }
-    __device__ __forceinline__ double *glevel(int h) const
-    {
-        return a.gj_scr + (((size_t)blockIdx.x * 2 + (size_t)hh) * (size_t)(a.nuts_maxdepth + 1) + (size_t)h) * gjw_level_doubles(EPL);
-    }
+    // so only their correctness matters (keeping all 25 in LDS cost the config-5 kernel 25 %: five waves per CU instead of eight).
+    // Each of the wave's chains has a stack of its own in both: the layout numbers the entries.
+    __device__ __forceinline__ int slot_of(int h) const { return a.gj_stack_off + Lay::lds_entry(a, h, hh) * LEV; }
+    __device__ __forceinline__ double *glevel(int h) const { return a.gj_scr + Lay::scr_entry(a, h, hh) * LEV; }
     // NJ:495-652 as a loop, as GradJump::build_tree
     __device__ __forceinline__ void build_tree(double &tg, double &rg, double &gg, double logu, int v, int j, double eps, double joint0, Tree &cur)
     {
@@ -1364,7 +1032,7 @@ struct GradJumpPair {
                         gj_lds[b + GJL_CAND_T * LD + wi] = cur.cand_t;
                         gj_lds[b + GJL_CAND_G * LD + wi] = cur.cand_g;
                     }
-                    if ((L & 31) == 0) {
+                    if (Lay::leader(L)) {
                         gj_lds[b + GJL_VECS * LD + GJS_LOGP] = cur.logp;
                         gj_lds[b + GJL_VECS * LD + GJS_N] = (double)cur.n;
                         gj_lds[b + GJL_VECS * LD + GJS_ALPHA] = cur.alpha;
@@ -1378,7 +1046,7 @@ struct GradJumpPair {
                         gp[GJL_CAND_T * LD + wi] = cur.cand_t;
                         gp[GJL_CAND_G * LD + wi] = cur.cand_g;
                     }
-                    if ((L & 31) == 0) {
+                    if (Lay::leader(L)) {
                         gp[GJL_VECS * LD + GJS_LOGP] = cur.logp;
                         gp[GJL_VECS * LD + GJS_N] = (double)cur.n;
                         gp[GJL_VECS * LD + GJS_ALPHA] = cur.alpha;
@@ -1386,7 +1054,7 @@ struct GradJumpPair {
                     }
                     __threadfence_block();                               // the wave's own global stores, visible to its other lanes
                 }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");    // one wave: its LDS / global accesses are served in order; the fence orders the compiler (no barrier inside divergent code)
+                Lay::order();                                            // the leader's writes before the other lanes' reads
                 pend |= 1u << h;
                 GJP_ADD(GJP_PUSH, tp0);
                 break;
@@ -1438,19 +1106,23 @@ struct GradJumpPair {
         const double it_call = st[GJ_NITER];
         double eta = 1.0 / (it_call + 10.0);
         st[GJ_HBAR] = (1.0 - eta) * st[GJ_HBAR] + eta * (a.nuts_delta - alpha / (double)nalpha);
-        if (it <= (long long)a.gj_nburn) {
+        if (it > (long long)a.gj_nburn) st[GJ_EPS] = st[GJ_EPSBAR];
+        else if constexpr (Lay::DA_TWO_LANES) {
             // seven evaluations of exp / log on values every lane of the half holds alike: the independent ones go side by side on
             // two lanes (log it_call beside log eps_bar, then the two exponentials), four evaluations deep instead of seven; the
-            // same functions of the same arguments
+            // same functions of the same arguments.  (Written here and not in the layout: behind a call of the layout's the
+            // compiler numbers the registers of the loop above differently.)
             const bool odd = L & 1;
             const double lg = det_log(odd ? st[GJ_EPSBAR] : it_call);
-            const double log_it = half_lanef(lg, 0), log_epsbar = half_lanef(lg, 1);
+            const double log_it = Lay::half_lanef(lg, 0, hh), log_epsbar = Lay::half_lanef(lg, 1, hh);
             const double ex = det_exp(odd ? -0.75 * log_it : st[GJ_MU] - det_sqrt(it_call) / 0.05 * st[GJ_HBAR]);
-            st[GJ_EPS] = half_lanef(ex, 0);
-            eta = half_lanef(ex, 1);
+            st[GJ_EPS] = Lay::half_lanef(ex, 0, hh);
+            eta = Lay::half_lanef(ex, 1, hh);
             st[GJ_EPSBAR] = det_exp((1.0 - eta) * log_epsbar + eta * det_log(st[GJ_EPS]));
         } else {
-            st[GJ_EPS] = st[GJ_EPSBAR];
+            st[GJ_EPS] = det_exp(st[GJ_MU] - det_sqrt(it_call) / 0.05 * st[GJ_HBAR]);
+            eta = det_exp(-0.75 * det_log(it_call));
+            st[GJ_EPSBAR] = det_exp((1.0 - eta) * det_log(st[GJ_EPSBAR]) + eta * det_log(st[GJ_EPS]));
         }
         qout = tab_vec<GJT_BACKWARD>(nullptr, sample);
         return logp0 - lnprob;                                           // undoes the outer Hastings ratio (NJ:838)
@@ -1467,9 +1139,9 @@ constexpr int GJ_BLOCK = 64;
 #ifndef PTMI_GJ_WPE
 #define PTMI_GJ_WPE 2
 #endif
-// PAIR (4-lane shapes, diagonal whitening, iso / curved families): two gradient jumps at a time, a half-wave each (GradJumpPair)
+// PAIR (4-lane shapes, diagonal whitening, iso / curved families): two gradient jumps at a time, a half-wave each (GjHalves)
 // W16 (the 16-lane shape at ndim <= 64): a gradient jump takes the whole wave there too
-// (GradJumpWide<16, LOGL, 16>: one element per lane instead of seven slots of every vector in each of the chain's 16 lanes)
+// (GjQuads: one element per lane instead of seven slots of every vector in each of the chain's 16 lanes)
 // GRP: parameter groups (PT:129-145).  SCAM / AM / DE move one group's parameters with that group's tables (propose() draws the group
 // and picks the table, [walker or 0][group] as in the GRP step kernels of ptmi_mh.inc.h); a NUTS / HMC pick moves every parameter with
 // the whitening tables of the full initial covariance and never looks at a group (PT:225-258; the oracle's mh_one takes g = 0 there).
@@ -1482,11 +1154,12 @@ __global__ __launch_bounds__(GJ_BLOCK, ((G == 4 && EPL <= 5) || W16) ? PTMI_GJ_W
     static_assert(!W16 || (G == 16 && !PAIR), "the 16-group whole-wave layout serves the 16-lane shape");
     static_assert(!GRP || (!PAIR && !W16), "parameter groups run the default layout of their lane width");
     constexpr int CPB = GJ_BLOCK / G;
-    constexpr bool WIDE = G == 4 || W16;         // a gradient jump takes the whole wave (GradJumpWide)
-    constexpr int WEPL = W16 ? 16 : EPL, WNS = W16 ? 4 : EPL;          // GradJumpWide's EPL (LD / 4); slots of a lane that hold elements in its layout
+    constexpr bool WIDE = G == 4 || W16;         // a gradient jump takes the whole wave, in the layout Wide
+    using Wide = std::conditional_t<W16 != 0, GjQuads<W16 == 2>, GjRows16<EPL>>;
+    constexpr int WEPL = W16 ? 16 : EPL, WNS = W16 ? 4 : EPL;          // Wide's LD / 4; slots of a lane that hold elements in its layout
     const int d = a.d, nt = a.nt;
     const long long nch = (long long)a.W * nt;
-    if (WIDE && W16 != 2) {                      // (W16 with full whitening tables: they stay in global memory, GradJumpWide::tab_vec)
+    if (WIDE && W16 != 2) {                      // (W16 with full whitening tables: they stay in global memory, GjQuads::tab_product)
         constexpr int LD = 4 * WEPL;
         if (a.gj_diag) {                         // diagonal whitening: the three diagonals (3 LD doubles instead of 3 LD^2: 0.5 KB instead of 9.6 KB at d = 20)
             for (int i = (int)threadIdx.x; i < 3 * LD; i += GJ_BLOCK) {
@@ -1599,7 +1272,7 @@ __global__ __launch_bounds__(GJ_BLOCK, ((G == 4 && EPL <= 5) || W16) ? PTMI_GJ_W
                 double qw = 0.0, qxy_c = 0.0;
                 if (on) {
                     double *stc = gj_lds + stl + 2 * lane0;                  // the chain's eight words (its four lanes' pairs)
-                    GradJumpPair<EPL, LOGL> gj(a, ch_c, beta_c, it, sid_c, xch);
+                    GradJumpLanes<GjHalves<EPL>, LOGL> gj(a, ch_c, beta_c, it, sid_c, xch);
                     double st[GJ_NSTATE];
 #pragma unroll
                     for (int j = 0; j < GJ_NSTATE; ++j) st[j] = stc[j];
@@ -1648,7 +1321,7 @@ __global__ __launch_bounds__(GJ_BLOCK, ((G == 4 && EPL <= 5) || W16) ? PTMI_GJ_W
                 const int w_c = (int)(ch_c / nt), t_c = __builtin_amdgcn_readlane(t, lane0);
                 double *stc = a.gj + ((size_t)w_c * nt + t_c) * GJ_NSTATE;
                 double qw;
-                GradJumpWide<WEPL, LOGL, W16 ? 16 : 4, W16 == 2> gj(a, ch_c, beta_c, it, sid_c, xch);
+                GradJumpLanes<Wide, LOGL> gj(a, ch_c, beta_c, it, sid_c, xch);
                 double st[GJ_NSTATE];
 #pragma unroll
                 for (int j = 0; j < GJ_NSTATE; ++j) st[j] = stc[j];

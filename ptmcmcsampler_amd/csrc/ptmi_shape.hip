@@ -37,7 +37,7 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
         if constexpr (E <= 8) {                 // the tree build keeps seven chain vectors in registers
             const long long nch = a.gj_order ? (long long)a.gj_nslots : (long long)h->cfg.nwalkers * h->cfg.ntemps;     // chain slots of the launch
             const int cpb = GJ_BLOCK / G;
-            // LDS of a block (one wave).  4-lane shapes (GradJumpWide): whitening tables with rows of 4 E | the tree stack,
+            // LDS of a block (one wave).  4-lane shapes (GradJumpLanes over GjRows16 / GjHalves): whitening tables with rows of 4 E | the tree stack,
             // one level per height | the exchange area of the layout change (64 doubles) | box bounds of the 4-lane test.
             // Wider shapes: lowest levels of the tree stack | box bounds.
             size_t off = 0;
@@ -52,12 +52,12 @@ int PTMI_CAT(PTMI_G, PTMI_E, PTMI_L)(int op, ptmi_engine *h, KArgs &a, int grid,
                 int levels = h->cfg.nuts_maxdepth + 1 < 11 ? h->cfg.nuts_maxdepth + 1 : 11;    // heights 0..10 in LDS, the rest in global scratch
                 if (lv < levels) levels = lv;
                 a.gj_lds_levels = levels;
-                // two jumps at a time, a half-wave each (GradJumpPair): diagonal whitening, no dense products; PTMI_GJ_NOPAIR: the
+                // two jumps at a time, a half-wave each (GjHalves): diagonal whitening, no dense products; PTMI_GJ_NOPAIR: the
                 // one-chain-per-wave layout (a test hook, same results)
                 pair = a.gj_diag && L != PTMI_LOGL_DENSE && !grp && !ptmi_env("PTMI_GJ_NOPAIR", 0);
                 off += (size_t)(pair ? 2 : 1) * a.gj_lds_levels * gjw_level_doubles(E) + (pair ? 72 + 2 * GJ_BLOCK : 64);       // pair: + the 16 chains' step-size states
             } else if (G == 16 && a.d <= 64 && !grp && !ptmi_env("PTMI_GJ_NOWIDE16", 0)) {
-                // the 16-lane shape at ndim <= 64: a gradient jump takes the whole wave (GradJumpWide<16, L, 16>, one element per lane);
+                // the 16-lane shape at ndim <= 64: a gradient jump takes the whole wave (GjQuads, one element per lane);
                 // PTMI_GJ_NOWIDE16: the per-chain layout (a test hook, same results)
                 w16 = true;
                 off = a.gj_diag ? (size_t)(3 * 64) : 0;                     // the three diagonals (full tables stay in global memory)

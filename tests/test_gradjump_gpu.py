@@ -56,7 +56,7 @@ CASES = [
     dict(d=130, nt=2, W=2, logl=("interval", 0.0, 10.0), logp=("flat",), grad_weights=(10, 10), weights=(10, 0, 0), hmc=(0.2, 2, 20), diag=True),
     dict(d=40, nt=3, W=4, logl=("interval", 0.0, 10.0), logp=("flat",), grad_weights=(0, 0), weights=(10, 10, 10)),
     # the 16-lane shape at ndim <= 64 with a diagonal covariance: a gradient jump takes the whole wave, one element per lane, the chain's 16
-    # lane groups in the wave's quads (GradJumpWide<16, L, 16>; the reference's test_nuts covariance -- from the Hessian of a target that
+    # lane groups in the wave's quads (GradJumpLanes over GjQuads; the reference's test_nuts covariance -- from the Hessian of a target that
     # factorizes -- is diagonal); the boundaries 33 and 64, a box prior, the curved family's partner lanes, a tree cap
     dict(d=40, nt=2, W=5, logl=("interval", 0.0, 10.0), logp=("flat",), grad_weights=(10, 10), weights=(10, 10, 10), hmc=(0.4, 2, 100), diag=True),
     dict(d=33, nt=3, W=3, logl=("iso",), logp=("box", -3.0, 3.0), grad_weights=(20, 5), weights=(5, 0, 5), diag=True),
