@@ -121,8 +121,10 @@ def test_device_exchange_with_emulated_ranks(nranks, cov_mode, ntb):
         assert engines[0].neighbour_swaps < n // 10           # 33 walkers on three-rank blocks: some sweep always crosses one
 
 
-def _run_emulated_ladder(nranks, ntb, d, W, n, cov0, p0, kw):
-    """One thread per temperature block on the one GPU (thread_comm.ThreadComm) + the whole ladder on the oracle."""
+def _run_emulated_ladder(nranks, ntb, d, W, n, cov0, p0, kw, ref=None, comm=None):
+    """One thread per temperature block on the one GPU (thread_comm.ThreadComm) + the whole ladder on the oracle.  ``ref``: a
+    reference that has run already (tests/test_sharded_modes_gpu.py: one the oracle cannot make from ``kw`` alone); ``comm``: the
+    ranks' communicator class, a ThreadComm."""
     import sys
     import threading
     sys.path.insert(0, __import__("os").path.dirname(__file__))
@@ -130,15 +132,17 @@ def _run_emulated_ladder(nranks, ntb, d, W, n, cov0, p0, kw):
     from oracle import oracle as orc
     from ptmcmcsampler_amd.sharded import ShardedPTEngine
     ntg = ntb * nranks
-    ref = orc.OracleEngine(d, ntg, W, cov0, **kw)
-    ref.init_state(p0)
-    ref.run(n)
+    if ref is None:
+        ref = orc.OracleEngine(d, ntg, W, cov0, **kw)
+        ref.init_state(p0)
+        ref.run(n)
     world = ThreadWorld(nranks)
     engines, errs = [None] * nranks, []
+    comm = ThreadComm if comm is None else comm
 
     def rank_main(r):
         try:
-            e = ShardedPTEngine(d, ntg, W, cov0, comm=ThreadComm(world, r), **kw)
+            e = ShardedPTEngine(d, ntg, W, cov0, comm=comm(world, r), **kw)
             assert e.device_exchange
             engines[r] = e
             e.init_state(p0)
@@ -310,7 +314,8 @@ def test_sharded_ladder_with_the_owner_factorizing_on_its_side_stream(eig_mode, 
 
 def test_two_real_processes_share_the_gpu_over_gloo():
     """True multi-process run of ShardedPTEngine + DistComm (two ranks on cuda:0, gloo moving device tensors),
-    both swap modes, against the oracle: tools/two_proc_one_gpu.py."""
+    both swap modes, and the device QL factorization on the owner's stream with the broadcast of its table right behind it (pooled,
+    eig_lag = 0: no device-wide synchronisation around the collective here), against the oracle: tools/two_proc_one_gpu.py."""
     import os
     import subprocess
     import sys
